@@ -13,7 +13,11 @@ selector sees N x 3,520 frames with budget 1200 -- at N = 8 that is the full nuS
 (704 scenes, 28,160 frames).  Point clouds are synthetic and resident in HBM before the timed
 region; weights are seeded random-init (no checkpoints offline).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+--dump-outputs DIR writes what the last timed step returned (rank 0): embeddings.npy (the swept 512-d BEV embeddings,
+float32; a fixed seeded row sample, with its row indices in embeddings_rows.npy, when the whole array would exceed
+DUMP_EMBED_BYTES) and selected.npy (the selected frame indices in pick order, float64).  Inputs and weights are seeded,
+so two builds run with the same arguments can be compared output for output.
 N > 1: either under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (the driver's way), or
 plain `python bench.py --gpus N`, which starts that launcher itself as a child process; `--gpus N` under a WORLD_SIZE that
 is not N is refused, and so is a run whose all-reduce counts a different number of ranks (launch_or_refuse).
@@ -43,6 +47,7 @@ HBM_PEAK_GBS = 8000.0             # MI355X_MICROARCH.md: HBM3E ~8 TB/s
 DENSE_GFLOP_PER_FRAME = 67.6      # neck 63.7 + heads 3.96 (2*MAC, fp32)
 MFMA_F32_PEAK_TFLOPS = 157.3      # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 dense peak
 MFMA_BF16_PEAK_TFLOPS = 2500.0    # MI355X_MICROARCH.md: dense bf16 MFMA peak (no sparsity)
+DUMP_EMBED_BYTES = 48 << 20       # --dump-outputs: above this the embeddings are written as a seeded row sample
 
 
 def parse():
@@ -66,10 +71,28 @@ def parse():
                          "value_bevfusion_camera_lidar = configs[4])")
     ap.add_argument("--no-extra-math", action="store_true",
                     help="skip the one extra step (outside the timed region) under AL3D_MATH=bf16x6 (value_bf16x6)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs as DIR/<name>.npy (rank 0)")
     ap.add_argument("--launch-check", action="store_true",
                     help="launcher rehearsal (no GPU needed): rendezvous, count the ranks, print a line with value null "
                          "and \"launch_check\": true, exit -- what tests/test_bench_launcher.py runs over gloo")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+def dump_outputs(out_dir, feats, selected):
+    """The last timed step's results as a caller of the hot path receives them: the embeddings and the picks."""
+    os.makedirs(out_dir, exist_ok=True)
+    emb = feats.detach().to("cpu", torch.float32).numpy()
+    if emb.nbytes > DUMP_EMBED_BYTES:
+        n_rows = DUMP_EMBED_BYTES // (emb.shape[1] * emb.itemsize)
+        rows = np.sort(np.random.default_rng(0).choice(emb.shape[0], size=n_rows, replace=False))
+        emb = emb[rows]
+        np.save(os.path.join(out_dir, "embeddings_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "embeddings.npy"), np.ascontiguousarray(emb))
+    np.save(os.path.join(out_dir, "selected.npy"), np.asarray(list(selected), dtype=np.float64))
 
 
 def launch_or_refuse(args):
@@ -671,6 +694,8 @@ def main():
         verified = None if args.no_verify else verify_selection(infos, state["feats"], state["selected"])
         first_selected = list(state["selected"])
         first_feats = state["feats"]
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, first_feats, first_selected)
         out = {
             "metric": "unlabeled frames scored+selected/sec (whole node; 40 frames = 1 scene); "
                       + {True: "selected set equals the CPU oracle's", False: "SELECTED SET DIFFERS FROM THE CPU ORACLE",
