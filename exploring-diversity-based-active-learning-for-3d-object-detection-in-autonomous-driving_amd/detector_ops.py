@@ -68,10 +68,15 @@ def split_f16x3(w_packed, scale=None):
 #            neck + head and in the sparse encoder
 #   "bf16x6" fp32-faithful six-product split on the bf16 matrix cores everywhere (full fp32 range)
 #   "f32"    fp32-input MFMA (bitwise an fp32 FMA chain)
+#   "auto"   f16x3, and the sweep re-runs under bf16x6 each batch whose embeddings left the f16x3 range
+#            (MATH reads "f16x3", MATH_AUTO is set: sweep.sweep_embeddings(recover_range=None))
 import os as _os
 MATH = _os.environ.get("AL3D_MATH", "f16x3")
+MATH_AUTO = MATH == "auto"
+if MATH_AUTO:
+    MATH = "f16x3"
 if MATH not in ("f16x3", "bf16x6", "f32"):
-    raise lib.Al3dError(f"AL3D_MATH={MATH!r}: expected f16x3, bf16x6 or f32")
+    raise lib.Al3dError(f"AL3D_MATH={MATH!r}: expected f16x3, bf16x6, f32 or auto")
 
 
 def sparse_math():
@@ -579,6 +584,19 @@ def gap_nhwc(x):
     out = torch.empty((B, C), dtype=torch.float32, device=x.device)
     ws = torch.empty((B, H, C), dtype=torch.float32, device=x.device)
     lib.call("al3d_gap_nhwc_f32", _ptr(x), B, H, W, C, _ptr(out), _ptr(ws), _stream())
+    return out
+
+
+def rows_nonfinite(x, out=None):
+    """[rows, cols] f32 device rows (row stride may exceed cols) -> uint8 [rows]: 1 where a row holds an inf or NaN."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2:
+        raise lib.Al3dError("rows_nonfinite: expected a [rows, cols] float32 device tensor")
+    if x.shape[1] and x.stride(1) != 1:
+        x = x.contiguous()
+    rows, cols = x.shape
+    if out is None:
+        out = torch.empty((rows,), dtype=torch.uint8, device=x.device)
+    lib.call("al3d_rows_nonfinite_u8", _ptr(x), rows, cols, max(x.stride(0), cols), _ptr(out), _stream())
     return out
 
 

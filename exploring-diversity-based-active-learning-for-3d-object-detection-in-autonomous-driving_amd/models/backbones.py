@@ -100,8 +100,17 @@ class _SparseEncoderBase(nn.Module):
 
     def _prepare(self, device):
         """Pack weights / fold BN once per device (eval only)."""
-        if getattr(self, "_packed_dev", None) == (device, D.MATH, D.SPCONV, D.L0, tuple(sorted(D.R16_COUTS)),
-                                                  tuple(sorted(D.BLK_PAIRS))):
+        key = (device, D.MATH, D.SPCONV, D.L0, tuple(sorted(D.R16_COUTS)), tuple(sorted(D.BLK_PAIRS)))
+        if getattr(self, "_packed_dev", None) == key:
+            return
+        # one pack per arithmetic (see RPN._prepare).  The level grids do not depend on the pack and every call leaves
+        # them clean: a new pack keeps them
+        packs = self.__dict__.setdefault("_packs", {})
+        if getattr(self, "_packed_dev", None) is None:
+            packs.clear()
+        if key in packs:
+            self._plan, self._raster_ok = packs[key]
+            self._packed_dev = key
             return
         plan = []
         # The input level's rows may be renumbered (raster order, csrc/spconv_l0.hip) only if they never leave the encoder:
@@ -136,8 +145,9 @@ class _SparseEncoderBase(nn.Module):
                     i += 1
             plan.append(dict(kind="stage_end"))
         self._plan = plan
-        self._packed_dev = (device, D.MATH, D.SPCONV, D.L0, tuple(sorted(D.R16_COUTS)), tuple(sorted(D.BLK_PAIRS)))
-        self._levels = {}
+        packs[key] = (plan, self._raster_ok)
+        self._packed_dev = key
+        self.__dict__.setdefault("_levels", {})
 
     @staticmethod
     def _pad_cin(m):

@@ -133,7 +133,16 @@ class MultiGroupHead(nn.Module):
 
     # ------------------------------------------------------------ fused 1x1 convs
     def _prepare(self, device):
-        if getattr(self, "_packed_dev", None) == (device, D.MATH, D.DENSE):
+        key = (device, D.MATH, D.DENSE)
+        if getattr(self, "_packed_dev", None) == key:
+            return
+        # one pack per arithmetic (see RPN._prepare)
+        packs = self.__dict__.setdefault("_packs", {})
+        if getattr(self, "_packed_dev", None) is None:
+            packs.clear()
+        if key in packs:
+            self._box_off, self._cls_off, self._ch, self._w, self._wscale, self._b = packs[key]
+            self._packed_dev = key
             return
         # channel order of the fused output: the box regressions of all tasks, then the class logits of all tasks.
         # The score pre-pass of the decode reads ONLY the class logits: kept together (36 of 236 channels for the six
@@ -155,7 +164,8 @@ class MultiGroupHead(nn.Module):
         self._w, self._wscale = D.pack_dense(
             D.pack_conv_weight(torch.cat([w.detach() for w in ws], dim=0)).to(device), None, 1, 1, 0)
         self._b = torch.cat([b.detach() for b in bs]).float().contiguous().to(device)
-        self._packed_dev = (device, D.MATH, D.DENSE)
+        packs[key] = (self._box_off, self._cls_off, self._ch, self._w, self._wscale, self._b)
+        self._packed_dev = key
 
     def accepts_pair(self, device):
         """True when the fused head convolution runs on the LDS-DMA kernel and can read pair pixels."""

@@ -70,7 +70,17 @@ class RPN(nn.Module):
                 nn.init.xavier_uniform_(m.weight)
 
     def _prepare(self, device):
-        if getattr(self, "_packed_dev", None) == (device, D.MATH, D.DENSE):
+        key = (device, D.MATH, D.DENSE)
+        if getattr(self, "_packed_dev", None) == key:
+            return
+        # one pack per arithmetic: a sweep that re-runs a batch under bf16x6 (AL3D_MATH=auto) flips back without re-packing.
+        # _packed_dev = None (never packed, or a caller asking for a fresh pack) drops them all
+        packs = self.__dict__.setdefault("_packs", {})
+        if getattr(self, "_packed_dev", None) is None:
+            packs.clear()
+        if key in packs:
+            self._blocks_p, self._deblocks_p = packs[key]
+            self._packed_dev = key
             return
         self._blocks_p, self._deblocks_p = [], []
         for blk in self.blocks:
@@ -97,7 +107,8 @@ class RPN(nn.Module):
                                         up.kernel_size[0], up.stride[0], 0)
                 self._deblocks_p.append(dict(deconv=False, w=w, scale=scale, shift=shift.to(device),
                                              k=up.kernel_size[0], s=up.stride[0]))
-        self._packed_dev = (device, D.MATH, D.DENSE)
+        packs[key] = (self._blocks_p, self._deblocks_p)
+        self._packed_dev = key
 
     def _kind(self, w):
         return getattr(w, "kind", None)

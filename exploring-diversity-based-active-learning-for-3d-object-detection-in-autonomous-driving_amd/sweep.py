@@ -5,7 +5,11 @@ New capability: under ``torch.distributed`` each rank sweeps the
 frames its sampler hands it and one RCCL all-gather restores the single-process
 ``[N,512]`` tensor in dataset order on every rank.
 """
+import logging
+
 import torch
+
+_log = logging.getLogger("al3d.sweep")
 
 
 def example_to_device(example, device, non_blocking=False):
@@ -146,32 +150,65 @@ def _tensors_of(obj):
                 yield from _tensors_of(v)
 
 
+# report of the last sweep_embeddings call on this rank: math, batches, recovered_batches (batch ordinals), tripped_frames
+# (dataset indices of the non-finite rows), recovered_frames (every frame of the re-run batches)
+LAST_SWEEP = {}
+
+
 def sweep_embeddings(detector, dataloader, device, num_frames=None, with_entropy=False,
-                     batch_local_weights=None):
+                     batch_local_weights=None, recover_range=None):
     """Run ``detector(example, return_loss=False, estimate=True)`` over the loader and
     return the ``[N,512]`` embeddings in dataset order (on ``device``).
 
     ``with_entropy``: also return the ``[N]`` per-frame mean box entropy
     (entropy_selector.py:72-75).  ``batch_local_weights``: UWE's second pass -- a ``[>=B]``
     tensor indexed by the position *inside the batch* that scales each embedding
-    (uwe_selector.py:96-99, quirk A.1 #8)."""
+    (uwe_selector.py:96-99, quirk A.1 #8).
+
+    ``recover_range`` (None: ``detector_ops.MATH_AUTO``, i.e. ``AL3D_MATH=auto``): under f16x3, flag every batch whose
+    raw embedding rows are not finite (one small kernel per batch, read behind the batch's completion event) and run
+    that batch again under bf16x6 (full fp32 range) in place; the report lands in ``LAST_SWEEP``."""
+    from . import detector_ops as D
     feats, index, ents = [], [], []
     seen = 0
+    on_gpu = torch.device(device).type == "cuda"
+    if recover_range is None:
+        recover_range = D.MATH_AUTO
+    recover = bool(recover_range) and on_gpu and D.MATH == "f16x3"
+    report = dict(math="auto" if recover else D.MATH, batches=0, recovered_batches=[], tripped_frames=[],
+                  recovered_frames=[])
+    LAST_SWEEP.clear()
+    checks = []                         # per batch awaiting its flags: (example, slot in feats, first row in index, flags)
+    timing = []                         # device start / end events of each re-run
     sampler_idx = None
     sampler = getattr(dataloader, "sampler", None)
     if sampler is not None and hasattr(sampler, "__iter__") and not isinstance(
             sampler, torch.utils.data.SequentialSampler):
         sampler_idx = list(iter(sampler))
-    def finish(example, preds, middle):
-        nonlocal seen
+    def outputs(preds, middle, check=False):
         emb = gap_embedding(middle[-1])
+        flags = None
+        if check:                       # on the raw embedding, before UWE's scaling (a weight of 0 would hide a row)
+            flags = torch.empty((emb.shape[0],), dtype=torch.uint8, pin_memory=True)
+            flags.copy_(D.rows_nonfinite(emb), non_blocking=True)
         if batch_local_weights is not None:
             from . import selector_ops as ops
             emb = ops.scale_rows(emb.contiguous(), batch_local_weights[: emb.shape[0]].contiguous())
+        ent = None
         if with_entropy:
-            ents.append(preds.frame_entropy() if hasattr(preds, "frame_entropy")
-                        else torch.stack([_entropy_of(p["scores"]) for p in preds]))
+            ent = (preds.frame_entropy() if hasattr(preds, "frame_entropy")
+                   else torch.stack([_entropy_of(p["scores"]) for p in preds]))
+        return emb, ent, flags
+
+    def finish(example, preds, middle):
+        nonlocal seen
+        emb, ent, flags = outputs(preds, middle, check=recover)
+        if with_entropy:
+            ents.append(ent)
+        if recover:
+            checks.append((example, len(feats), seen, flags))
         feats.append(emb)
+        report["batches"] += 1
         b = emb.shape[0]
         if sampler_idx is not None:
             index.extend(sampler_idx[seen:seen + b])
@@ -179,7 +216,41 @@ def sweep_embeddings(detector, dataloader, device, num_frames=None, with_entropy
             index.extend(range(seen, seen + b))
         seen += b
 
-    on_gpu = torch.device(device).type == "cuda"
+    def settle(main, side):
+        """The flags of the oldest unchecked batch are on the host (its completion event has been waited for): re-run
+        it under bf16x6 if any of its rows tripped.  Called before the loader is advanced."""
+        example, slot, first, flags = checks.pop(0)
+        bad = flags.numpy().nonzero()[0].tolist()
+        if not bad:
+            return
+        frames = index[first:first + feats[slot].shape[0]]
+        tripped = [frames[r] for r in bad]
+        _log.warning("batch %d: frame(s) %s left the f16x3 range; re-running frames %s under bf16x6",
+                     slot, tripped, frames)
+        if side is not None:
+            main.wait_stream(side)      # the encoder's level grids are shared with the next batch's index work
+        t = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        saved = D.MATH
+        D.MATH = "bf16x6"
+        try:
+            with torch.cuda.stream(main):
+                t[0].record(main)
+                # no `book`: the batch's rulebook was built for the f16x3 kernels (raster level 0, tiled tables)
+                preds, middle = detector(example, return_loss=False, estimate=True)
+                emb, ent, _ = outputs(preds, middle)
+                t[1].record(main)
+        finally:
+            D.MATH = saved
+        if side is not None:
+            side.wait_stream(main)
+        timing.append(t)
+        feats[slot] = emb
+        if with_entropy:
+            ents[slot] = ent
+        report["recovered_batches"].append(slot)
+        report["tripped_frames"] += tripped
+        report["recovered_frames"] += frames
+
     mode = PIPELINE if on_gpu else None
     if mode == "split" and not (hasattr(detector, "sparse_stage") and hasattr(detector, "dense_stage")):
         mode = "ahead"
@@ -191,6 +262,9 @@ def sweep_embeddings(detector, dataloader, device, num_frames=None, with_entropy
                 example = example_to_device(data_batch, device, non_blocking=False)
                 preds, middle = detector(example, return_loss=False, estimate=True)
                 finish(example, preds, middle)
+                if checks:
+                    torch.cuda.current_stream(device).synchronize()
+                    settle(torch.cuda.current_stream(device), None)
         else:
             # Software pipeline over batches.  The work of the batch that is due on the caller's
             # stream is enqueued FIRST (it contains no host synchronisation), then the host turns to
@@ -212,7 +286,7 @@ def sweep_embeddings(detector, dataloader, device, num_frames=None, with_entropy
             # it when the NEXT batch's sparse encoder is through, like the index work above
             nms_head = getattr(detector, "bbox_head", None)
             if not (NMS_AFTER_SPARSE and mode == "ahead" and SIDE_AFTER_SPARSE and hasattr(detector, "dense_stage")
-                    and hasattr(nms_head, "flush_deferred")) or with_entropy:
+                    and hasattr(nms_head, "flush_deferred")) or with_entropy or recover:
                 nms_head = None
             if nms_head is not None:
                 nms_head.defer_nms = True
@@ -235,6 +309,8 @@ def sweep_embeddings(detector, dataloader, device, num_frames=None, with_entropy
                           preds, middle = detector.dense_stage(example, x, middle, estimate=True)
                       elif mode == "ahead":
                           bb = getattr(detector, "backbone", None)
+                          if recover:             # a re-run batch would fire the hook too
+                              bb = None
                           if SIDE_AFTER_STAGE >= 0 and bb is not None:
                               def _hook(k, _side=side, _main=main):
                                   if k == SIDE_AFTER_STAGE:
@@ -259,6 +335,8 @@ def sweep_embeddings(detector, dataloader, device, num_frames=None, with_entropy
                   # otherwise prepare (and keep alive) every remaining batch of the pool at once
                   while len(done) > 1:
                       done.pop(0).synchronize()
+                      if checks:
+                          settle(main, side)
                   with torch.cuda.stream(side):
                       try:
                           data_batch = next(it)
@@ -277,6 +355,9 @@ def sweep_embeddings(detector, dataloader, device, num_frames=None, with_entropy
                 if nms_head is not None:        # the last batch's launch; later predict() calls launch at once again
                     nms_head.defer_nms = False
                     nms_head.flush_deferred()
+            while checks:                       # the last batch's flags
+                done.pop(0).synchronize()
+                settle(main, side)
             main.wait_stream(side)
             if main is not caller:
                 caller.wait_stream(main)
@@ -286,21 +367,31 @@ def sweep_embeddings(detector, dataloader, device, num_frames=None, with_entropy
     idx = torch.as_tensor(index, dtype=torch.int64, device=local.device)
     n = num_frames if num_frames is not None else int(idx.max().item()) + 1
     out = gather_in_dataset_order(local, idx, n)
+    for _, t1 in timing:                # host waits only when a batch was re-run
+        t1.synchronize()
+    report["recovery_ms"] = [float(t0.elapsed_time(t1)) for t0, t1 in timing]
+    LAST_SWEEP.update(report)
     # checked AFTER the collective, on the gathered tensor: every rank sees the same rows, so all
     # ranks raise together instead of one rank leaving the others inside the all-gather
-    _check_range(out)
+    _check_range(out, recovered=recover)
     if with_entropy:
         e = gather_in_dataset_order(torch.cat(ents).unsqueeze(1), idx, n).squeeze(1)
         return out, e
     return out
 
 
-def _check_range(local):
+def _check_range(local, recovered=False):
     """f16x3 arithmetic carries activations below 65504 only; anything larger turns into inf/NaN in
-    the layer's output and from there into the frame's embedding.  One reduction per sweep."""
+    the layer's output and from there into the frame's embedding.  One reduction per sweep.
+    ``recovered``: the sweep already re-ran every tripped batch under bf16x6 (``local`` in dataset order)."""
     from . import detector_ops as D
     from .lib import Al3dError
     if D.MATH == "f16x3" and local.numel() and not bool(torch.isfinite(local).all()):
+        if recovered:
+            rows = (~torch.isfinite(local).all(dim=1)).nonzero().flatten().tolist()
+            raise Al3dError(f"{len(rows)} frame embedding(s) are not finite and not recoverable: they stay non-finite "
+                            f"under AL3D_MATH=bf16x6 too (non-finite input, or a module without bf16x6 kernels); "
+                            f"frames {rows}")
         bad = int((~torch.isfinite(local).all(dim=1)).sum())
         raise Al3dError(f"{bad} frame embedding(s) are not finite: an activation left the f16x3 range "
                         "(|x| < 65504); rerun with AL3D_MATH=bf16x6 (full fp32 range)")

@@ -551,6 +551,10 @@ int al3d_gap_reduce_parts_f32(const float* gap_part, int B, int parts, int C, in
 int64_t al3d_gap_workspace_bytes(int B, int H, int C);
 int al3d_gap_nhwc_f32(const float* x, int B, int H, int W, int C, float* out, void* workspace,
                       void* stream);
+/* Per-row range check of the sweep's embeddings (AL3D_MATH=auto; replaces, per batch, sweep.py's _check_range over the
+ * gathered pool): flags[r] = 1 if any of x[r*ld + 0..cols) is inf or NaN (exponent bits all ones), else 0.  One wave64
+ * per row, float4 loads when x is 16-byte aligned and ld % 4 == 0.  rows >= 0, 1 <= cols <= ld. */
+int al3d_rows_nonfinite_u8(const float* x, int rows, int cols, int ld, uint8_t* flags, void* stream);
 
 /* ---------------------------------------------------------------- camera branch: BEV pooling (f4)
  * bevfusion/mmdet3d/models/vtransforms/base.py:127-163 (`bev_pool`: cell = ((geom - (bx - dx/2)) / dx).long(),

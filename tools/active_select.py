@@ -159,6 +159,12 @@ def main():
     selector = build_selector(dict(sel_cfg))
     logger.info("begin selection")
     selector.select_samples(local_rank=local_rank)
+    if args.pred:
+        from al3d import sweep as S
+        rep = S.LAST_SWEEP
+        if rep.get("math") == "auto":   # AL3D_MATH=auto: batches this rank re-ran under bf16x6
+            print(f"rank {rank}: {len(rep['recovered_batches'])} of {rep['batches']} batches recovered under bf16x6 "
+                  f"(frames {rep['tripped_frames']} left the f16x3 range)", flush=True)
     selector.dump_file()
 
 
