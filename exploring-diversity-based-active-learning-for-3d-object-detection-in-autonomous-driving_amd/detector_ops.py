@@ -79,10 +79,6 @@ if MATH not in ("f16x3", "bf16x6", "f32"):
     raise lib.Al3dError(f"AL3D_MATH={MATH!r}: expected f16x3, bf16x6, f32 or auto")
 
 
-def sparse_math():
-    """Arithmetic of the sparse encoder under the current MATH."""
-    return MATH
-
 
 # structure of the f16x3 dense kernels: "auto" = 3x3/s1 layers on the fragment-streamed halo kernel, every other
 # geometry (stride-2 entry, 1x1 / deconv deblocks, fused head) on the LDS-DMA kernel; "stream" = round 1's policy
@@ -168,17 +164,9 @@ def wino_ok(cout, cin, ksize, stride, pad):
     return (ksize, stride, pad) == (3, 1, 1) and cout % 64 == 0 and cin % 16 == 0
 
 
-class GldsPacked:
-    """f16x3 sparse-conv weights in the LDS image order of the DMA-gather kernel
-    (al3d_sp_pack_glds_f16x3: [K][Cin/16][2][ceil32(Cout)][16] f16, halves swizzled)."""
-    dtype = torch.float16
-
-    def __init__(self, data, cout, K, cin):
-        self.data, self.cout, self.K, self.cin = data, cout, K, cin
-
-
 def pack_glds_f16x3(planes):
-    """f16 planes [2,Cout,K,Cin] (split_f16x3 of the [Cout,K,Cin] weights) -> GldsPacked."""
+    """f16 planes [2,Cout,K,Cin] (split_f16x3 of the [Cout,K,Cin] weights) -> the LDS image order of the DMA-gather
+    kernels (al3d_sp_pack_glds_f16x3: [K][Cin/16][2][ceil32(Cout)][16] f16, halves swizzled)."""
     planes = _dev(planes, torch.float16, "planes")
     _, cout, K, cin = planes.shape
     n = lib.load().al3d_sp_pack_glds_f16x3_elems(cout, K, cin)
@@ -186,7 +174,7 @@ def pack_glds_f16x3(planes):
         raise lib.Al3dError(f"pack_glds_f16x3: unsupported shape Cout={cout} K={K} Cin={cin}")
     out = torch.empty((n,), dtype=torch.float16, device=planes.device)
     lib.call("al3d_sp_pack_glds_f16x3", _ptr(planes), cout, K, cin, _ptr(out), _stream())
-    return GldsPacked(out, cout, K, cin)
+    return out
 
 
 def frag_ok(cout, cin, ksize, stride, pad):
@@ -255,13 +243,6 @@ if _os.environ.get("AL3D_RNG_PAIRS") is not None:   # dev override, e.g. "32x32,
     RNG_PAIRS = {tuple(int(v) for v in t.split("x")) for t in _os.environ["AL3D_RNG_PAIRS"].split(",") if t}
 
 
-def sparse_rng(cin, cout):
-    """True when the 27-tap submanifold f16x3 layer cin -> cout runs on the range-gather kernel."""
-    if MATH != "f16x3" or SPCONV not in ("auto", "rng"):
-        return False
-    return (cin, cout) in (RNG_BUILT if SPCONV == "rng" else RNG_PAIRS & RNG_BUILT)
-
-
 # Block-staged kernel (csrc/spconv_blk.hip): 27-tap submanifold layers of these channel pairs stage the union of a
 # 128-row chunk's neighbourhoods once; the encoder then numbers the level's rows column by column
 # (al3d_sp_down_sites_blocked).  Built, bit-identical, and MEASURED SLOWER than the range / per-tap kernels on lidar
@@ -289,16 +270,6 @@ if _os.environ.get("AL3D_MASK_SORT_WINDOWS"):
 
 
 BLK_ORDER_ONLY = _os.environ.get("AL3D_BLK_ORDER_ONLY", "0") == "1"   # dev: column order for these pairs' levels, old kernels
-
-
-def sparse_blk_order(cin, cout, K=27):
-    """True when the level whose 27-tap submanifold layers are cin -> cout is numbered column by column."""
-    return MATH == "f16x3" and SPCONV == "auto" and K == 27 and (cin, cout) in (BLK_PAIRS & BLK_BUILT)
-
-
-def sparse_blk(cin, cout, K=27):
-    """True when the 27-tap submanifold f16x3 layer cin -> cout runs on the block-staged kernel."""
-    return sparse_blk_order(cin, cout, K) and not BLK_ORDER_ONLY
 
 
 class BlkPlan:
@@ -349,22 +320,9 @@ def sparse_raster():
     return MATH == "f16x3" and SPCONV == "auto" and L0 == "raster"
 
 
-def sparse_r16(cin, cout, K=27):
-    """True when the 27-tap f16x3 layer 16 -> cout runs on the item-stream kernel."""
-    return sparse_raster() and cin == 16 and K == 27 and cout in R16_COUTS
-
-
-class R16Packed:
-    """f16x3 weights of a 16-input-channel 27-tap layer as the item-stream kernel's LDS image
-    (al3d_sp_pack_r16_f16x3: [27][2 planes][2 k-halves][Cout][8] f16)."""
-    dtype = torch.float16
-
-    def __init__(self, data, cout):
-        self.data, self.cout, self.K, self.cin = data, cout, 27, 16
-
-
 def pack_r16_f16x3(planes):
-    """f16 planes [2,Cout,27,16] (split_f16x3 of the [Cout,27,16] weights) -> R16Packed."""
+    """f16 planes [2,Cout,27,16] (split_f16x3 of the [Cout,27,16] weights) -> the item-stream kernel's LDS image
+    (al3d_sp_pack_r16_f16x3: [27][2 planes][2 k-halves][Cout][8] f16)."""
     planes = _dev(planes, torch.float16, "planes")
     _, cout, K, cin = planes.shape
     n = lib.load().al3d_sp_pack_r16_f16x3_elems(cout)
@@ -372,7 +330,7 @@ def pack_r16_f16x3(planes):
         raise lib.Al3dError(f"pack_r16_f16x3: unsupported shape Cout={cout} K={K} Cin={cin}")
     out = torch.empty((n,), dtype=torch.float16, device=planes.device)
     lib.call("al3d_sp_pack_r16_f16x3", _ptr(planes), cout, _ptr(out), _stream())
-    return R16Packed(out, cout)
+    return out
 
 
 def raster_perm(coords, batch, shape, frame_rows_max=0):
@@ -422,14 +380,152 @@ def tile_items(nbr, n_out, tmask):
     return first, items
 
 
-def sparse_glds(cin=None, cout=None):
-    """True when the f16x3 sparse layer cin -> cout gets the LDS-DMA kernels' weight image (no arguments: any layer
-    may): the per-tap gather kernel, or the range-gather kernel where sparse_rng says so."""
-    if MATH != "f16x3" or SPCONV not in ("auto", "glds", "rng"):
-        return False
-    if cin is None or SPCONV == "glds":
-        return True
-    return (cin, cout) in GLDS_PAIRS or sparse_rng(cin, cout)
+# ------------------------------------------------------------------ sparse-conv dispatch (the encoder and sparse_conv_layer)
+# The 3-D layers the matrix-core kernels are built for (others, e.g. 5 -> 16 in f32, run on the VALU kernel)
+MFMA_PAIRS = {(16, 16), (16, 32), (32, 32), (32, 64), (64, 64), (64, 128), (128, 128)}
+
+# structure -> (al3d_sp_conv_* entry point, weight format, tiled table, side data).  Weight formats (sparse_pack): "kic" f32
+# [K,Cin,Cout], "oki" f32 [Cout,K,Cin], "bf16x6" planes (split_bf16x3), "f16x3" planes (split_f16x3), "glds"
+# (pack_glds_f16x3), "r16" (pack_r16_f16x3).  Tiled tables (pitched, + per-tile tap masks) are read by the f16x3 kernels
+# with an io argument, and only those read and write pair rows.  Side data, built once per table (sparse_side): "trng"
+# (al3d_sp_tile_ranges), "plan" (block_plan), "items" (tile_items).
+SPARSE = {
+    False: ("al3d_sp_conv_f32", "kic", False, None),
+    True: ("al3d_sp_conv_mfma_f32", "oki", False, None),
+    "bf16x6": ("al3d_sp_conv_bf16x6", "bf16x6", False, None),
+    "wave": ("al3d_sp_conv_wave_bf16x6", "bf16x6", False, None),
+    "wave2": ("al3d_sp_conv_wave2_bf16x6", "bf16x6", False, None),
+    "wave2_f16x3": ("al3d_sp_conv_wave2_f16x3", "f16x3", False, None),
+    "wave2_f16x3_tiles": ("al3d_sp_conv_wave2_f16x3_tiles_io", "f16x3", True, None),
+    "glds_f16x3": ("al3d_sp_conv_glds_f16x3_io", "glds", True, None),
+    "rng_f16x3": ("al3d_sp_conv_rng_f16x3", "glds", True, "trng"),
+    "blk_f16x3": ("al3d_sp_conv_blk_f16x3", "glds", True, "plan"),
+    "r16_f16x3": ("al3d_sp_conv_r16_f16x3", "r16", True, "items"),
+}
+# the table arguments of a tiled kernel between the pitch and K
+_SIDE_ARGS = {None: lambda t: (t["tmask"],), "trng": lambda t: (t["tmask"], t["trng"]),
+              "plan": lambda t: (t["tmask"], t["plan"].hdr, t["plan"].rows, t["plan"].loc),
+              "items": lambda t: (t["items"][1], t["items"][0])}
+
+
+def sparse_structure(cin, cout, K, subm, raster_ok):
+    """(structure, input width, column order) of the sparse layer cin -> cout with K taps under the current settings.
+    A narrow first layer (5 -> 16) runs zero-padded to 16 input channels on the matrix cores (not in f32).  raster_ok: the
+    layer may read raster-ordered rows (the encoder's renumbered level 0: the item-stream kernel).  Column order: the
+    level this submanifold layer reads is numbered column by column (the block-staged kernel, or AL3D_BLK_ORDER_ONLY)."""
+    if MATH != "f32" and cin < 16 and (16, cout) in MFMA_PAIRS:
+        cin = 16
+    pair = (cin, cout)
+    if pair not in MFMA_PAIRS:
+        return False, cin, False
+    if MATH == "f32":
+        return True, cin, False
+    if MATH == "bf16x6":
+        # measured per channel pair on the real rulebooks (tools/bench_splayers.py): the software-pipelined wave kernel
+        # wins everywhere; "wave" / "tile" select the older structures (same bits)
+        return {"wave": "wave", "tile": "bf16x6"}.get(SPCONV, "wave2"), cin, False
+    auto = SPCONV == "auto"
+    cols = auto and subm and K == 27 and pair in BLK_PAIRS & BLK_BUILT
+    rng = SPCONV in ("auto", "rng") and pair in (RNG_BUILT if SPCONV == "rng" else RNG_PAIRS & RNG_BUILT)
+    if raster_ok and sparse_raster() and cin == 16 and K == 27 and cout in R16_COUTS:
+        name = "r16_f16x3"
+    elif cols and not BLK_ORDER_ONLY:
+        name = "blk_f16x3"
+    elif rng and subm and K == 27:
+        name = "rng_f16x3"
+    elif SPCONV == "glds" or rng or (auto and pair in GLDS_PAIRS):
+        name = "glds_f16x3"
+    else:
+        name = "wave2_f16x3_tiles"
+    return name, cin, cols
+
+
+def sparse_pack(name, w, scale=None, cin=None):
+    """Weights [K,Cin,Cout] f32 (device) -> (weights in structure `name`'s format, the scale to hand it: the f16x3 split
+    folds its weight exponent into it).  cin > Cin: zero-padded input channels (sparse_structure's narrow first layer)."""
+    if cin is not None and cin != w.shape[1]:
+        w = torch.nn.functional.pad(w, (0, 0, 0, cin - w.shape[1]))
+    fmt = SPARSE[name][1]
+    if fmt == "kic":
+        return w.contiguous(), scale
+    w = w.permute(2, 0, 1).contiguous()
+    if fmt == "oki":
+        return w, scale
+    if fmt == "bf16x6":
+        return split_bf16x3(w), scale
+    planes, scale = split_f16x3(w, scale)
+    return {"glds": pack_glds_f16x3, "r16": pack_r16_f16x3}.get(fmt, lambda p: p)(planes), scale
+
+
+def _i3(v):
+    import ctypes
+    return (ctypes.c_int * 3)(*[int(x) for x in v])
+
+
+def sparse_table(tiled, coords, n, batch, dims, grid, k, stride=None, pad=None):
+    """Tap-major table of the n output sites `coords` of a layer with kernel k: submanifold (stride None: the sites are the
+    input level's) or strided (stride, pad); dims and grid [batch, *dims] are the input level's.  tiled: pitched, with
+    per-tile tap masks.  -> dict(nbr [K, pitch | max(n, 1)] i32, n, K, tmask | None): a rulebook entry, side data goes in too."""
+    K = int(k[0]) * int(k[1]) * int(k[2])
+    dev = coords.device
+    if tiled:
+        pitch = lib.load().al3d_sp_table_pitch(n)
+        nbr = torch.empty((K, pitch), dtype=torch.int32, device=dev)
+        tmask = torch.empty((pitch // 32,), dtype=torch.int32, device=dev)
+        out = (_ptr(nbr), pitch, _ptr(tmask))
+    else:
+        nbr, tmask = torch.empty((K, max(n, 1)), dtype=torch.int32, device=dev), None
+        out = (_ptr(nbr),)
+    if stride is None:
+        fn, geom = "al3d_sp_subm_table", (batch, *dims, _ptr(grid), *k)
+    else:
+        fn, geom = "al3d_sp_down_table", (_i3(k), _i3(stride), _i3(pad), batch, *dims, _ptr(grid))
+    lib.call(fn + ("_tiles" if tiled else ""), _ptr(coords), n, *geom, *out, _stream())
+    return dict(nbr=nbr, n=n, K=K, tmask=tmask)
+
+
+def sparse_side(name, tab, cin, cout):
+    """Adds to table `tab` (sparse_table's) the side data structure `name` reads, unless it holds it already: one build
+    per table, shared by the layers of a level."""
+    side = SPARSE[name][3]
+    if side is None or side in tab:
+        return
+    nbr, n = tab["nbr"], tab["n"]
+    if side == "trng":          # (lo, len) of every (tile, kz, ky) group
+        tab["trng"] = torch.empty((max(nbr.shape[1] // 32, 1), 9, 2), dtype=torch.int32, device=nbr.device)
+        lib.call("al3d_sp_tile_ranges", _ptr(nbr), nbr.shape[1], tab["K"], n, _ptr(tab["trng"]), _stream())
+    elif side == "plan":
+        tab["plan"] = block_plan(nbr, n, cin, cout)
+    else:
+        tab["items"] = tile_items(nbr, n, tab["tmask"])
+
+
+def sparse_down_sites(coords, n, k, stride, pad, batch, odims, grid_out, cols=False):
+    """Output sites of a strided conv over the n input sites `coords`, numbered in raster (b, z, y, x) order, or column by
+    column (al3d_sp_down_sites_blocked); grid_out [batch, *odims] (all -1) gets their rows.  One small D2H.
+    -> coords_out [n_out, 4] i32"""
+    dev = coords.device
+    cap = min(n * int(k[0]) * int(k[1]) * int(k[2]), batch * int(odims[0]) * int(odims[1]) * int(odims[2]))
+    out = torch.empty((max(cap, 1), 4), dtype=torch.int32, device=dev)
+    counter = torch.zeros(1, dtype=torch.int32, device=dev)
+    fn = "al3d_sp_down_sites_blocked" if cols else "al3d_sp_down_sites"
+    ws = torch.empty(getattr(lib.load(), fn + "_workspace_bytes")(batch, *odims), dtype=torch.uint8, device=dev)
+    lib.call(fn, _ptr(coords), n, _i3(k), _i3(stride), _i3(pad), batch, *odims, _ptr(grid_out), _ptr(out), _ptr(counter),
+             cap, _ptr(ws), _stream())
+    return out[:int(counter.item())]
+
+
+def sparse_launch(name, feats, tab, w, cin, cout, scale, shift, residual, relu, out, io=0):
+    """The one launch of every structure: out [n, Cout] = conv of feats [*, cin] over table `tab` (with its side data),
+    * scale + shift (+ residual) (ReLU).  w, scale: sparse_pack's.  io: IO_* flags (pair rows)."""
+    fn, _, tiled, side = SPARSE[name]
+    if io and not tiled:
+        raise lib.Al3dError(f"sparse conv {name!r}: pair rows exist for the tiled f16x3 kernels only")
+    nbr = tab["nbr"]
+    lead = (nbr.shape[1], *[_ptr(t) for t in _SIDE_ARGS[side](tab)]) if tiled else ()
+    tail = ((io, R16_TPW) if side == "items" else (io,)) if tiled else ()
+    lib.call(fn, _ptr(feats), _ptr(nbr), *lead, tab["K"], _ptr(w), cin, cout, _ptr(scale), _ptr(shift), _ptr(residual),
+             1 if relu else 0, _ptr(out), tab["n"], *tail, _stream())
 
 
 # ------------------------------------------------------------------ kernels
@@ -662,121 +758,38 @@ class Voxelizer:
 
 
 # ------------------------------------------------------------------ single sparse conv layer
-MFMA_PAIRS = {(16, 16), (16, 32), (32, 32), (32, 64), (64, 64), (64, 128), (128, 128)}
-
-
 def sparse_conv_layer(feats, coords, batch, in_shape, weight, ksize, stride, pad, subm,
                       scale=None, shift=None, residual=None, relu=False, mfma=None, io=0):
-    """One spconv layer on device (building block of the encoder, also used by the tests).
-    feats [n,Cin] f32, coords [n,4] i32 (b,z,y,x), weight [kz,ky,kx,Cin,Cout].
-    Returns (fout [n_out,Cout], coords_out [n_out,4], out_shape)."""
-    import ctypes
-    import numpy as np
+    """One spconv layer on device through the encoder's dispatch (used by the tests).  mfma: a SPARSE structure, by
+    default the one the encoder would run on rows in the caller's order.  feats [n,Cin] f32, coords [n,4] i32 (b,z,y,x),
+    weight [kz,ky,kx,Cin,Cout].  Returns (fout [n_out,Cout], coords_out [n_out,4] (strided: raster order), out_shape)."""
     dev = feats.device
-    st = _stream()
     k = [int(v) for v in ksize]
     n, cin = feats.shape
     cout = weight.shape[-1]
     K = k[0] * k[1] * k[2]
-    w = weight.reshape(K, cin, cout).contiguous().float()
-    D_, H_, W_ = [int(v) for v in in_shape]
-    grid_in = torch.full((batch * D_ * H_ * W_,), -1, dtype=torch.int32, device=dev)
-    lib.call("al3d_sp_scatter_index", _ptr(coords), n, batch, D_, H_, W_, _ptr(grid_in), 1, st)
-    if mfma is None:
-        mfma = (cin, cout) in MFMA_PAIRS and ({"bf16x6": "wave2", "f16x3": "glds_f16x3" if sparse_glds(cin, cout) else "wave2_f16x3"}
-                                               .get(sparse_math(), True))
-    tiled = mfma in ("glds_f16x3", "wave2_f16x3_tiles", "rng_f16x3", "r16_f16x3", "blk_f16x3")     # pitched table + per-tile tap masks
-    tmask = None
+    name, width = (mfma, cin) if mfma is not None else sparse_structure(cin, cout, K, subm, False)[:2]
+    if width != cin:
+        feats = torch.nn.functional.pad(feats, (0, width - cin))
+    w, scale = sparse_pack(name, weight.reshape(K, cin, cout).float(), scale, width)
+    tiled = SPARSE[name][2]
+    dims = [int(v) for v in in_shape]
+    grid_in = torch.full((batch * dims[0] * dims[1] * dims[2],), -1, dtype=torch.int32, device=dev)
+    lib.call("al3d_sp_scatter_index", _ptr(coords), n, batch, *dims, _ptr(grid_in), 1, _stream())
     if subm:
-        if tiled:
-            pitch = lib.load().al3d_sp_table_pitch(n)
-            nbr = torch.empty((K, pitch), dtype=torch.int32, device=dev)
-            tmask = torch.empty((pitch // 32,), dtype=torch.int32, device=dev)
-            lib.call("al3d_sp_subm_table_tiles", _ptr(coords), n, batch, D_, H_, W_, _ptr(grid_in), k[0], k[1], k[2],
-                     _ptr(nbr), pitch, _ptr(tmask), st)
-        else:
-            nbr = torch.empty((max(n, 1), K), dtype=torch.int32, device=dev)
-            lib.call("al3d_sp_subm_table", _ptr(coords), n, batch, D_, H_, W_, _ptr(grid_in), k[0], k[1], k[2],
-                     _ptr(nbr), st)
-        ocoords, n_out, oshape = coords, n, [D_, H_, W_]
+        ocoords, oshape = coords, dims
+        tab = sparse_table(tiled, coords, n, batch, dims, grid_in, k)
     else:
         s3, p3 = [int(v) for v in stride], [int(v) for v in pad]
-        oshape = [(in_shape[d] + 2 * p3[d] - (k[d] - 1) - 1) // s3[d] + 1 for d in range(3)]
+        oshape = [(dims[d] + 2 * p3[d] - k[d]) // s3[d] + 1 for d in range(3)]
         grid_out = torch.full((batch * oshape[0] * oshape[1] * oshape[2],), -1, dtype=torch.int32, device=dev)
-        cap = min(n * K, grid_out.numel())
-        ocoords = torch.empty((max(cap, 1), 4), dtype=torch.int32, device=dev)
-        counter = torch.zeros(1, dtype=torch.int32, device=dev)
-        I3 = ctypes.c_int * 3
-        lib.call("al3d_sp_down_claim", _ptr(coords), n, I3(*k), I3(*s3), I3(*p3), batch, *oshape,
-                 _ptr(grid_out), _ptr(ocoords), _ptr(counter), cap, st)
-        n_out = int(counter.item())
-        ocoords = ocoords[:n_out].contiguous()
-        if tiled:
-            pitch = lib.load().al3d_sp_table_pitch(n_out)
-            nbr = torch.empty((K, pitch), dtype=torch.int32, device=dev)
-            tmask = torch.empty((pitch // 32,), dtype=torch.int32, device=dev)
-            lib.call("al3d_sp_down_table_tiles", _ptr(ocoords), n_out, I3(*k), I3(*s3), I3(*p3), batch, D_, H_, W_,
-                     _ptr(grid_in), _ptr(nbr), pitch, _ptr(tmask), st)
-        else:
-            nbr = torch.empty((max(n_out, 1), K), dtype=torch.int32, device=dev)
-            lib.call("al3d_sp_down_table", _ptr(ocoords), n_out, I3(*k), I3(*s3), I3(*p3), batch, D_, H_, W_,
-                     _ptr(grid_in), _ptr(nbr), st)
-    out = torch.empty((n_out, cout), dtype=torch.float32, device=dev)
-    if io and mfma not in ("glds_f16x3", "wave2_f16x3_tiles", "rng_f16x3", "r16_f16x3", "blk_f16x3"):
-        raise lib.Al3dError("sparse_conv_layer: pair rows exist for the tiled f16x3 kernels only")
-    if mfma == "glds_f16x3":
-        w3, sc3 = split_f16x3(w.permute(2, 0, 1).contiguous(), scale)
-        pk = pack_glds_f16x3(w3)
-        lib.call("al3d_sp_conv_glds_f16x3_io", _ptr(feats), _ptr(nbr), nbr.shape[1], _ptr(tmask), K, _ptr(pk.data), cin,
-                 cout, _ptr(sc3), _ptr(shift), _ptr(residual), 1 if relu else 0, _ptr(out), n_out, io, st)
-    elif mfma == "rng_f16x3":
-        if not subm or K != 27:
-            raise lib.Al3dError("sparse_conv_layer: the range-gather kernel serves 27-tap submanifold layers")
-        w3, sc3 = split_f16x3(w.permute(2, 0, 1).contiguous(), scale)
-        pk = pack_glds_f16x3(w3)
-        trng = torch.empty((nbr.shape[1] // 32, 9, 2), dtype=torch.int32, device=dev)
-        lib.call("al3d_sp_tile_ranges", _ptr(nbr), nbr.shape[1], K, n_out, _ptr(trng), st)
-        lib.call("al3d_sp_conv_rng_f16x3", _ptr(feats), _ptr(nbr), nbr.shape[1], _ptr(tmask), _ptr(trng), K,
-                 _ptr(pk.data), cin, cout, _ptr(sc3), _ptr(shift), _ptr(residual), 1 if relu else 0, _ptr(out), n_out, io, st)
-    elif mfma == "blk_f16x3":
-        if not subm or K != 27:
-            raise lib.Al3dError("sparse_conv_layer: the block-staged kernel serves 27-tap submanifold layers")
-        w3, sc3 = split_f16x3(w.permute(2, 0, 1).contiguous(), scale)
-        pk = pack_glds_f16x3(w3)
-        plan = block_plan(nbr, n_out, cin, cout)
-        sparse_conv_layer.last_plan = plan
-        lib.call("al3d_sp_conv_blk_f16x3", _ptr(feats), _ptr(nbr), nbr.shape[1], _ptr(tmask), _ptr(plan.hdr), _ptr(plan.rows),
-                 _ptr(plan.loc), K, _ptr(pk.data), cin, cout, _ptr(sc3), _ptr(shift), _ptr(residual), 1 if relu else 0,
-                 _ptr(out), n_out, io, st)
-    elif mfma == "r16_f16x3":
-        if K != 27 or cin != 16:
-            raise lib.Al3dError("sparse_conv_layer: the item-stream kernel serves 27-tap layers with 16 input channels")
-        w3, sc3 = split_f16x3(w.permute(2, 0, 1).contiguous(), scale)
-        pk = pack_r16_f16x3(w3)
-        first, items = tile_items(nbr, n_out, tmask)
-        lib.call("al3d_sp_conv_r16_f16x3", _ptr(feats), _ptr(nbr), nbr.shape[1], _ptr(items), _ptr(first), K, _ptr(pk.data),
-                 cin, cout, _ptr(sc3), _ptr(shift), _ptr(residual), 1 if relu else 0, _ptr(out), n_out, io, R16_TPW, st)
-    elif mfma == "wave2_f16x3_tiles":
-        w3, sc3 = split_f16x3(w.permute(2, 0, 1).contiguous(), scale)
-        lib.call("al3d_sp_conv_wave2_f16x3_tiles_io", _ptr(feats), _ptr(nbr), nbr.shape[1], _ptr(tmask), K, _ptr(w3), cin,
-                 cout, _ptr(sc3), _ptr(shift), _ptr(residual), 1 if relu else 0, _ptr(out), n_out, io, st)
-    elif mfma == "wave2_f16x3":
-        w3, sc3 = split_f16x3(w.permute(2, 0, 1).contiguous(), scale)
-        lib.call("al3d_sp_conv_wave2_f16x3", _ptr(feats), _ptr(nbr), K, _ptr(w3), cin, cout, _ptr(sc3),
-                 _ptr(shift), _ptr(residual), 1 if relu else 0, _ptr(out), n_out, st)
-    elif mfma in ("bf16x6", "wave", "wave2"):
-        w6 = split_bf16x3(w.permute(2, 0, 1).contiguous())
-        fn = {"bf16x6": "al3d_sp_conv_bf16x6", "wave": "al3d_sp_conv_wave_bf16x6",
-              "wave2": "al3d_sp_conv_wave2_bf16x6"}[mfma]
-        lib.call(fn, _ptr(feats), _ptr(nbr), K, _ptr(w6), cin, cout, _ptr(scale),
-                 _ptr(shift), _ptr(residual), 1 if relu else 0, _ptr(out), n_out, st)
-    elif mfma:
-        w_ock = w.permute(2, 0, 1).contiguous()          # [Cout, K, Cin]
-        lib.call("al3d_sp_conv_mfma_f32", _ptr(feats), _ptr(nbr), K, _ptr(w_ock), cin, cout, _ptr(scale),
-                 _ptr(shift), _ptr(residual), 1 if relu else 0, _ptr(out), n_out, st)
-    else:
-        lib.call("al3d_sp_conv_f32", _ptr(feats), _ptr(nbr), K, _ptr(w), cin, cout, _ptr(scale),
-                 _ptr(shift), _ptr(residual), 1 if relu else 0, _ptr(out), n_out, st)
+        ocoords = sparse_down_sites(coords, n, k, s3, p3, batch, oshape, grid_out)
+        tab = sparse_table(tiled, ocoords, ocoords.shape[0], batch, dims, grid_in, k, s3, p3)
+    sparse_side(name, tab, width, cout)
+    if "plan" in tab:
+        sparse_conv_layer.last_plan = tab["plan"]
+    out = torch.empty((tab["n"], cout), dtype=torch.float32, device=dev)
+    sparse_launch(name, feats, tab, w, width, cout, scale, shift, residual, relu, out, io)
     return out, ocoords, oshape
 
 

@@ -59,8 +59,6 @@ SIGNATURES = {
     "al3d_sp_scatter_index": (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_int, c_p]),
     "al3d_sp_subm_table": (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_int, c_int, c_int,
                                    c_p, c_p]),
-    "al3d_sp_down_claim": (c_int, [c_p, c_int, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_p,
-                                   c_p, c_int, c_p]),
     "al3d_sp_down_sites_workspace_bytes": (c_i64, [c_int, c_int, c_int, c_int]),
     "al3d_sp_down_sites": (c_int, [c_p, c_int, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_p,
                                    c_p, c_int, c_p, c_p]),

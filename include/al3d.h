@@ -237,14 +237,9 @@ int al3d_sp_scatter_index(const int* coords, int n, int B, int D, int H, int W, 
                           int mode /* 1: grid=row id, 0: grid=-1 */, void* stream);
 int al3d_sp_subm_table(const int* coords, int n, int B, int D, int H, int W, const int* grid,
                        int kd, int kh, int kw, int* nbr, void* stream);
-/* strided conv: discover output sites (coords_out rows in arbitrary order, *counter = count,
- * grid_out filled with their row ids) ... ksize/stride/pad are HOST int[3] (z, y, x). */
-int al3d_sp_down_claim(const int* coords_in, int n_in, const int* ksize, const int* stride,
-                       const int* pad, int B, int OD, int OH, int OW, int* grid_out,
-                       int* coords_out, int* counter, int cap, void* stream);
-/* Deterministic variant used by the encoder: mark the fed output cells, scan the grid, number
- * the sites in raster (b,z,y,x) order.  Same outputs as al3d_sp_down_claim but with a fixed
- * row order; workspace >= al3d_sp_down_sites_workspace_bytes(). */
+/* strided conv: discover the output sites (coords_out rows, *counter = count, grid_out (all -1 on entry) filled with
+ * their row ids): mark the fed output cells, scan the grid, number the sites in raster (b,z,y,x) order.
+ * ksize/stride/pad are HOST int[3] (z, y, x); workspace >= al3d_sp_down_sites_workspace_bytes(). */
 int64_t al3d_sp_down_sites_workspace_bytes(int B, int OD, int OH, int OW);
 int al3d_sp_down_sites(const int* coords_in, int n_in, const int* ksize, const int* stride,
                        const int* pad, int B, int OD, int OH, int OW, int* grid_out,

@@ -99,7 +99,7 @@ def test_sparse_conv_glds_kernel_is_bit_identical(cin, cout, geom):
                                           residual=None if res is None else _t(res), relu=True, mfma=mode)
         outs.append((got.cpu().numpy(), gco.cpu().numpy()))
     assert outs[0][0].shape[0] > 0 and np.isfinite(outs[0][0]).all()
-    # sparse_conv_layer claims strided output sites with atomics (row order differs from run to run):
+    # strided output rows are in raster order, the oracle's in first-touch order:
     # compare site by site through the dense scatter
     _, _, oshape = D.sparse_conv_layer(_t(feats[:1]), _t(coords[:1]), batch, shape, _t(w), k, s, p, subm, mfma=False)
     a = to_dense(outs[0][0], outs[0][1], batch, oshape)
@@ -235,9 +235,9 @@ def test_sparse_conv_residual_and_empty(oracle):
 # ---------------------------------------------------------------- the encoder's OWN index path vs the oracle
 def _one_stage_encoder(mods):
     """A one-stage encoder built from the product's `_SparseEncoderBase`: its `_run` goes through
-    `build_rulebook` (al3d_sp_scatter_index / al3d_sp_subm_table / al3d_sp_down_sites /
-    al3d_sp_down_table), `_pack` (incl. the zero-padded 5 -> 16 first layer) and `_conv` -- the code the
-    shipped FPNSpMiddleResNetFHD runs, unlike `detector_ops.sparse_conv_layer` (al3d_sp_down_claim)."""
+    `_prepare` (sparse_structure + sparse_pack, incl. the zero-padded 5 -> 16 first layer), `build_rulebook`
+    (level grids, al3d_sp_down_sites, the shared level tables) and `_conv` -- the code the shipped
+    FPNSpMiddleResNetFHD runs, with its own level grids and table sharing."""
     from torch import nn
     from al3d.models.backbones import _SparseEncoderBase
 

@@ -112,7 +112,7 @@ class Case:
             got = D.rows_convert(got, False)
         got, gco = got.cpu().double().numpy(), gco.cpu().numpy()
         assert gshape == self.oshape, (mfma, gshape, self.oshape)
-        # sites: exactly the reference's, as sets (strided rows are claimed with atomics, in any order)
+        # sites: exactly the reference's, as sets (strided rows are in raster order, the reference's in its own)
         kg, kr = R.cell_key(gco, self.oshape), R.cell_key(self.ocoords, self.oshape)
         assert len(kg) == len(kr) and len(np.unique(kg)) == len(kg), mfma
         pos = np.searchsorted(np.sort(kr), kg)

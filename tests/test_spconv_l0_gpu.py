@@ -242,7 +242,7 @@ def test_item_stream_kernel_is_bit_identical(cout, geom, order):
     def run(mode):
         got, gco, osh = D.sparse_conv_layer(_t(feats), _t(coords), batch, shape, _t(w), k, s, p, subm, scale=_t(scale),
                                             shift=_t(shift), residual=None if res is None else _t(res), relu=True, mfma=mode)
-        key = _raster_key(gco.cpu().numpy(), osh)                        # strided sites are claimed with atomics: align by cell
+        key = _raster_key(gco.cpu().numpy(), osh)                        # align the rows by cell
         return got.cpu().numpy()[np.argsort(key, kind="stable")]
     ref = run("wave2_f16x3_tiles")
     assert ref.shape[0] > 0 and np.isfinite(ref).all()

@@ -29,7 +29,7 @@ for mode in modes:
     def timed(*a, **k):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(); conv(*a, **k); e1.record()
-        ev.append((a[0].in_channels, a[0].out_channels, a[3], e0, e1))
+        ev.append((a[0]["mod"].in_channels, a[0]["mod"].out_channels, a[1]["K"], e0, e1))
     bb._conv = timed
     with torch.no_grad():
         book = bb.rulebook_for(ex["coordinates"], bs, ex["shape"][0])

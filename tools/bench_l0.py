@@ -33,13 +33,14 @@ for tag, l0, couts, rows in modes:
     D.L0, D.R16_COUTS, D.L0_ROWS = l0, couts, rows
     enc._packed_dev = None
     times, names = [], []
-    def timed(m, feats, nbr, K, step, residual, out, n, st, **kw):
+    def timed(step, b, feats, residual, out, io=0):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        orig(m, feats, nbr, K, step, residual, out, n, st, **kw)
+        orig(step, b, feats, residual, out, io)
         e1.record()
         times.append((e0, e1))
-        names.append(f"{feats.shape[-1]:3d}->{m.out_channels:3d} K={K:2d} n={n:8d} {'res' if residual is not None else '   '} {type(step['w']).__name__[:10]}")
+        names.append(f"{feats.shape[-1]:3d}->{step['mod'].out_channels:3d} K={b['K']:2d} n={b['n']:8d} "
+                     f"{'res' if residual is not None else '   '} {str(step['sp'])[:10]}")
     B._SparseEncoderBase._conv = staticmethod(timed)
     book_ms = []
     with torch.no_grad():

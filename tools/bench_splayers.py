@@ -29,9 +29,9 @@ pool = PoolFrames.from_synthetic(bs, dev, num_base=8)
 ex = next(iter(DeviceSweepLoader(pool, cfg.voxel_generator, anchors, batch_size=bs, device=dev)))
 calls = []
 orig = B._SparseEncoderBase._conv
-def rec(m, feats, nbr, K, step, residual, out, n, st, tmask=None, trng=None, io=0):
-    calls.append((m, feats, nbr, K, step, residual, n, io))
-    return orig(m, feats, nbr, K, step, residual, out, n, st, tmask=tmask, trng=trng, io=io)
+def rec(step, b, feats, residual, out, io=0):
+    calls.append((step["mod"], feats, b["nbr"], b["K"], step, residual, b["n"], io))
+    return orig(step, b, feats, residual, out, io)
 B._SparseEncoderBase._conv = staticmethod(rec)
 with torch.no_grad():
     model.backbone(ex["voxel_features"], ex["coordinates"], bs, ex["shape"][0])
@@ -62,7 +62,7 @@ for (m, feats, nbr, K, step, residual, n, io) in calls:
         tiled = tiled_cache[key]
     for f in fns:
         out = torch.empty((n, co), device=dev)
-        w = D.pack_glds_f16x3(step["w"]).data if ("glds" in f or "rng" in f) else step["w"]
+        w = D.pack_glds_f16x3(step["w"]) if ("glds" in f or "rng" in f) else step["w"]
         def call():
             if "rng" in f:
                 if not m.subm:

@@ -21,9 +21,9 @@ pool = PoolFrames.from_synthetic(bs, dev, num_base=8)
 ex = next(iter(DeviceSweepLoader(pool, cfg.voxel_generator, anchors, batch_size=bs, device=dev)))
 calls = []
 orig = B._SparseEncoderBase._conv
-def rec(m, feats, nbr, K, step, residual, out, n, st, **kw):
-    calls.append((m, nbr, K, n))
-    return orig(m, feats, nbr, K, step, residual, out, n, st, **kw)
+def rec(step, b, feats, residual, out, io=0):
+    calls.append((step["mod"], b["nbr"], b["K"], b["n"]))
+    return orig(step, b, feats, residual, out, io)
 B._SparseEncoderBase._conv = staticmethod(rec)
 with torch.no_grad():
     model.backbone(ex["voxel_features"], ex["coordinates"], bs, ex["shape"][0])
