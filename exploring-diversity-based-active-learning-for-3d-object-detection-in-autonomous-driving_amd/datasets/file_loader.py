@@ -95,7 +95,8 @@ class FileSweepLoader:
     therefore not reproducible)."""
 
     def __init__(self, infos, voxel_cfg, anchors, batch_size=8, device="cuda", nsweeps=10, root=None, threads=8,
-                 indices=None, depth=2, min_distance=1.0):
+                 indices=None, depth=2, min_distance=1.0, with_points=False):
+        self.with_points = bool(with_points)   # also yield the padded point slots (``voxels``) for PillarFeatureNet
         self.infos = infos
         self.batch_size = int(batch_size)
         self.device = torch.device(device)
@@ -210,9 +211,9 @@ class FileSweepLoader:
         lib.call("al3d_merge_sweeps_batch_range_f32", base, base + st.o_off, st.nf, st.total, base + st.o_xf, base + st.o_has,
                  base + st.o_tl, base + st.o_key, base + st.o_ff, st.B, self.min_distance, int(self.rule), rg, out.data_ptr(),
                  frame_off.data_ptr(), ws.data_ptr(), stream.cuda_stream)
-        v = self.voxelizer(out, frame_off)
+        v = self.voxelizer(out, frame_off, want_voxels=self.with_points)
         gs = self.voxelizer.grid_size
-        return {
+        ex = {
             "voxel_features": v["feat"], "coordinates": v["coords"], "num_points": v["num_points"],
             "num_voxels": v["num_voxels"], "voxel_cap": v["voxel_cap"],
             "shape": np.tile(np.asarray(gs, dtype=np.int64)[None], (st.B, 1)),
@@ -220,6 +221,9 @@ class FileSweepLoader:
             "metadata": [{"token": str(self.infos[i].get("token", f"frame{i:06d}")), "index": i} for i in st.ids],
             "points": out, "point_offsets": frame_off,
         }
+        if self.with_points:
+            ex["voxels"] = v["voxels"]
+        return ex
 
     def __iter__(self):
         nb = len(self)

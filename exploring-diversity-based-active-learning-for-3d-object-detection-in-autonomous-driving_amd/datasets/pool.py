@@ -76,7 +76,8 @@ class DeviceSweepLoader:
     keys the detector reads (voxelnet.py:84-97, mg_head.py:710-724): ``voxel_features``,
     ``coordinates``, ``num_points``, ``num_voxels``, ``shape``, ``anchors``, ``metadata``."""
 
-    def __init__(self, pool, voxel_cfg, anchors, batch_size=4, indices=None, device="cuda"):
+    def __init__(self, pool, voxel_cfg, anchors, batch_size=4, indices=None, device="cuda", with_points=False):
+        self.with_points = bool(with_points)   # also yield the padded point slots (``voxels``) for PillarFeatureNet
         self.pool = pool
         self.batch_size = int(batch_size)
         self.device = torch.device(device)
@@ -104,15 +105,18 @@ class DeviceSweepLoader:
                 pts = self.pool.flat[self.pool.offsets[ids[0]]:self.pool.offsets[ids[-1] + 1]]
             else:
                 pts = torch.cat(frames, dim=0) if len(frames) > 1 else frames[0]
-            v = self.voxelizer(pts, off)
+            v = self.voxelizer(pts, off, want_voxels=self.with_points)
             B = len(ids)
-            yield {
+            ex = {
                 "voxel_features": v["feat"], "coordinates": v["coords"], "num_points": v["num_points"],
                 "num_voxels": v["num_voxels"], "voxel_cap": v["voxel_cap"],
                 "shape": np.tile(np.asarray(gs, dtype=np.int64)[None], (B, 1)),
                 "anchors": self.anchors,
                 "metadata": [{"token": self.pool.tokens[i], "index": i} for i in ids],
             }
+            if self.with_points:
+                ex["voxels"] = v["voxels"]
+            yield ex
 
 
 class CameraLidarSweepLoader(DeviceSweepLoader):

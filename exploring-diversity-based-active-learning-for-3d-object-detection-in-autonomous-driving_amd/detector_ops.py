@@ -757,6 +757,68 @@ class Voxelizer:
                     voxels=None if voxels is None else voxels[:m])
 
 
+# ------------------------------------------------------------------ PointPillars pillar net
+class PillarNet:
+    """Folded PFN layers of a ``PillarFeatureNet`` for ``al3d_pillar_net_*`` (csrc/pillars.hip).  ``layers``: one or
+    two ``(linear, bn)`` pairs in eval mode; weights are transposed to [in, units] and BN folded to scale / shift."""
+
+    def __init__(self, layers, vx, vy, x_offset, y_offset, with_distance, device):
+        if not 1 <= len(layers) <= 2:
+            raise lib.Al3dError(f"PillarNet: 1 or 2 PFN layers supported, got {len(layers)}")
+        self.packs = []
+        for lin, bn in layers:
+            units = lin.weight.shape[0]
+            if units % 16 or not 16 <= units <= 128:
+                raise lib.Al3dError(f"PillarNet: a PFN layer has {units} units; the kernel needs a multiple of 16 "
+                                    "in [16, 128]")
+            scale, shift = fold_bn(bn)
+            w = lin.weight.detach().float().t().contiguous()
+            self.packs.append((w.to(device), scale.to(device), shift.to(device), units))
+        self.geom = (float(vx), float(vy), float(x_offset), float(y_offset), int(bool(with_distance)))
+        self.channels = self.packs[-1][3]
+
+    def _args(self, voxels, num_points, coords):
+        voxels = _dev(voxels, torch.float32, "voxels").contiguous()
+        num_points = _dev(num_points.to(torch.int32), torch.int32, "num_points").contiguous()
+        coords = _dev(coords.to(torch.int32), torch.int32, "coords").contiguous()
+        M, P, F = voxels.shape
+        if num_points.numel() != M or tuple(coords.shape) != (M, 4):
+            raise lib.Al3dError(f"PillarNet: {M} pillars but num_points {tuple(num_points.shape)}, "
+                                f"coords {tuple(coords.shape)}")
+        w1, s1, b1, u1 = self.packs[0]
+        if w1.shape[0] != F + 5 + self.geom[4]:
+            raise lib.Al3dError(f"PillarNet: {F} point features need a first layer of {F + 5 + self.geom[4]} inputs, "
+                                f"got {w1.shape[0]}")
+        w2, s2, b2, u2 = self.packs[1] if len(self.packs) == 2 else (None, None, None, 0)
+        keep = (voxels, num_points, coords)        # the pointers below stay valid while the caller holds these
+        return (_ptr(voxels), _ptr(num_points), _ptr(coords), M, P, F, *self.geom,
+                _ptr(w1), _ptr(s1), _ptr(b1), u1, _ptr(w2), _ptr(s2), _ptr(b2), u2), keep
+
+    def rows(self, voxels, num_points, coords):
+        """-> [M, C] pillar features (PillarFeatureNet.forward)."""
+        args, keep = self._args(voxels, num_points, coords)
+        out = torch.empty((args[3], self.channels), dtype=torch.float32, device=keep[0].device)
+        lib.call("al3d_pillar_net_f32", *args, _ptr(out), _stream())
+        return out
+
+    def canvas(self, voxels, num_points, coords, batch, ny, nx):
+        """-> NHWC canvas [batch, ny, nx, C]: the net fused with the scatter (zero where there is no pillar)."""
+        args, keep = self._args(voxels, num_points, coords)
+        out = torch.empty((batch, ny, nx, self.channels), dtype=torch.float32, device=keep[0].device)
+        lib.call("al3d_pillar_net_scatter_f32", *args, batch, ny, nx, _ptr(out), _stream())
+        return out
+
+
+def pillar_scatter(rows, coords, batch, ny, nx):
+    """PointPillarsScatter: rows [M, C] at coords (b, z, y, x) -> NHWC canvas [batch, ny, nx, C], zero elsewhere."""
+    rows = _dev(rows, torch.float32, "rows").contiguous()
+    coords = _dev(coords.to(torch.int32), torch.int32, "coords").contiguous()
+    M, C = rows.shape
+    out = torch.empty((batch, ny, nx, C), dtype=torch.float32, device=rows.device)
+    lib.call("al3d_pillar_scatter_nhwc_f32", _ptr(rows), _ptr(coords), M, C, batch, ny, nx, _ptr(out), _stream())
+    return out
+
+
 # ------------------------------------------------------------------ single sparse conv layer
 def sparse_conv_layer(feats, coords, batch, in_shape, weight, ksize, stride, pad, subm,
                       scale=None, shift=None, residual=None, relu=False, mfma=None, io=0):

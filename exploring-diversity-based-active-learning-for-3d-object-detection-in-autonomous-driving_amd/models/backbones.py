@@ -338,3 +338,30 @@ class FPNSpMiddleResNetFHD(_SparseEncoderBase):
             book = self.build_rulebook(coors, batch_size, sparse_shape, frame_rows_max)
         final, middle = self._run(voxel_features, coors, batch_size, sparse_shape, book=book)
         return self.dense_nhwc(final, out=book.pop("dense", None)), middle
+
+
+@BACKBONES.register_module
+class PointPillarsScatter(nn.Module):
+    """Pillar rows -> BEV pseudo image (det3d/models/readers/pillar_encoder.py:155-211; BEVFusion's
+    bevfusion/mmdet3d/models/backbones/pillar_encoder.py:185-240 under ``in_channels`` / ``output_shape``).
+
+    ``forward(voxel_features [M,C], coords [M,4] (b,z,y,x), batch_size, input_shape)`` -> this build's channels-last
+    canvas ``[B, ny, nx, C]`` (H = y, W = x), zero where there is no pillar; ``input_shape`` is the voxel grid
+    (nx, ny, nz), or ``output_shape`` (nx, ny) when None.  One ``al3d_pillar_scatter_nhwc_f32`` launch.  The
+    ``PointPillars`` detector does not call it: its reader writes the canvas directly."""
+
+    def __init__(self, num_input_features=64, norm_cfg=None, name="PointPillarsScatter", in_channels=None,
+                 output_shape=None, **kwargs):
+        super().__init__()
+        self.name = name
+        self.nchannels = num_input_features if in_channels is None else in_channels
+        self.output_shape = output_shape
+
+    def forward(self, voxel_features, coords, batch_size, input_shape=None):
+        shape = input_shape if input_shape is not None else self.output_shape
+        if shape is None:
+            raise lib.Al3dError("PointPillarsScatter: no input_shape and no output_shape")
+        if voxel_features.shape[-1] != self.nchannels:
+            raise lib.Al3dError(f"PointPillarsScatter: {voxel_features.shape[-1]} channels, built for {self.nchannels}")
+        nx, ny = int(shape[0]), int(shape[1])
+        return D.pillar_scatter(voxel_features, coords, int(batch_size), ny, nx)

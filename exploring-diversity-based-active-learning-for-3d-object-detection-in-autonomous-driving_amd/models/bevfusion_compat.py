@@ -104,3 +104,36 @@ def convert_decoder_state_dict(sd, decoder_prefix="decoder.", neck_prefix="neck.
 def to_bevfusion_coords(coords_bzyx):
     """(batch, z, y, x) -> (batch, x, y, z)."""
     return coords_bzyx[:, [0, 3, 2, 1]]
+
+
+def convert_pointpillars_state_dict(sd, lidar_prefix="encoders.lidar.backbone.pts_voxel_encoder.", decoder_prefix="decoder.",
+                                    head_prefix="heads.object."):
+    """BEVFusion pointpillars.yaml state dict -> state dict of this build's ``PointPillars``
+    (examples/active/bevfusion_pointpillars_*.py).
+
+    - ``<lidar_prefix>pfn_layers.<i>.{linear,norm}.*`` -> ``reader.pfn_layers.<i>.*``: same names and layouts (the
+      PFN layers are per point, so the canvas orientation does not reach them).
+    - the 3-block ``decoder.backbone`` / ``decoder.neck`` -> ``neck.*`` through ``convert_decoder_state_dict`` (2-D kernels
+      transposed with ``_t2``: their canvas is [C, nx, ny], H = x; this build's is H = y).
+    - ``<head_prefix>*`` -> ``bbox_head.*`` unchanged: the head is built with ``transpose_input=True`` and transposes the
+      map it is handed, so its kernels keep the reference's orientation.  Absent head entries are skipped (the
+      embedding-only graph has no head).
+    ``PointPillarsScatter`` has no parameters.  Raises KeyError if a PFN or decoder parameter is missing."""
+    out = {}
+    i = 0
+    while f"{lidar_prefix}pfn_layers.{i}.linear.weight" in sd:
+        out[f"reader.pfn_layers.{i}.linear.weight"] = sd[f"{lidar_prefix}pfn_layers.{i}.linear.weight"]
+        for k in _BN:
+            src = f"{lidar_prefix}pfn_layers.{i}.norm.{k}"
+            if src in sd:
+                out[f"reader.pfn_layers.{i}.norm.{k}"] = sd[src]
+            elif k != "num_batches_tracked":
+                raise KeyError(src)
+        i += 1
+    if i == 0:
+        raise KeyError(f"{lidar_prefix}pfn_layers.0.linear.weight")
+    out.update(convert_decoder_state_dict(sd, decoder_prefix, "neck."))
+    for k, v in sd.items():
+        if k.startswith(head_prefix):
+            out["bbox_head." + k[len(head_prefix):]] = v
+    return out

@@ -122,6 +122,9 @@ class FPNVoxelNet(SingleStageDetector):
             x = self.neck(x, out_pair=True) if want else self.neck(x)
             pair = bool(want and getattr(self.neck, "last_out_pair", False))
             middle.append(NHWCFeature(x, getattr(self.neck, "embedding", None), pair=pair))
+        return self._head_stage(example, x, middle, pair, finetune=finetune, **kwargs)
+
+    def _head_stage(self, example, x, middle, pair, finetune=False, **kwargs):
         if self.bbox_head is None:
             if not kwargs.get("estimate", False):
                 raise RuntimeError("this detector was built without a bbox_head: only the estimate=True "
@@ -149,3 +152,55 @@ class VoxelNet(FPNVoxelNet):
     def forward(self, example, return_loss=True, **kwargs):
         kwargs.pop("estimate", None)
         return super().forward(example, return_loss=return_loss, **kwargs)
+
+
+@DETECTORS.register_module
+class PointPillars(FPNVoxelNet):
+    """PointPillars (det3d/models/detectors/point_pillars.py; BEVFusion's PointPillarsEncoder,
+    bevfusion/mmdet3d/models/backbones/pillar_encoder.py:243-258): ``PillarFeatureNet`` reader, ``PointPillarsScatter``
+    backbone, dense neck, optional head.  Same call contract as ``FPNVoxelNet``; the example must carry the padded
+    point slots (``voxels``, ``num_points``: the loaders' ``with_points=True``).
+
+    ``sparse_stage`` runs the reader and the scatter as ONE launch (``al3d_pillar_net_scatter_f32``): the pillar rows
+    go straight into the zeroed NHWC canvas.  There is no rulebook (``prepare`` returns None).  The dense kernels take
+    maps below 2^31 elements; a larger canvas (512 x 512 x 64 at batch >= 128) runs the neck in frame chunks, which
+    gives the same bits as running the chunks as batches of their own."""
+
+    DENSE_LIMIT = 1 << 31
+
+    def prepare(self, example):
+        return None
+
+    def extract_feat(self, data):
+        """det3d's point_pillars.py:23-39 keys (features, num_voxels, coors, batch_size, input_shape) -> (canvas, [])."""
+        nx, ny = int(data["input_shape"][0]), int(data["input_shape"][1])
+        net = self.reader.net(data["features"].device)
+        x = net.canvas(data["features"].float(), data["num_voxels"], data["coors"], int(data["batch_size"]), ny, nx)
+        middle = []
+        if self.with_neck:
+            x = self.neck(x)
+            middle.append(NHWCFeature(x, getattr(self.neck, "embedding", None)))
+        return x, middle
+
+    def sparse_stage(self, example, book=None):
+        voxels = example.get("voxels")
+        if voxels is None:
+            raise RuntimeError("PointPillars needs the padded point slots: build the loader with with_points=True")
+        nx, ny = int(example["shape"][0][0]), int(example["shape"][0][1])
+        net = self.reader.net(voxels.device)
+        x = net.canvas(voxels, example["num_points"], example["coordinates"], len(example["num_voxels"]), ny, nx)
+        return x, []
+
+    def dense_stage(self, example, x, middle, finetune=False, **kwargs):
+        B, H, W, C = x.shape
+        if not self.with_neck or B * H * W * C < self.DENSE_LIMIT:
+            return super().dense_stage(example, x, middle, finetune=finetune, **kwargs)
+        n = max(1, (self.DENSE_LIMIT - 1) // (H * W * C))
+        outs, embs = [], []
+        for s in range(0, B, n):
+            outs.append(self.neck(x[s:s + n]))
+            embs.append(getattr(self.neck, "embedding", None))
+        y = torch.cat(outs)
+        emb = torch.cat(embs) if all(e is not None for e in embs) else None
+        middle.append(NHWCFeature(y, emb))
+        return self._head_stage(example, y, middle, False, finetune=finetune, **kwargs)

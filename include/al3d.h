@@ -551,6 +551,31 @@ int al3d_gap_nhwc_f32(const float* x, int B, int H, int W, int C, float* out, vo
  * per row, float4 loads when x is 16-byte aligned and ld % 4 == 0.  rows >= 0, 1 <= cols <= ld. */
 int al3d_rows_nonfinite_u8(const float* x, int rows, int cols, int ld, uint8_t* flags, void* stream);
 
+/* ---------------------------------------------------------------- detector: PointPillars pillar net (f32)
+ * PillarFeatureNet.forward + PFNLayer.forward (det3d/models/readers/pillar_encoder.py:17-152;
+ * bevfusion/mmdet3d/models/backbones/pillar_encoder.py:47-182) on the voxelizer's padded slots: voxels [M,P,F] f32 (slots
+ * at or past num_points zero), num_points [M] i32 (clipped to P), coords [M,4] i32 (b,z,y,x).  Decoration per slot:
+ * [f_0..f_{F-1}, xyz - mean over the clipped count, x - (x_index*vx + x_offset), y - (y_index*vy + y_offset), |xyz| if
+ * with_distance], zero past num_points.  Layer l: relu(linear * s_l + b_l) (eval BN folded), max over ALL P slots
+ * (the padded ones hold relu(b_1)); a second layer reads [h, max].  w1 [F+5+wd, U1] and w2 [2*U1, U2] are the linear
+ * weights transposed; w2 = NULL for one layer.  U1, U2 multiples of 16 in [16, 128]; 1 <= P <= 64; 3 <= F <= 10.
+ * al3d_pillar_net_f32 writes rows out [M, C] (C = U2, or U1 with one layer).  Plain f32 FMAs, no atomics. */
+int al3d_pillar_net_f32(const float* voxels, const int* num_points, const int* coords, int M, int P, int F, float vx,
+                        float vy, float x_offset, float y_offset, int with_distance, const float* w1, const float* s1,
+                        const float* b1, int U1, const float* w2, const float* s2, const float* b2, int U2, float* out,
+                        void* stream);
+/* Same net fused with PointPillarsScatter.forward (det3d/models/readers/pillar_encoder.py:155-211;
+ * bevfusion/.../pillar_encoder.py:185-240): canvas [B,ny,nx,C] f32 NHWC is zeroed (memset) and each pillar's row is
+ * stored at cell (b, y, x); pillars outside the canvas are dropped.  Bit-identical to al3d_pillar_net_f32 followed by
+ * al3d_pillar_scatter_nhwc_f32. */
+int al3d_pillar_net_scatter_f32(const float* voxels, const int* num_points, const int* coords, int M, int P, int F,
+                                float vx, float vy, float x_offset, float y_offset, int with_distance, const float* w1,
+                                const float* s1, const float* b1, int U1, const float* w2, const float* s2,
+                                const float* b2, int U2, int B, int ny, int nx, float* canvas, void* stream);
+/* PointPillarsScatter.forward alone (same lines): rows [M,C] -> zeroed canvas [B,ny,nx,C] at (b, y, x) of coords. */
+int al3d_pillar_scatter_nhwc_f32(const float* rows, const int* coords, int M, int C, int B, int ny, int nx,
+                                 float* canvas, void* stream);
+
 /* ---------------------------------------------------------------- camera branch: BEV pooling (f4)
  * bevfusion/mmdet3d/models/vtransforms/base.py:127-163 (`bev_pool`: cell = ((geom - (bx - dx/2)) / dx).long(),
  * points outside the grid dropped) + ops/bev_pool/bev_pool.py:82-97 + src/bev_pool_cuda.cu:21-44 (sum of the points

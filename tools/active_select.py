@@ -123,6 +123,8 @@ def main():
         head_cfg = cfg.model.get("bbox_head")
         anchors = generate_task_anchors(cfg.tasks, cfg.target_assigner.anchor_generators, [1, 128, 128]) \
             if head_cfg is not None and head_cfg.get("type") == "MultiGroupHead" else None      # TransFusionHead is anchor-free
+        # PillarFeatureNet reads the padded point slots of each pillar, not the voxelizer's mean
+        with_points = cfg.model.get("reader", {}).get("type") == "PillarFeatureNet"
         if args.synthetic_scenes and cfg.model.get("type") == "BEVFusion":
             # camera+lidar: the lidar batch plus synthetic six-camera images and one calibration rig (configs[4])
             from al3d.datasets import CameraLidarSweepLoader
@@ -145,14 +147,15 @@ def main():
                                            resize_lim=tuple(cam.get("resize_test", (0.48, 0.48))))
         elif args.synthetic_scenes:
             pool = PoolFrames.from_synthetic(len(mine), dev, seed=1000 + rank)
-            loader = DeviceSweepLoader(pool, cfg.voxel_generator, anchors, batch_size=args.batch, device=dev)
+            loader = DeviceSweepLoader(pool, cfg.voxel_generator, anchors, batch_size=args.batch, device=dev,
+                                       with_points=with_points)
         else:
             # real files: streamed by the native reader pool one batch ahead of the detector (the reference's
             # 8 DataLoader workers, build_loader.py:23-59), never staged as a whole pool
             from al3d.datasets import FileSweepLoader
             loader = FileSweepLoader([infos[i] for i in mine], cfg.voxel_generator, anchors, batch_size=args.batch,
                                      device=dev, nsweeps=cfg.nsweeps, root=cfg.data_root,
-                                     threads=int(os.environ.get("AL3D_READER_THREADS", "8")))
+                                     threads=int(os.environ.get("AL3D_READER_THREADS", "8")), with_points=with_points)
         loader.sampler = mine
 
     sel_cfg.update({"detector": model, "dataloader": loader, "logger": logger, "pred": args.pred})
