@@ -861,3 +861,76 @@ def box_decode(enc, anchors):
     out = torch.empty((enc.shape[0], 9), dtype=torch.float32, device=enc.device)
     lib.call("al3d_box_decode_f32", _ptr(enc), _ptr(anchors), enc.shape[0], _ptr(out), _stream())
     return out
+
+
+# ------------------------------------------------------------------ CenterPoint head (csrc/center_head.hip)
+def conv3x3_grouped_nhwc(x, w, bias, cout, coff, out=None, ldc=None):
+    """The last convolutions of separate heads in one launch: x [B,H,W,G*64]; group g convolves its own 64 channels
+    with w rows [sum(cout[:g]) : sum(cout[:g+1])] of w [sum cout, 9, 64] (3x3, padding 1, tap = ky*3+kx) plus bias and
+    writes cout[g] <= 8 channels at coff[g] of out [B,H,W,ldc]."""
+    import ctypes
+    x = _dev(x, torch.float32, "x")
+    w = _dev(w, torch.float32, "w")
+    bias = _dev(bias, torch.float32, "bias")
+    B, H, W, C = x.shape
+    G = len(cout)
+    if C != G * 64 or tuple(w.shape) != (sum(cout), 9, 64) or bias.numel() != sum(cout) or len(coff) != G:
+        raise lib.Al3dError("conv3x3_grouped_nhwc: x must hold 64 channels per group, w [sum cout, 9, 64], bias [sum cout]")
+    if out is None:
+        ldc = max(o + c for o, c in zip(coff, cout)) if ldc is None else ldc
+        out = torch.empty((B, H, W, ldc), dtype=torch.float32, device=x.device)
+    assert out.shape[:3] == (B, H, W) and out.is_contiguous() and out.dtype == torch.float32
+    IntG = ctypes.c_int * G
+    lib.call("al3d_conv3x3_grouped_nhwc_f32", _ptr(x), _ptr(w), _ptr(bias), _ptr(out), B, H, W, G,
+             IntG(*[int(c) for c in cout]), IntG(*[int(c) for c in coff]), out.shape[3], _stream())
+    return out
+
+
+CENTER_CHANNELS = ("heatmap", "reg", "height", "dim", "rot", "vel")      # order of a task's row in ``chan_off``
+
+
+def center_decode_nms(hout, task_ncls, chan_off, *, swapped, max_num, norm_bbox, out_size_factor, voxel_size, pc_range,
+                      coder_score_threshold, post_center_range, nms_type, nms_scale, min_radius, score_threshold, nms_thr,
+                      pre_max_size, post_max_size, post_center_limit_range, merge=True):
+    """CenterPoint post-processing of a head output ``hout`` [B,D0,D1,CH] (channels-last, raw) in one device call
+    (``al3d_center_decode_nms_f32``; semantics in include/al3d.h).  ``chan_off[t]``: channels of CENTER_CHANNELS for
+    task t (reg / vel: -1 when the head has none).  ``nms_type``: "rotate" / "circle" or one per task; ``nms_scale``:
+    per task, per class.  A falsy ``coder_score_threshold`` / non-positive ``score_threshold`` filters nothing, as in
+    the reference.  -> boxes [B,nt,post,9], scores [B,nt,post], labels i32 [B,nt,post], counts i32 [B,nt] on the
+    device; nothing is read back."""
+    import ctypes
+    hout = _dev(hout, torch.float32, "hout")
+    B, D0, D1, CH = hout.shape
+    nt = len(task_ncls)
+    kinds = [nms_type] * nt if isinstance(nms_type, str) else list(nms_type)
+    if len(kinds) != nt or any(k not in ("rotate", "circle") for k in kinds):
+        raise NotImplementedError(f"nms_type {nms_type!r}: one of 'rotate' / 'circle', or one per task")
+    if int(max_num) > D0 * D1:
+        raise lib.Al3dError(f"center_decode_nms: max_num {max_num} exceeds the {D0} x {D1} cells of the map (torch.topk raises too)")
+    post = int(post_max_size)
+    dev = hout.device
+    boxes = torch.empty((B, nt, post, 9), dtype=torch.float32, device=dev)
+    scores = torch.empty((B, nt, post), dtype=torch.float32, device=dev)
+    labels = torch.empty((B, nt, post), dtype=torch.int32, device=dev)
+    counts = torch.zeros((B, nt), dtype=torch.int32, device=dev)
+    ws = torch.empty(max(int(lib.load().al3d_center_decode_nms_workspace_bytes(B, D0, D1, sum(task_ncls))), 1),
+                     dtype=torch.uint8, device=dev)
+    IntT, F6 = ctypes.c_int * nt, ctypes.c_float * 6
+    scale = [1.0] * (4 * nt)
+    for t in range(nt):
+        for c in range(task_ncls[t]):
+            scale[4 * t + c] = float(nms_scale[t][c])
+    radius = [float(min_radius[t]) if kinds[t] == "circle" else 0.0 for t in range(nt)]
+    limit = None if post_center_limit_range is None or len(post_center_limit_range) == 0 \
+        else F6(*[float(v) for v in post_center_limit_range])
+    lib.call("al3d_center_decode_nms_f32", _ptr(hout), B, D0, D1, CH, 1 if swapped else 0, nt,
+             IntT(*[int(n) for n in task_ncls]), (ctypes.c_int * (6 * nt))(*[int(v) for row in chan_off for v in row]),
+             int(max_num), 1 if norm_bbox else 0,
+             (ctypes.c_float * 5)(float(out_size_factor), float(voxel_size[0]), float(voxel_size[1]), float(pc_range[0]),
+                                  float(pc_range[1])),
+             float(coder_score_threshold) if coder_score_threshold else -1.0, F6(*[float(v) for v in post_center_range]),
+             IntT(*[0 if k == "rotate" else 1 for k in kinds]), (ctypes.c_float * (4 * nt))(*scale),
+             (ctypes.c_float * nt)(*radius), float(score_threshold) if score_threshold and score_threshold > 0.0 else -1.0,
+             float(nms_thr), int(pre_max_size), post, limit, 1 if merge else 0, _ptr(boxes), _ptr(scores), _ptr(labels),
+             _ptr(counts), _ptr(ws), _stream())
+    return boxes, scores, labels, counts

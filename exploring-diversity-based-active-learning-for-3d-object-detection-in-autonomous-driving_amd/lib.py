@@ -192,6 +192,11 @@ SIGNATURES = {
                                             c_p, c_p, c_p, c_int, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_p,
                                             c_p]),
     "al3d_pillar_scatter_nhwc_f32": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p]),
+    "al3d_center_decode_nms_workspace_bytes": (c_i64, [c_int, c_int, c_int, c_int]),
+    "al3d_center_decode_nms_f32": (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_int, c_int, c_p, c_flt,
+                                           c_p, c_p, c_p, c_p, c_flt, c_flt, c_int, c_int, c_p, c_int, c_p, c_p, c_p, c_p,
+                                           c_p, c_p]),
+    "al3d_conv3x3_grouped_nhwc_f32": (c_int, [c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_p, c_int, c_p]),
     "al3d_pack_f16x3_wino": (c_int, [c_p, c_int, c_int, c_p, c_p]),
     "al3d_conv3x3_nhwc_f16x3_wino": (c_int, [c_p, c_p, c_p, c_p, c_p] + [c_int] * 9 + [c_p]),
     "al3d_tok_patch_rows_f32": (c_int, [c_p, c_int, c_int, c_int, c_int, c_p, c_p]),

@@ -9,6 +9,7 @@ from .detectors import FPNVoxelNet, PointPillars, VoxelNet
 from .box_coder import GroundBox3dCoderTorch, build_box_coder
 from .bevfusion_camera import ConvFuser, DepthLSSTransform, GeneralizedLSSFPN, LSSViewTransform
 from .transfusion_head import TransFusionHead
+from .center_head import CenterHead, SeparateHead
 from .swin import SwinTransformer
 from .bevfusion_model import BEVFusion, BEVFusionCameraLidar
 

@@ -101,7 +101,7 @@ class BEVFusionCameraLidar(nn.Module):
             preds = self.head(dec)
             if timed:
                 self.head.get_bboxes(preds)            # the decode is part of the stage's time
-            mark("TransFusionHead")
+            mark(type(self.head).__name__)
         if timed:
             torch.cuda.synchronize()
             self.stage_ms = {b[0]: a[1].elapsed_time(b[1]) for a, b in zip(marks[:-1], marks[1:])}

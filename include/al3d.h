@@ -830,6 +830,33 @@ int64_t al3d_tok_mha16_workspace_bytes(int B, int heads, int Pq, int Pk);
 int al3d_tok_mha16_f32(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, int B, int heads, int Pq,
                        int Pk, float scale, float* out, int ldo, void* workspace, void* stream);
 
+/* CenterPoint head post-processing (bevfusion/mmdet3d/models/heads/bbox/centerpoint.py:637-884 with
+ * core/bbox/coders/centerpoint_bbox_coders.py:62-225, ops/iou3d/src/iou3d_kernel.cu:244-331 and
+ * core/post_processing/box3d_nms.py:180-219) as a whole-GPU score pre-pass plus one workgroup per (sample, task); no
+ * host synchronisation.  hout [B][D0][D1][CH] is the head's raw channels-last output; swapped = 0: the map is [x, y]
+ * as in the reference, 1: [y, x] (this build's [H, W]).  chan_off [ntasks][6]: channel of heatmap, reg, height, dim,
+ * rot, vel of each task (reg / vel: -1 = absent -> +0.5 / 7-value boxes, written with two zeros).  geom5 =
+ * out_size_factor, voxel_size x, y, pc_range x, y.  Per class the max_num best cells, then the max_num best of those
+ * (equal scores: the smaller class * D0 * D1 + cell); decode; keep score > coder_score_thr (strict) inside the closed
+ * coder_range6; then per task nms_kind 0: keep score >= test_score_thr, the first pre_max, greedy rotated NMS on the
+ * BEV boxes scaled by nms_scale [ntasks][4] (suppress on IoU > nms_thr, strict), first post_max, limit_range6 (may be
+ * null); 1: circle NMS (suppress on squared distance <= min_radius[task]), first post_max.  merge != 0: z -= dim2 / 2
+ * and labels offset by the classes of the earlier tasks.  Outputs boxes [B][ntasks][post_max][9], scores, labels
+ * [B][ntasks][post_max], counts [B][ntasks].  max_num <= 1024 and <= D0 * D1, classes per task <= 4, post_max <= 512. */
+int64_t al3d_center_decode_nms_workspace_bytes(int B, int D0, int D1, int sum_classes);
+int al3d_center_decode_nms_f32(const float* hout, int B, int D0, int D1, int CH, int swapped, int ntasks,
+                               const int* task_ncls, const int* chan_off, int max_num, int norm_bbox,
+                               const float* geom5, float coder_score_thr, const float* coder_range6,
+                               const int* nms_kind, const float* nms_scale, const float* min_radius,
+                               float test_score_thr, float nms_thr, int pre_max, int post_max,
+                               const float* limit_range6, int merge, float* boxes, float* scores, int* labels,
+                               int* counts, void* workspace, void* stream);
+/* The last convolutions of CenterPoint's separate heads (centerpoint.py:76-86) in one launch: G groups, each 3x3 /
+ * stride 1 / padding 1 with bias, 64 -> cout[g] <= 8 channels.  x [B][H][W][G*64], w [sum cout][9][64] (tap = ky*3+kx)
+ * and bias [sum cout] in group order, out [B][H][W][ldc] written at channel coff[g].  f32 FMAs, weights in LDS. */
+int al3d_conv3x3_grouped_nhwc_f32(const float* x, const float* w, const float* bias, float* out, int B, int H, int W,
+                                  int G, const int* cout, const int* coff, int ldc, void* stream);
+
 /* ---------------------------------------------------------------- runtime
  * A HIP stream restricted to n_cus compute units starting at first_cu (hipExtStreamCreateWithCUMask); the
  * reference has no analogue (its loader workers are host processes, det3d/datasets/loader/build_loader.py:23-59):
