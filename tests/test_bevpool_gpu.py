@@ -182,3 +182,22 @@ def test_full_size_camera_lidar_fusion_pass():
     assert 0.2 < float(kept.float().mean()) <= 1.0
     print(f"camera+lidar fusion pass at configs[4] shapes: {dt * 1e3:.1f} ms per sample "
           f"({int(kept.sum())} of {kept.numel()} frustum points inside the grid)")
+
+
+@pytest.mark.parametrize("C", [6, 260])
+def test_bev_pool_fused_lss_generic_kernel_bit_exact(oracle, C):
+    """The fused Lift-Splat pooling at channel counts the float4 kernel does not take (C % 4 != 0; C / 4 > 64):
+    bev_sum_kernel<1>, against the oracle and against pooling the materialised depth x context rows."""
+    from al3d.models.bevfusion_camera import bev_pool
+    rng = np.random.default_rng(60 + C)
+    B, N, D, fH, fW = 2, 3, 7, 6, 10
+    depth = rng.uniform(0, 1, (B * N, D, fH, fW)).astype(np.float32)
+    ctx = rng.normal(size=(B * N, fH, fW, C)).astype(np.float32)
+    geom = rng.uniform(-6, 6, (B * N * D * fH * fW, 3)).astype(np.float32)
+    nx, dx, bx = np.array([30, 30, 1]), np.array([0.4, 0.4, 20.0], np.float32), np.array([-5.8, -5.8, 0.0], np.float32)
+    lo = bx - dx / np.float32(2)
+    ref = oracle.bev_pool(ctx.reshape(-1, C), geom, B, lo, dx, nx, depth=depth.reshape(-1), D=D, fHW=fH * fW)
+    got = bev_pool(_t(ctx), _t(geom), B, dx, bx, nx, depth=_t(depth)).cpu().numpy()
+    assert np.abs(ref).sum() > 0 and np.array_equal(got.view(np.int32), ref.view(np.int32))
+    mat = bev_pool(_t((depth[..., None] * ctx[:, None]).reshape(-1, C)), _t(geom), B, dx, bx, nx).cpu().numpy()
+    assert np.array_equal(got.view(np.int32), mat.view(np.int32))

@@ -428,3 +428,125 @@ def test_conv3x3_winograd_f16x3_is_fp32_class(B, H, W, Cin, Cout, xmag):
     want = torch.relu(ref.to(DEV) * bs.double() + bt.double())
     assert float((wide[..., 8:8 + Cout].double() - want).abs().max()) <= 2e-6 * float(scale.max()) * float(bs.max()) + 1e-6
     assert bool((wide[..., :8] == 7.0).all()) and bool((wide[..., 8 + Cout:] == 7.0).all())
+
+
+# ---------------------------------------------------------------- channel windows the 16-byte epilogues cannot serve
+def _window_layer(kind, Cout):
+    """(x NCHW, w torch layout, k, s, p) of a small layer for `kind`: frag (3x3/s1/p1), dma (3x3/s2/p1), deconv (2x2)."""
+    g = torch.Generator().manual_seed(len(kind) * 100 + Cout)
+    if kind == "frag":
+        return torch.randn(2, 32, 9, 37, generator=g), torch.randn(Cout, 32, 3, 3, generator=g) / 17.0, 3, 1, 1
+    if kind == "dma":
+        return torch.randn(2, 64, 13, 19, generator=g), torch.randn(Cout, 64, 3, 3, generator=g) / 24.0, 3, 2, 1
+    return torch.randn(2, 64, 7, 9, generator=g), torch.randn(64, Cout, 2, 2, generator=g) / 8.0, 2, 2, 0
+
+
+WINDOWS = {"ldc_odd": (33, 32, 0), "coff_mod4_1": (36, 33, 0), "base_plus_4_bytes": (32, 32, 1)}   # (ldc - Cout, coff, first float)
+
+
+@pytest.mark.parametrize("kind,Cout,window", [(k, c, w) for k, c in (("frag", 128), ("dma", 40), ("deconv", 40)) for w in WINDOWS] +
+                         [("dma", 38, "cout_mod4_2"), ("deconv", 38, "cout_mod4_2")])
+def test_f16x3_window_without_16_byte_alignment(kind, Cout, window):
+    """The streamed 3x3 kernel and the LDS-DMA conv / deconv fall back to untransposed dword stores when ldc, coff or Cout
+    is not a multiple of 4 or `out` is not 16-byte aligned (frag_kernel<1, 2>, dma2_kernel<M, 3, 4>).  Each such window:
+    the float64 convolution at the gate of test_conv2d_f16x3_is_fp32_class (1.5e-6 of the abs chain, 3x the f32 kernel),
+    the bits of the LDS-staged kernel into an aligned window (same products, same order), and the fill value everywhere
+    outside the window -- the floats before and after the map included."""
+    import dense_fp64 as R2
+    from al3d import detector_ops as D
+    x, w, k, s, p = _window_layer(kind, Cout)
+    dec = kind == "deconv"
+    g = torch.Generator().manual_seed(Cout)
+    scale, shift = torch.rand(Cout, generator=g) + 0.5, torch.randn(Cout, generator=g) * 0.1
+    ref, norm = R2.deconv_fp64(x, w, scale, shift, True) if dec else R2.conv_fp64(x, w, s, p, scale, shift, True)
+    B, OH, OW = ref.shape[:3]
+    xd, sd, td = _nhwc(x).to(DEV), scale.to(DEV), shift.to(DEV)
+    wp = (D.pack_deconv_weight(w) if dec else D.pack_conv_weight(w)).to(DEV)
+
+    def layer(wgt, sc, out=None, coff=0):
+        if dec:
+            return D.deconv2x2_nhwc(xd, wgt, sc, td, True, out=out, coff=coff)
+        return D.conv2d_nhwc(xd, wgt, sc, td, k, s, p, True, out=out, coff=coff)
+    e32 = R2.err(layer(wp, sd), ref, norm)
+    w3, sc3 = D.split_f16x3(wp, sd)
+    wk = D.pack_frag_f16x3(w3) if kind == "frag" else D.pack_dma_f16x3(w3)
+    staged = torch.full((B, OH, OW, Cout + 32), -3.0, device=DEV)
+    layer(w3, sc3, out=staged, coff=32)                                    # the LDS-staged kernel, aligned window
+    extra, coff, first = WINDOWS.get(window, (34, 32, 0))                  # cout_mod4_2: ldc, coff multiples of 4
+    ldc, n = Cout + extra, B * OH * OW * (Cout + extra)
+    buf = torch.full((n + 8,), -3.0, device=DEV)
+    out = buf[first:first + n].view(B, OH, OW, ldc)
+    assert (out.data_ptr() % 16 != 0) == (first != 0) and buf.data_ptr() % 16 == 0
+    layer(wk, sc3, out=out, coff=coff)
+    e = R2.err(out[..., coff:coff + Cout], ref, norm)
+    print(kind, Cout, window, "e", e, "e_f32", e32)
+    R2.check_split_gate(e, e32, f"{kind} {window}")
+    assert torch.equal(out[..., coff:coff + Cout], staged[..., 32:])
+    assert torch.all(out[..., :coff] == -3.0) and torch.all(out[..., coff + Cout:] == -3.0)
+    assert torch.all(buf[:first] == -3.0) and torch.all(buf[first + n:] == -3.0)
+    if kind != "frag":                                                     # the fused-GAP partials of the fallback epilogue
+        parts = D.gap_parts(OH, OW, dec)
+        ga = torch.full((B, parts, Cout + 32), -7.0, device=DEV)
+        gb = torch.full((B, parts, ldc), -7.0, device=DEV)
+        kw = dict(relu=True) if dec else dict(ksize=k, stride=s, pad=p, relu=True)
+        fn = D.deconv2x2_nhwc if dec else D.conv2d_nhwc
+        fn(xd, w3, sc3, td, out=staged, coff=32, gap=ga, **kw)
+        fn(xd, wk, sc3, td, out=out, coff=coff, gap=gb, **kw)
+        assert torch.equal(ga[..., 32:], gb[..., coff:coff + Cout])
+        assert torch.all(gb[..., :coff] == -7.0) and torch.all(gb[..., coff + Cout:] == -7.0)
+
+
+@pytest.mark.parametrize("kind", ["frag", "dma", "deconv"])
+def test_f16x3_alignment_requirements_are_errors(kind):
+    """What the entry points require is refused, not worked around: `in` 16-byte aligned; pair output with coff and ldc
+    multiples of 8."""
+    from al3d import detector_ops as D
+    from al3d.lib import Al3dError
+    Cout = 128
+    x, w, k, s, p = _window_layer(kind, Cout)
+    dec = kind == "deconv"
+    xd = _nhwc(x).to(DEV)
+    wp = (D.pack_deconv_weight(w) if dec else D.pack_conv_weight(w)).to(DEV)
+    w3, sc3 = D.split_f16x3(wp)
+    wk = D.pack_frag_f16x3(w3) if kind == "frag" else D.pack_dma_f16x3(w3)
+
+    def layer(xin, **kw):
+        return D.deconv2x2_nhwc(xin, wk, sc3, None, True, **kw) if dec else D.conv2d_nhwc(xin, wk, sc3, None, k, s, p, True, **kw)
+    good = layer(xd)
+    xbuf = torch.zeros(xd.numel() + 4, device=DEV)
+    xoff = xbuf[1:1 + xd.numel()].view_as(xd).copy_(xd)
+    assert xoff.data_ptr() % 16 == 4
+    with pytest.raises(Al3dError, match="16-byte aligned"):
+        layer(xoff)
+    B, OH, OW = good.shape[:3]
+    for ldc, coff in ((Cout + 12, 4), (Cout + 12, 8)):                     # coff % 8 != 0; ldc % 8 != 0
+        out = torch.full((B, OH, OW, ldc), -3.0, device=DEV)
+        with pytest.raises(Al3dError, match="multiples of 8"):
+            layer(xd, out=out, coff=coff, io=D.IO_OUT_PAIR)
+        assert torch.all(out == -3.0)
+    assert torch.equal(layer(xd), good)                                    # the refusals left the library usable
+
+
+@pytest.mark.parametrize("B,C,H,W", [(2, 101, 24, 40), (1, 1030, 5, 7)])
+def test_gap_generic_kernel_matches_two_stage_mean(B, C, H, W):
+    """Channel counts the float4 row kernel does not take (C % 4 != 0; C / 4 > 256): gap_rows_kernel, against the
+    two-stage mean in float64 (rows left to right, then top to bottom: fp32 summation error of W + H addends)."""
+    from al3d import detector_ops as D
+    g = torch.Generator().manual_seed(C)
+    x = torch.rand(B, C, H, W, generator=g) - 0.25
+    ref = x.double().mean(-1).mean(-1)
+    nrm = x.double().abs().mean(-1).mean(-1)
+    got = D.gap_nhwc(_nhwc(x).to(DEV)).cpu().double()
+    assert float(((got - ref).abs() / nrm).max()) <= (W + H) * 2.0 ** -24
+
+
+def test_merge_bf16x3_inverts_the_split():
+    """al3d_merge_bf16x3 (merge_planes_kernel): (x1 + x2) + x3 of split_bf16x3's planes is the f32 value, exactly."""
+    from al3d import detector_ops as D
+    from al3d import lib
+    g = torch.Generator().manual_seed(2)
+    w = (torch.randn(4099, generator=g) * torch.exp(torch.randn(4099, generator=g) * 3)).to(DEV)
+    s3 = D.split_bf16x3(w)
+    out = torch.full((4099 + 3,), -3.0, device=DEV)
+    lib.call("al3d_merge_bf16x3", s3.data_ptr(), 4099, out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    assert torch.equal(out[:4099], w) and torch.all(out[4099:] == -3.0)

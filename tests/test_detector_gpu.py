@@ -983,3 +983,39 @@ def test_head_nms_super_rounds_equal_the_sequential_rule(oracle, seed, score_bia
         np.testing.assert_allclose(got["box3d_lidar"].cpu().numpy()[:, :8], bb[:, :8], rtol=1e-4, atol=1e-4)
         total += len(ss)
     assert total > 0
+
+
+def test_head_decode_with_interleaved_channel_layout():
+    """The decode's score pre-pass has two forms: class logits of a location within one 128-channel window of its record
+    (head_score_rows_kernel: the product's layout, boxes of all tasks then logits of all tasks) or anywhere
+    (head_score_kernel).  The same head output with every task's logits behind its own box channels takes the second
+    form and must give the detections of the first -- which test_head_predict_vs_oracle pins to the oracle -- exactly."""
+    B, H, W = 2, 16, 16
+    cfg, head, anchors = _head_setup(7, H, W, 0.0)
+    x = torch.randn(B, H, W, 512, generator=torch.Generator().manual_seed(3)).to(DEV)
+    ex = {"anchors": [_t(a) for a in anchors], "metadata": [{"i": i} for i in range(B)]}
+    with torch.no_grad():
+        preds = head(x)
+        want = head.predict(ex, preds, cfg.test_cfg)
+        want = [want[b] for b in range(B)]
+        fused = preds[0]["_fused"]
+        order, box_off, cls_off = [], [], []
+        for t, task in enumerate(head.tasks):
+            box_off.append(len(order))
+            order += range(head._box_off[t], head._box_off[t] + task.conv_box.out_channels)
+            cls_off.append(len(order))
+            order += range(head._cls_off[t], head._cls_off[t] + task.conv_cls.out_channels)
+        assert sorted(order) == list(range(fused.shape[-1]))
+        assert cls_off[-1] + head.tasks[-1].conv_cls.out_channels - cls_off[0] > 128       # beyond the staged window
+        inter = fused[..., order].contiguous()
+        saved = head._box_off, head._cls_off
+        head._box_off, head._cls_off = box_off, cls_off
+        try:
+            got = head.predict(ex, [{"_fused": inter}], cfg.test_cfg)
+            got = [got[b] for b in range(B)]
+        finally:
+            head._box_off, head._cls_off = saved
+    for b in range(B):
+        assert len(want[b]["scores"]) > 50
+        for key in ("box3d_lidar", "scores", "label_preds"):
+            assert torch.equal(got[b][key], want[b][key]), (b, key)

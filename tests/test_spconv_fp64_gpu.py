@@ -396,3 +396,19 @@ def test_encoder_full_size_vs_fp64():
         assert e <= 1e-5, f"{math}: e = {e:.3e}"
     for math in ("f16x3", "bf16x6"):
         assert errs[math] <= 3.0 * errs["f32"], f"{math}: e = {errs[math]:.3e} > 3 e_f32 = {3 * errs['f32']:.3e}"
+
+
+# ---------------------------------------------------------------- 6. the four-channel VALU layer
+@pytest.mark.parametrize("geom", ["subm", "down"])
+def test_four_channel_valu_layer_vs_fp64(geom):
+    """4 -> 16 (sp_conv_kernel<4, 16>: points without a time channel) is built beside 5 -> 16 and no model of the suite
+    selects it: the f32 VALU structure against the float64 reference, e <= 1.5e-6 like every other structure."""
+    rng = np.random.default_rng(416 + len(geom))
+    shape, batch, n = [9, 41, 37], 3, 3001
+    _, coords = random_sparse(rng, batch, shape, n, 1)
+    for xmag in (1.0, 1e-15, 1e15):
+        case = Case(rng, coords, batch, shape, 4, 16, geom, xmag)
+        got = case.run(False)
+        assert np.isfinite(got).all()
+        e = case.err(got)
+        assert e <= 1.5e-6, f"{geom} 4->16 x{xmag:g}: e = {e:.3e}"

@@ -387,9 +387,8 @@ def test_fused_mlp_kernel_matches_float64_and_the_split_path(T_, C):
     ln_w, ln_b = torch.randn(C, generator=g) * 0.2 + 1.0, torch.randn(C, generator=g) * 0.1
     w1, b1 = torch.randn(4 * C, C, generator=g) / C ** 0.5, torch.randn(4 * C, generator=g) * 0.1
     w2, b2 = torch.randn(C, 4 * C, generator=g) / (4 * C) ** 0.5, torch.randn(C, generator=g) * 0.1
-    xd = x.double()
-    xn = F.layer_norm(xd, (C,), ln_w.double(), ln_b.double(), 1e-5)
-    ref = xd + F.gelu(xn @ w1.double().t() + b1.double()) @ w2.double().t() + b2.double()
+    from dense_fp64 import mlp_fp64
+    ref = mlp_fp64(x, ln_w, ln_b, w1, b1, w2, b2, 1e-5)
     dev = lambda t: t.to(DEV)
     pk = Tk.PackedMlp(dev(ln_w), dev(ln_b), 1e-5, dev(w1), dev(b1), dev(w2), dev(b2))
     got = Tk.mlp(dev(x).clone(), pk).cpu().double()
@@ -651,3 +650,27 @@ def test_fused_patch_embedding_matches_float64_and_the_three_launches(B, H, W, n
     e_f, e_s = float((fused.double() - ref).abs().max()), float((split.double() - ref).abs().max())
     print("fused", e_f / scale, "split", e_s / scale)
     assert e_f <= 3.0 * e_s + 2e-7 * scale and e_f <= 2e-6 * scale, (e_f, e_s, scale)
+
+
+@pytest.mark.parametrize("M,K,N", [(257, 96, 96), (300, 192, 576)])
+def test_token_gemm_f32_rows_in_pair_rows_out(M, K, N):
+    """f32 rows in, pair rows out (tok_linear_f16x3_kernel<2>; the other three row-format forms run in
+    test_token_gemm_is_fp32_class): the stored pair rows are the split of the f32-output launch, which meets the float64
+    gate of that test."""
+    from al3d import detector_ops as D
+    from al3d import token_ops as T
+    g = torch.Generator().manual_seed(M + K)
+    a = (torch.randn(M, K, generator=g) * torch.exp(torch.randn(M, K, generator=g))).to(DEV)
+    w = (torch.randn(N, K, generator=g) / K ** 0.5).to(DEV)
+    b = (torch.randn(N, generator=g) * 0.1).to(DEV)
+    pk = T.PackedLinear(w, b)
+    ref = a.double() @ w.double().t() + b.double()
+    scale = a.abs().double() @ w.abs().double().t() + b.abs().double()
+    got = T.linear(a, pk)
+    e3 = float(((got.double() - ref).abs() / scale).max())
+    e32 = float((((a @ w.t() + b).double() - ref).abs() / scale).max())
+    assert e3 < 1.5e-6 and e3 < 3.0 * e32 + 1e-7, (e3, e32)
+    pair = T.linear(a, pk, out_pair=True)
+    assert torch.equal(pair.view(torch.int32), D.rows_convert(got, True).view(torch.int32))
+    back = D.rows_convert(pair, False)
+    assert bool(((back - got).abs() <= 2.0 ** -21 * got.abs() + 2.0 ** -35).all())
