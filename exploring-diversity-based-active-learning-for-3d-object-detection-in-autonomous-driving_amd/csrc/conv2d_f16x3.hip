@@ -52,12 +52,35 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
-// AL3D_F3_MAP=band (default) | rr: see f3_tile_of_block
-static inline int f3_map_default()
+// This file's A/B knobs, read from the environment once per process (the same bits under every setting)
+struct F3Knobs {
+    int xmap;          // AL3D_F3_MAP=band (default) | rr: see f3_tile_of_block
+    int frag_direct;   // AL3D_FRAG_EPI=direct: the streamed 3x3 kernel's untransposed f32 epilogue everywhere
+    int frag_shape;    // AL3D_FRAG_SHAPE=2 (default) | 1 | 0: its wave shape, see al3d_conv3x3_nhwc_f16x3_frag
+    int dma_stages;    // AL3D_DMA_STAGES=3 (default: 48 KB, three workgroups per CU, measured best) | 4 | 5
+    int dma_pipe;      // AL3D_DMA_PIPE=1 (default: conv2d_f16x3_dma2_kernel) | 0 (conv2d_f16x3_dma_kernel)
+    int dma_direct;    // AL3D_DMA_EPI=direct: the LDS-DMA kernel's untransposed dword stores everywhere
+};
+static const F3Knobs& f3_knobs()
 {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("AL3D_F3_MAP"); v = !(e && e[0] == 'r'); }
-    return v;
+    static const F3Knobs knobs = [] {
+        F3Knobs k;
+        const char* e = getenv("AL3D_F3_MAP");
+        k.xmap = !(e && e[0] == 'r');
+        e = getenv("AL3D_FRAG_EPI");
+        k.frag_direct = e && e[0] == 'd';
+        e = getenv("AL3D_FRAG_SHAPE");
+        k.frag_shape = e ? atoi(e) : 2;
+        e = getenv("AL3D_DMA_STAGES");
+        k.dma_stages = e ? atoi(e) : 3;
+        if (k.dma_stages != 3 && k.dma_stages != 4 && k.dma_stages != 5) k.dma_stages = 3;
+        e = getenv("AL3D_DMA_PIPE");
+        k.dma_pipe = e ? atoi(e) != 0 : 1;
+        e = getenv("AL3D_DMA_EPI");
+        k.dma_direct = e && e[0] == 'd';
+        return k;
+    }();
+    return knobs;
 }
 
 struct ConvF3Params {
@@ -73,7 +96,7 @@ struct ConvF3Params {
     int64_t plane;          // elements per weight plane = Cout * taps * Cin
     float* gap;             // optional [B][gap_parts][ldc]: per-workgroup channel sums of the stored values (fused GAP)
     int gap_parts;
-    int xmap = f3_map_default();   // workgroup -> (pixel tile, column block) order, see f3_tile_of_block
+    int xmap = f3_knobs().xmap;    // workgroup -> (pixel tile, column block) order, see f3_tile_of_block
     int io = 0;             // row formats of in / out (sp_rows.h: bit 0 = in pair pixels, bit 1 = write pair pixels); DMA kernel only
 };
 
@@ -1135,50 +1158,88 @@ extern "C" int al3d_pack_f16x3_bstream(const void* planes_f16x2, int Cout, int t
     return AL3D_OK;
 }
 
+// ------------------------------------------------------------------ host side: one parameter builder for every launch
+// What a kernel family asks of a launch: its workgroup's pixel tile, whether the kernel strides over two weight planes
+// (the fragment-ordered and LDS-image formats of the generic kernels interleave them: plane = 0), and the checks it
+// adds to convf3_check
+struct ConvF3Family {
+    int th, tw;
+    bool planes;         // p.plane = Cout * taps * Cin
+    int cin_mult;        // > 0, the fragment-streamed 3x3 kernels: Cout % 128 == 0 and Cin % cin_mult == 0
+    bool dma;            // the LDS-DMA kernel: io flags, 32-bit input offsets
+};
+static const ConvF3Family F3_FAM_LDS = {F3_TH, F3_TW, true, 0, false}, F3_FAM_HALO = {G3_TH, G3_TW, true, 0, false},
+                          F3_FAM_BSTREAM = {F3_TH, F3_TW, false, 0, false}, F3_FAM_FRAG = {G3_TH, G3_TW, true, 32, false},
+                          F3_FAM_FRAG16 = {G3_TH, G3_TW, true, 64, false}, F3_FAM_DMA = {F3_TH, F3_TW, false, 0, true};
+
+// Checks the arguments of entry point `name`, fills the parameters and calls launch(p, grid); `kernel` names the launch in
+// a launch error.  deconv: the 2x2 / stride-2 transposed conv (pixel tiles over the input map, one grid plane per tap;
+// ksize, stride, pad = 2, 2, 0).  gap may be null; io: sp_rows.h flags (LDS-DMA family, 0 elsewhere)
+template <class Launch>
+static int convf3_launch(const char* name, const char* kernel, const ConvF3Family& fam, const float* in, const void* wgt,
+                         const float* scale, const float* shift, float* out, int B, int H, int W, int Cin, int Cout,
+                         int ksize, int stride, int pad, bool deconv, int ldc, int coff, int relu, float* gap,
+                         int gap_parts, int io, Launch&& launch)
+{
+    ConvF3Params p;
+    p.gap = gap; p.gap_parts = gap_parts; p.io = io;
+    p.in = in; p.wgt = (const _Float16*)wgt; p.scale = scale; p.shift = shift; p.out = out;
+    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
+    p.ksize = ksize; p.stride = stride; p.pad = pad; p.ldc = ldc; p.coff = coff; p.relu = relu;
+    if (fam.dma) {
+        AL3D_REQUIRE(io >= 0 && io < 4 && (!(io & 2) || (Cout % 8 == 0 && ldc % 8 == 0 && coff % 8 == 0)),
+                     "%s: bad io flags (pair output needs Cout, ldc, coff multiples of 8)", name);
+        AL3D_REQUIRE(io == 0 || (f3_knobs().dma_pipe && f3_knobs().dma_stages == 3),
+                     "%s: pair pixels need the shipped kernel shape (AL3D_DMA_PIPE=1, 3 stages)", name);
+    }
+    AL3D_REQUIRE(ksize >= 1 && ksize <= 7 && stride >= 1 && pad >= 0, "%s: bad geometry", name);
+    p.OH = deconv ? 2 * H : (H + 2 * pad - ksize) / stride + 1;
+    p.OW = deconv ? 2 * W : (W + 2 * pad - ksize) / stride + 1;
+    AL3D_REQUIRE(deconv || (p.OH >= 1 && p.OW >= 1), "%s: empty output", name);
+    p.plane = fam.planes ? (int64_t)Cout * (deconv ? 4 : ksize * ksize) * Cin : 0;
+    int rc = convf3_check(p, name);
+    if (rc) return rc;
+    AL3D_REQUIRE(!fam.cin_mult || (Cout % 128 == 0 && Cin % fam.cin_mult == 0),
+                 "%s: needs Cout %% 128 == 0 and Cin %% %d == 0 (got %d, %d)", name, fam.cin_mult, Cout, Cin);
+    AL3D_REQUIRE(!fam.dma || (int64_t)B * H * W * Cin < ((int64_t)1 << 31), "%s: input above 2^31 elements", name);
+    AL3D_REQUIRE(!gap || gap_parts >= al3d_gap_parts_count(p.OH, p.OW, deconv),
+                 "%s: gap_parts must be at least al3d_gap_parts_count(OH, OW, %d)", name, (int)deconv);
+    p.tiles_x = (int)al3d_cdiv(deconv ? W : p.OW, fam.tw);
+    p.tiles_y = (int)al3d_cdiv(deconv ? H : p.OH, fam.th);
+    p.ntiles = p.tiles_x * p.tiles_y * B; p.nblocks = (int)al3d_cdiv(Cout, F3_BN);
+    launch(p, deconv ? dim3(f3_grid(p), 1, 4) : dim3(f3_grid(p)));
+    AL3D_CHECK_LAUNCH(kernel);
+    return AL3D_OK;
+}
+
+// f(integral_constant<int, V>) for the first V that equals v, for the last V when none does: one instantiation of f per V
+template <int... V, class F> static void f3_switch(int v, F&& f)
+{
+    constexpr int vals[] = {V...}, last = vals[sizeof...(V) - 1];
+    (void)(... || ((v == V || V == last) && (f(F3_IC(V)), true)));
+}
+
 extern "C" int al3d_conv2d_nhwc_f16x3_bstream(const float* in, const void* wgt_frag, const float* scale,
                                               const float* shift, float* out, int B, int H, int W, int Cin,
                                               int Cout, int ksize, int stride, int pad, int ldc, int coff,
                                               int relu, void* stream)
 {
-    ConvF3Params p;
-    p.gap = nullptr; p.gap_parts = 0;
-    p.in = in; p.wgt = (const _Float16*)wgt_frag; p.scale = scale; p.shift = shift; p.out = out;
-    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
-    p.ksize = ksize; p.stride = stride; p.pad = pad; p.ldc = ldc; p.coff = coff; p.relu = relu;
-    AL3D_REQUIRE(ksize >= 1 && ksize <= 7 && stride >= 1 && pad >= 0, "al3d_conv2d_nhwc_f16x3_bstream: bad geometry");
-    p.OH = (H + 2 * pad - ksize) / stride + 1;
-    p.OW = (W + 2 * pad - ksize) / stride + 1;
-    AL3D_REQUIRE(p.OH >= 1 && p.OW >= 1, "al3d_conv2d_nhwc_f16x3_bstream: empty output");
-    p.plane = 0;
-    int rc = convf3_check(p, "al3d_conv2d_nhwc_f16x3_bstream");
-    if (rc) return rc;
-    p.tiles_x = (int)al3d_cdiv(p.OW, F3_TW);
-    p.tiles_y = (int)al3d_cdiv(p.OH, F3_TH);
-    p.ntiles = p.tiles_x * p.tiles_y * B; p.nblocks = (int)al3d_cdiv(Cout, F3_BN);
-    hipLaunchKernelGGL(conv2d_f16x3_bstream_kernel<0>, dim3(f3_grid(p)), dim3(256), 0, (hipStream_t)stream, p);
-    AL3D_CHECK_LAUNCH("conv2d_f16x3_bstream_kernel<conv>");
-    return AL3D_OK;
+    return convf3_launch("al3d_conv2d_nhwc_f16x3_bstream", "conv2d_f16x3_bstream_kernel<conv>", F3_FAM_BSTREAM, in, wgt_frag,
+                         scale, shift, out, B, H, W, Cin, Cout, ksize, stride, pad, false, ldc, coff, relu, nullptr, 0, 0,
+                         [&](const ConvF3Params& p, dim3 grid) {
+        hipLaunchKernelGGL(conv2d_f16x3_bstream_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    });
 }
 
 extern "C" int al3d_deconv2x2_nhwc_f16x3_bstream(const float* in, const void* wgt_frag, const float* scale,
                                                  const float* shift, float* out, int B, int H, int W, int Cin,
                                                  int Cout, int ldc, int coff, int relu, void* stream)
 {
-    ConvF3Params p;
-    p.gap = nullptr; p.gap_parts = 0;
-    p.in = in; p.wgt = (const _Float16*)wgt_frag; p.scale = scale; p.shift = shift; p.out = out;
-    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
-    p.ksize = 2; p.stride = 2; p.pad = 0; p.ldc = ldc; p.coff = coff; p.relu = relu;
-    p.OH = 2 * H; p.OW = 2 * W;
-    p.plane = 0;
-    int rc = convf3_check(p, "al3d_deconv2x2_nhwc_f16x3_bstream");
-    if (rc) return rc;
-    p.tiles_x = (int)al3d_cdiv(W, F3_TW);
-    p.tiles_y = (int)al3d_cdiv(H, F3_TH);
-    p.ntiles = p.tiles_x * p.tiles_y * B; p.nblocks = (int)al3d_cdiv(Cout, F3_BN);
-    hipLaunchKernelGGL(conv2d_f16x3_bstream_kernel<1>, dim3(f3_grid(p), 1, 4), dim3(256), 0, (hipStream_t)stream, p);
-    AL3D_CHECK_LAUNCH("conv2d_f16x3_bstream_kernel<deconv>");
-    return AL3D_OK;
+    return convf3_launch("al3d_deconv2x2_nhwc_f16x3_bstream", "conv2d_f16x3_bstream_kernel<deconv>", F3_FAM_BSTREAM, in,
+                         wgt_frag, scale, shift, out, B, H, W, Cin, Cout, 2, 2, 0, true, ldc, coff, relu, nullptr, 0, 0,
+                         [&](const ConvF3Params& p, dim3 grid) {
+        hipLaunchKernelGGL(conv2d_f16x3_bstream_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    });
 }
 
 // planes [2][Cout][9][Cin] (al3d_split_f16x3) -> fragment order [2][Cout/32][Cin/16][9][64][8]
@@ -1247,30 +1308,34 @@ extern "C" int al3d_conv3x3_nhwc_f16x3_frag16(const float* in, const void* wgt_f
                                               const float* shift, float* out, int B, int H, int W, int Cin,
                                               int Cout, int ldc, int coff, int relu, void* stream)
 {
-    ConvF3Params p;
-    p.gap = nullptr; p.gap_parts = 0;
-    p.in = in; p.wgt = (const _Float16*)wgt_frag16; p.scale = scale; p.shift = shift; p.out = out;
-    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
-    p.ksize = 3; p.stride = 1; p.pad = 1; p.ldc = ldc; p.coff = coff; p.relu = relu;
-    p.OH = H; p.OW = W;
-    p.plane = (int64_t)Cout * 9 * Cin;
-    AL3D_REQUIRE(in && wgt_frag16 && out && scale, "al3d_conv3x3_nhwc_f16x3_frag16: null pointer");
-    AL3D_REQUIRE(B >= 1 && H >= 1 && W >= 1, "al3d_conv3x3_nhwc_f16x3_frag16: bad shape");
-    AL3D_REQUIRE(Cout % 128 == 0 && Cin % 64 == 0 && Cout >= 128 && Cin >= 64,
-                 "al3d_conv3x3_nhwc_f16x3_frag16: needs Cout %% 128 == 0 and Cin %% 64 == 0 (got %d, %d)", Cout, Cin);
-    AL3D_REQUIRE(coff >= 0 && coff + Cout <= ldc, "al3d_conv3x3_nhwc_f16x3_frag16: channel window exceeds ldc=%d", ldc);
-    AL3D_REQUIRE(((uintptr_t)in & 15) == 0 && ((uintptr_t)wgt_frag16 & 15) == 0,
-                 "al3d_conv3x3_nhwc_f16x3_frag16: in/wgt must be 16-byte aligned");
-    p.tiles_x = (int)al3d_cdiv(p.OW, G3_TW);
-    p.tiles_y = (int)al3d_cdiv(p.OH, G3_TH);
-    p.ntiles = p.tiles_x * p.tiles_y * B; p.nblocks = Cout / F3_BN;
-    hipLaunchKernelGGL(conv3x3_f16x3_frag16_kernel, dim3(f3_grid(p)), dim3(256), 0, (hipStream_t)stream, p);
-    AL3D_CHECK_LAUNCH("conv3x3_f16x3_frag16_kernel");
-    return AL3D_OK;
+    return convf3_launch("al3d_conv3x3_nhwc_f16x3_frag16", "conv3x3_f16x3_frag16_kernel", F3_FAM_FRAG16, in, wgt_frag16, scale,
+                         shift, out, B, H, W, Cin, Cout, 3, 1, 1, false, ldc, coff, relu, nullptr, 0, 0,
+                         [&](const ConvF3Params& p, dim3 grid) {
+        hipLaunchKernelGGL(conv3x3_f16x3_frag16_kernel, grid, dim3(256), 0, (hipStream_t)stream, p);
+    });
 }
 
+// Epilogue (first template argument): 2 = pair pixels, 1 = untransposed f32 stores (AL3D_FRAG_EPI=direct, or a window the
+// 16-byte stores cannot serve), 0 = 16-byte stores.  Wave shape (second): 2 (default, round 5) = four image rows x ONE
+// 32-channel tile per wave, the next chunk's halo halves in their own registers (requested at taps 0 / 1, stored at taps
+// 4 / 5); 1 = the same wave shape with the halves sharing two registers (requested at 0 / 3, stored at 2 / 5); 0 = round 1's
+// two rows x two tiles (AL3D_FRAG_SHAPE=0|1 for A/B).  Same bits; the nine `<0>` launches of the neck: 1,670 (shape 0) ->
+// 1,607 (1) -> 1,597 us (2) on one box
 static int conv3x3_frag_impl(const float* in, const void* wgt_frag, const float* scale, const float* shift, float* out,
-                             int B, int H, int W, int Cin, int Cout, int ldc, int coff, int relu, int io, void* stream);
+                             int B, int H, int W, int Cin, int Cout, int ldc, int coff, int relu, int io, void* stream)
+{
+    const bool vec_ok = ldc % 4 == 0 && coff % 4 == 0 && ((uintptr_t)out & 15) == 0;
+    const int epi = (io & SP_IO_OUT_PAIR) ? 2 : (f3_knobs().frag_direct || !vec_ok) ? 1 : 0;
+    const int shape = f3_knobs().frag_shape == 2 ? 2 : f3_knobs().frag_shape ? 1 : 0;
+    return convf3_launch("al3d_conv3x3_nhwc_f16x3_frag", "conv3x3_f16x3_frag_kernel", F3_FAM_FRAG, in, wgt_frag, scale, shift,
+                         out, B, H, W, Cin, Cout, 3, 1, 1, false, ldc, coff, relu, nullptr, 0, 0,
+                         [&](const ConvF3Params& p, dim3 grid) {
+        f3_switch<2, 1, 0>(shape, [&](auto shape_) { f3_switch<2, 1, 0>(epi, [&](auto epi_) {
+            hipLaunchKernelGGL((conv3x3_f16x3_frag_kernel<decltype(epi_)::value, decltype(shape_)::value>), grid, dim3(256), 0,
+                               (hipStream_t)stream, p);
+        }); });
+    });
+}
 
 extern "C" int al3d_conv3x3_nhwc_f16x3_frag(const float* in, const void* wgt_frag, const float* scale,
                                             const float* shift, float* out, int B, int H, int W, int Cin,
@@ -1287,52 +1352,6 @@ extern "C" int al3d_conv3x3_nhwc_f16x3_frag_io(const float* in, const void* wgt_
     AL3D_REQUIRE(io == 0 || (io == 2 && ldc % 8 == 0 && coff % 8 == 0),
                  "al3d_conv3x3_nhwc_f16x3_frag_io: io must be 0 or 2 (pair output; ldc, coff multiples of 8)");
     return conv3x3_frag_impl(in, wgt_frag, scale, shift, out, B, H, W, Cin, Cout, ldc, coff, relu, io, stream);
-}
-
-static int conv3x3_frag_impl(const float* in, const void* wgt_frag, const float* scale, const float* shift, float* out,
-                             int B, int H, int W, int Cin, int Cout, int ldc, int coff, int relu, int io, void* stream)
-{
-    ConvF3Params p;
-    p.gap = nullptr; p.gap_parts = 0;
-    p.in = in; p.wgt = (const _Float16*)wgt_frag; p.scale = scale; p.shift = shift; p.out = out;
-    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
-    p.ksize = 3; p.stride = 1; p.pad = 1; p.ldc = ldc; p.coff = coff; p.relu = relu;
-    p.OH = H; p.OW = W;
-    p.plane = (int64_t)Cout * 9 * Cin;
-    AL3D_REQUIRE(in && wgt_frag && out && scale, "al3d_conv3x3_nhwc_f16x3_frag: null pointer");
-    AL3D_REQUIRE(B >= 1 && H >= 1 && W >= 1, "al3d_conv3x3_nhwc_f16x3_frag: bad shape");
-    AL3D_REQUIRE(Cout % 128 == 0 && Cin % 32 == 0 && Cout >= 128 && Cin >= 32,
-                 "al3d_conv3x3_nhwc_f16x3_frag: needs Cout %% 128 == 0 and Cin %% 32 == 0 (got %d, %d)", Cout, Cin);
-    AL3D_REQUIRE(coff >= 0 && coff + Cout <= ldc, "al3d_conv3x3_nhwc_f16x3_frag: channel window exceeds ldc=%d", ldc);
-    AL3D_REQUIRE(((uintptr_t)in & 15) == 0 && ((uintptr_t)wgt_frag & 15) == 0,
-                 "al3d_conv3x3_nhwc_f16x3_frag: in/wgt must be 16-byte aligned");
-    p.tiles_x = (int)al3d_cdiv(p.OW, G3_TW);
-    p.tiles_y = (int)al3d_cdiv(p.OH, G3_TH);
-    p.ntiles = p.tiles_x * p.tiles_y * B; p.nblocks = Cout / F3_BN;
-    static int direct = -1;                            // AL3D_FRAG_EPI=direct: the untransposed f32 epilogue, for A/B
-    if (direct < 0) { const char* e = getenv("AL3D_FRAG_EPI"); direct = e && e[0] == 'd'; }
-    const bool vec_ok = ldc % 4 == 0 && coff % 4 == 0 && ((uintptr_t)out & 15) == 0;
-    // wave shape: 2 (default, round 5) = four image rows x ONE 32-channel tile per wave, the next chunk's halo halves in their
-    // own registers (requested at taps 0 / 1, stored at taps 4 / 5); 1 = the same wave shape with the halves sharing two registers
-    // (requested at 0 / 3, stored at 2 / 5); 0 = round 1's two rows x two tiles (AL3D_FRAG_SHAPE=0|1 for A/B).  Same bits; the
-    // nine `<0>` launches of the neck: 1,670 (shape 0) -> 1,607 (1) -> 1,597 us (2) on one box
-    static int shape = -1;
-    if (shape < 0) { const char* e = getenv("AL3D_FRAG_SHAPE"); shape = e ? atoi(e) : 2; }
-    if (shape == 2) {
-        if (io & SP_IO_OUT_PAIR) hipLaunchKernelGGL((conv3x3_f16x3_frag_kernel<2, 2>), dim3(f3_grid(p)), dim3(256), 0, (hipStream_t)stream, p);
-        else if (direct || !vec_ok) hipLaunchKernelGGL((conv3x3_f16x3_frag_kernel<1, 2>), dim3(f3_grid(p)), dim3(256), 0, (hipStream_t)stream, p);
-        else hipLaunchKernelGGL((conv3x3_f16x3_frag_kernel<0, 2>), dim3(f3_grid(p)), dim3(256), 0, (hipStream_t)stream, p);
-    }
-    else if (shape) {
-        if (io & SP_IO_OUT_PAIR) hipLaunchKernelGGL((conv3x3_f16x3_frag_kernel<2, 1>), dim3(f3_grid(p)), dim3(256), 0, (hipStream_t)stream, p);
-        else if (direct || !vec_ok) hipLaunchKernelGGL((conv3x3_f16x3_frag_kernel<1, 1>), dim3(f3_grid(p)), dim3(256), 0, (hipStream_t)stream, p);
-        else hipLaunchKernelGGL((conv3x3_f16x3_frag_kernel<0, 1>), dim3(f3_grid(p)), dim3(256), 0, (hipStream_t)stream, p);
-    }
-    else if (io & SP_IO_OUT_PAIR) hipLaunchKernelGGL(conv3x3_f16x3_frag_kernel<2>, dim3(f3_grid(p)), dim3(256), 0, (hipStream_t)stream, p);
-    else if (direct || !vec_ok) hipLaunchKernelGGL(conv3x3_f16x3_frag_kernel<1>, dim3(f3_grid(p)), dim3(256), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(conv3x3_f16x3_frag_kernel<0>, dim3(f3_grid(p)), dim3(256), 0, (hipStream_t)stream, p);
-    AL3D_CHECK_LAUNCH("conv3x3_f16x3_frag_kernel");
-    return AL3D_OK;
 }
 
 // one-off weight split: f32 [count] * 2^sexp -> f16 [2][count] (wh, wl)
@@ -1376,39 +1395,19 @@ extern "C" int al3d_gap_reduce_parts_f32(const float* gap_part, int B, int parts
     return AL3D_OK;
 }
 
-static int conv2d_f16x3_impl(const float* in, const void* wgt_f16x3, const float* scale,
+static int conv2d_f16x3_impl(const char* name, const float* in, const void* wgt_f16x3, const float* scale,
                              const float* shift, float* out, int B, int H, int W, int Cin,
                              int Cout, int ksize, int stride, int pad, int ldc, int coff,
                              int relu, float* gap_part, int gap_parts, void* stream)
 {
-    ConvF3Params p;
-    p.gap = gap_part; p.gap_parts = gap_parts;
-    p.in = in; p.wgt = (const _Float16*)wgt_f16x3; p.scale = scale; p.shift = shift; p.out = out;
-    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
-    p.ksize = ksize; p.stride = stride; p.pad = pad; p.ldc = ldc; p.coff = coff; p.relu = relu;
-    AL3D_REQUIRE(ksize >= 1 && ksize <= 7 && stride >= 1 && pad >= 0, "al3d_conv2d_nhwc_f16x3: bad geometry");
-    p.OH = (H + 2 * pad - ksize) / stride + 1;
-    p.OW = (W + 2 * pad - ksize) / stride + 1;
-    AL3D_REQUIRE(p.OH >= 1 && p.OW >= 1, "al3d_conv2d_nhwc_f16x3: empty output");
-    p.plane = (int64_t)Cout * ksize * ksize * Cin;
-    int rc = convf3_check(p, "al3d_conv2d_nhwc_f16x3");
-    if (rc) return rc;
-    AL3D_REQUIRE(!gap_part || gap_parts >= al3d_gap_parts_count(p.OH, p.OW, 0),
-                 "al3d_conv2d_nhwc_f16x3_gap: gap_parts must be at least al3d_gap_parts_count(OH, OW, 0)");
-    if (!gap_part && ksize == 3 && stride == 1 && pad == 1 && Cin % (2 * F3_BK) == 0) {     // halo-staged fast path (chunk pairs)
-        p.tiles_x = (int)al3d_cdiv(p.OW, G3_TW);
-        p.tiles_y = (int)al3d_cdiv(p.OH, G3_TH);
-        p.ntiles = p.tiles_x * p.tiles_y * B; p.nblocks = (int)al3d_cdiv(Cout, F3_BN);
-        hipLaunchKernelGGL(conv3x3_f16x3_halo_kernel, dim3(f3_grid(p)), dim3(256), 0, (hipStream_t)stream, p);
-        AL3D_CHECK_LAUNCH("conv3x3_f16x3_halo_kernel");
-        return AL3D_OK;
-    }
-    p.tiles_x = (int)al3d_cdiv(p.OW, F3_TW);
-    p.tiles_y = (int)al3d_cdiv(p.OH, F3_TH);
-    p.ntiles = p.tiles_x * p.tiles_y * B; p.nblocks = (int)al3d_cdiv(Cout, F3_BN);
-    hipLaunchKernelGGL(conv2d_f16x3_kernel<0>, dim3(f3_grid(p)), dim3(256), 0, (hipStream_t)stream, p);
-    AL3D_CHECK_LAUNCH("conv2d_f16x3_kernel<conv>");
-    return AL3D_OK;
+    // halo-staged fast path (chunk pairs): 3x3/s1/p1 without the fused GAP
+    const bool halo = !gap_part && ksize == 3 && stride == 1 && pad == 1 && Cin % (2 * F3_BK) == 0;
+    return convf3_launch(name, halo ? "conv3x3_f16x3_halo_kernel" : "conv2d_f16x3_kernel<conv>", halo ? F3_FAM_HALO : F3_FAM_LDS,
+                         in, wgt_f16x3, scale, shift, out, B, H, W, Cin, Cout, ksize, stride, pad, false, ldc, coff, relu,
+                         gap_part, gap_parts, 0, [&](const ConvF3Params& p, dim3 grid) {
+        if (halo) hipLaunchKernelGGL(conv3x3_f16x3_halo_kernel, grid, dim3(256), 0, (hipStream_t)stream, p);
+        else hipLaunchKernelGGL(conv2d_f16x3_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    });
 }
 
 extern "C" int al3d_conv2d_nhwc_f16x3(const float* in, const void* wgt_f16x3, const float* scale,
@@ -1416,8 +1415,8 @@ extern "C" int al3d_conv2d_nhwc_f16x3(const float* in, const void* wgt_f16x3, co
                                       int Cout, int ksize, int stride, int pad, int ldc, int coff,
                                       int relu, void* stream)
 {
-    return conv2d_f16x3_impl(in, wgt_f16x3, scale, shift, out, B, H, W, Cin, Cout, ksize, stride, pad, ldc, coff, relu,
-                             nullptr, 0, stream);
+    return conv2d_f16x3_impl("al3d_conv2d_nhwc_f16x3", in, wgt_f16x3, scale, shift, out, B, H, W, Cin, Cout, ksize, stride, pad,
+                             ldc, coff, relu, nullptr, 0, stream);
 }
 
 extern "C" int al3d_conv2d_nhwc_f16x3_gap(const float* in, const void* wgt_f16x3, const float* scale,
@@ -1426,38 +1425,26 @@ extern "C" int al3d_conv2d_nhwc_f16x3_gap(const float* in, const void* wgt_f16x3
                                           int relu, float* gap_part, int gap_parts, void* stream)
 {
     AL3D_REQUIRE(gap_part, "al3d_conv2d_nhwc_f16x3_gap: null gap_part");
-    return conv2d_f16x3_impl(in, wgt_f16x3, scale, shift, out, B, H, W, Cin, Cout, ksize, stride, pad, ldc, coff, relu,
-                             gap_part, gap_parts, stream);
+    return conv2d_f16x3_impl("al3d_conv2d_nhwc_f16x3_gap", in, wgt_f16x3, scale, shift, out, B, H, W, Cin, Cout, ksize, stride,
+                             pad, ldc, coff, relu, gap_part, gap_parts, stream);
 }
 
-static int deconv2x2_f16x3_impl(const float* in, const void* wgt_f16x3, const float* scale,
+static int deconv2x2_f16x3_impl(const char* name, const float* in, const void* wgt_f16x3, const float* scale,
                                 const float* shift, float* out, int B, int H, int W, int Cin,
                                 int Cout, int ldc, int coff, int relu, float* gap_part, int gap_parts, void* stream)
 {
-    ConvF3Params p;
-    p.gap = gap_part; p.gap_parts = gap_parts;
-    p.in = in; p.wgt = (const _Float16*)wgt_f16x3; p.scale = scale; p.shift = shift; p.out = out;
-    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
-    p.ksize = 2; p.stride = 2; p.pad = 0; p.ldc = ldc; p.coff = coff; p.relu = relu;
-    p.OH = 2 * H; p.OW = 2 * W;
-    p.plane = (int64_t)Cout * 4 * Cin;
-    int rc = convf3_check(p, "al3d_deconv2x2_nhwc_f16x3");
-    if (rc) return rc;
-    p.tiles_x = (int)al3d_cdiv(W, F3_TW);
-    p.tiles_y = (int)al3d_cdiv(H, F3_TH);
-    p.ntiles = p.tiles_x * p.tiles_y * B; p.nblocks = (int)al3d_cdiv(Cout, F3_BN);
-    AL3D_REQUIRE(!gap_part || gap_parts >= al3d_gap_parts_count(p.OH, p.OW, 1),
-                 "al3d_deconv2x2_nhwc_f16x3_gap: gap_parts must be at least al3d_gap_parts_count(2H, 2W, 1)");
-    hipLaunchKernelGGL(conv2d_f16x3_kernel<1>, dim3(f3_grid(p), 1, 4), dim3(256), 0, (hipStream_t)stream, p);
-    AL3D_CHECK_LAUNCH("conv2d_f16x3_kernel<deconv>");
-    return AL3D_OK;
+    return convf3_launch(name, "conv2d_f16x3_kernel<deconv>", F3_FAM_LDS, in, wgt_f16x3, scale, shift, out, B, H, W, Cin, Cout,
+                         2, 2, 0, true, ldc, coff, relu, gap_part, gap_parts, 0, [&](const ConvF3Params& p, dim3 grid) {
+        hipLaunchKernelGGL(conv2d_f16x3_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    });
 }
 
 extern "C" int al3d_deconv2x2_nhwc_f16x3(const float* in, const void* wgt_f16x3, const float* scale,
                                          const float* shift, float* out, int B, int H, int W, int Cin,
                                          int Cout, int ldc, int coff, int relu, void* stream)
 {
-    return deconv2x2_f16x3_impl(in, wgt_f16x3, scale, shift, out, B, H, W, Cin, Cout, ldc, coff, relu, nullptr, 0, stream);
+    return deconv2x2_f16x3_impl("al3d_deconv2x2_nhwc_f16x3", in, wgt_f16x3, scale, shift, out, B, H, W, Cin, Cout, ldc, coff,
+                                relu, nullptr, 0, stream);
 }
 
 extern "C" int al3d_deconv2x2_nhwc_f16x3_gap(const float* in, const void* wgt_f16x3, const float* scale,
@@ -1466,8 +1453,8 @@ extern "C" int al3d_deconv2x2_nhwc_f16x3_gap(const float* in, const void* wgt_f1
                                              void* stream)
 {
     AL3D_REQUIRE(gap_part, "al3d_deconv2x2_nhwc_f16x3_gap: null gap_part");
-    return deconv2x2_f16x3_impl(in, wgt_f16x3, scale, shift, out, B, H, W, Cin, Cout, ldc, coff, relu, gap_part, gap_parts,
-                                stream);
+    return deconv2x2_f16x3_impl("al3d_deconv2x2_nhwc_f16x3_gap", in, wgt_f16x3, scale, shift, out, B, H, W, Cin, Cout, ldc,
+                                coff, relu, gap_part, gap_parts, stream);
 }
 
 // ------------------------------------------------------------------ any geometry, both operands by LDS-DMA
@@ -1966,55 +1953,25 @@ extern "C" int al3d_pack_f16x3_dma(const void* planes_f16x2, int Cout, int taps,
     return AL3D_OK;
 }
 
-static int dma_stages()
-{
-    static int ns = 0;
-    if (!ns) {
-        const char* e = getenv("AL3D_DMA_STAGES");
-        ns = e ? atoi(e) : 3;                          // 3 stages = 48 KB: three workgroups per CU (measured best)
-        if (ns != 3 && ns != 4 && ns != 5) ns = 3;
-    }
-    return ns;
-}
-
-static int dma_pipe()
-{
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("AL3D_DMA_PIPE");
-        v = e ? atoi(e) != 0 : 1;
-    }
-    return v;
-}
-
+// Epilogue form: 16-byte stores through an LDS transposition need Cout, ldc, coff multiples of 4 and an aligned base; else
+// (or AL3D_DMA_EPI=direct, for A/B) untransposed dword stores.  The shipped shape (AL3D_DMA_PIPE=1, 3 stages) has all row /
+// pixel format combinations; the others f32 pixels and dword stores only
 template <int MODE> static void launch_dma(const ConvF3Params& p, dim3 grid, hipStream_t s)
 {
-    // epilogue form: 16-byte stores through an LDS transposition need Cout, ldc, coff multiples of 4 and an aligned base
-    static int direct = -1;                            // AL3D_DMA_EPI=direct: untransposed dword stores everywhere, for A/B
-    if (direct < 0) { const char* e = getenv("AL3D_DMA_EPI"); direct = e && e[0] == 'd'; }
+    const F3Knobs& k = f3_knobs();
     const bool vec_ok = p.Cout % 4 == 0 && p.ldc % 4 == 0 && p.coff % 4 == 0 && ((uintptr_t)p.out & 15) == 0;
-    if (dma_pipe() && dma_stages() == 3) {             // the shipped shape: all row / pixel format combinations
-        const int io = p.io | ((p.io & 2) == 0 && (direct || !vec_ok) ? 4 : 0);
-        switch (io) {
-        case 0: hipLaunchKernelGGL((conv2d_f16x3_dma2_kernel<MODE, 3, 0>), grid, dim3(256), 0, s, p); break;
-        case 1: hipLaunchKernelGGL((conv2d_f16x3_dma2_kernel<MODE, 3, 1>), grid, dim3(256), 0, s, p); break;
-        case 2: hipLaunchKernelGGL((conv2d_f16x3_dma2_kernel<MODE, 3, 2>), grid, dim3(256), 0, s, p); break;
-        case 3: hipLaunchKernelGGL((conv2d_f16x3_dma2_kernel<MODE, 3, 3>), grid, dim3(256), 0, s, p); break;
-        case 4: hipLaunchKernelGGL((conv2d_f16x3_dma2_kernel<MODE, 3, 4>), grid, dim3(256), 0, s, p); break;
-        default: hipLaunchKernelGGL((conv2d_f16x3_dma2_kernel<MODE, 3, 5>), grid, dim3(256), 0, s, p); break;
-        }
-        return;
-    }
-    if (dma_pipe()) {
-        if (dma_stages() == 5) hipLaunchKernelGGL((conv2d_f16x3_dma2_kernel<MODE, 5, 4>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((conv2d_f16x3_dma2_kernel<MODE, 4, 4>), grid, dim3(256), 0, s, p);
-        return;
-    }
-    switch (dma_stages()) {
-    case 4: hipLaunchKernelGGL((conv2d_f16x3_dma_kernel<MODE, 4>), grid, dim3(256), 0, s, p); break;
-    case 5: hipLaunchKernelGGL((conv2d_f16x3_dma_kernel<MODE, 5>), grid, dim3(256), 0, s, p); break;
-    default: hipLaunchKernelGGL((conv2d_f16x3_dma_kernel<MODE, 3>), grid, dim3(256), 0, s, p); break;
-    }
+    if (k.dma_pipe && k.dma_stages == 3)
+        f3_switch<0, 1, 2, 3, 4, 5>(p.io | ((p.io & 2) == 0 && (k.dma_direct || !vec_ok) ? 4 : 0), [&](auto io_) {
+            hipLaunchKernelGGL((conv2d_f16x3_dma2_kernel<MODE, 3, decltype(io_)::value>), grid, dim3(256), 0, s, p);
+        });
+    else if (k.dma_pipe)
+        f3_switch<5, 4>(k.dma_stages, [&](auto ns_) {
+            hipLaunchKernelGGL((conv2d_f16x3_dma2_kernel<MODE, decltype(ns_)::value, 4>), grid, dim3(256), 0, s, p);
+        });
+    else
+        f3_switch<4, 5, 3>(k.dma_stages, [&](auto ns_) {
+            hipLaunchKernelGGL((conv2d_f16x3_dma_kernel<MODE, decltype(ns_)::value>), grid, dim3(256), 0, s, p);
+        });
 }
 
 // gap_part may be null (no fused GAP); otherwise [B][gap_parts][ldc] with gap_parts >= al3d_gap_parts_count
@@ -2023,30 +1980,9 @@ extern "C" int al3d_conv2d_nhwc_f16x3_dma(const float* in, const void* wgt_image
                                           int Cout, int ksize, int stride, int pad, int ldc, int coff,
                                           int relu, float* gap_part, int gap_parts, int io, void* stream)
 {
-    ConvF3Params p;
-    p.gap = gap_part; p.gap_parts = gap_parts; p.io = io;
-    AL3D_REQUIRE(io >= 0 && io < 4 && (!(io & 2) || (Cout % 8 == 0 && ldc % 8 == 0 && coff % 8 == 0)),
-                 "al3d_conv2d_nhwc_f16x3_dma: bad io flags (pair output needs Cout, ldc, coff multiples of 8)");
-    AL3D_REQUIRE(io == 0 || (dma_pipe() && dma_stages() == 3), "al3d_conv2d_nhwc_f16x3_dma: pair pixels need the shipped kernel shape (AL3D_DMA_PIPE=1, 3 stages)");
-    p.in = in; p.wgt = (const _Float16*)wgt_image; p.scale = scale; p.shift = shift; p.out = out;
-    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
-    p.ksize = ksize; p.stride = stride; p.pad = pad; p.ldc = ldc; p.coff = coff; p.relu = relu;
-    AL3D_REQUIRE(ksize >= 1 && ksize <= 7 && stride >= 1 && pad >= 0, "al3d_conv2d_nhwc_f16x3_dma: bad geometry");
-    p.OH = (H + 2 * pad - ksize) / stride + 1;
-    p.OW = (W + 2 * pad - ksize) / stride + 1;
-    AL3D_REQUIRE(p.OH >= 1 && p.OW >= 1, "al3d_conv2d_nhwc_f16x3_dma: empty output");
-    p.plane = 0;
-    int rc = convf3_check(p, "al3d_conv2d_nhwc_f16x3_dma");
-    if (rc) return rc;
-    AL3D_REQUIRE((int64_t)B * H * W * Cin < ((int64_t)1 << 31), "al3d_conv2d_nhwc_f16x3_dma: input above 2^31 elements");
-    AL3D_REQUIRE(!gap_part || gap_parts >= al3d_gap_parts_count(p.OH, p.OW, 0),
-                 "al3d_conv2d_nhwc_f16x3_dma: gap_parts must be at least al3d_gap_parts_count(OH, OW, 0)");
-    p.tiles_x = (int)al3d_cdiv(p.OW, F3_TW);
-    p.tiles_y = (int)al3d_cdiv(p.OH, F3_TH);
-    p.ntiles = p.tiles_x * p.tiles_y * B; p.nblocks = (int)al3d_cdiv(Cout, F3_BN);
-    launch_dma<0>(p, dim3(f3_grid(p)), (hipStream_t)stream);
-    AL3D_CHECK_LAUNCH("conv2d_f16x3_dma_kernel<conv>");
-    return AL3D_OK;
+    return convf3_launch("al3d_conv2d_nhwc_f16x3_dma", "conv2d_f16x3_dma_kernel<conv>", F3_FAM_DMA, in, wgt_image, scale, shift,
+                         out, B, H, W, Cin, Cout, ksize, stride, pad, false, ldc, coff, relu, gap_part, gap_parts, io,
+                         [&](const ConvF3Params& p, dim3 grid) { launch_dma<0>(p, grid, (hipStream_t)stream); });
 }
 
 extern "C" int al3d_deconv2x2_nhwc_f16x3_dma(const float* in, const void* wgt_image, const float* scale,
@@ -2054,25 +1990,7 @@ extern "C" int al3d_deconv2x2_nhwc_f16x3_dma(const float* in, const void* wgt_im
                                              int Cout, int ldc, int coff, int relu, float* gap_part, int gap_parts,
                                              int io, void* stream)
 {
-    ConvF3Params p;
-    p.gap = gap_part; p.gap_parts = gap_parts; p.io = io;
-    AL3D_REQUIRE(io >= 0 && io < 4 && (!(io & 2) || (Cout % 8 == 0 && ldc % 8 == 0 && coff % 8 == 0)),
-                 "al3d_deconv2x2_nhwc_f16x3_dma: bad io flags (pair output needs Cout, ldc, coff multiples of 8)");
-    AL3D_REQUIRE(io == 0 || (dma_pipe() && dma_stages() == 3), "al3d_deconv2x2_nhwc_f16x3_dma: pair pixels need the shipped kernel shape (AL3D_DMA_PIPE=1, 3 stages)");
-    p.in = in; p.wgt = (const _Float16*)wgt_image; p.scale = scale; p.shift = shift; p.out = out;
-    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
-    p.ksize = 2; p.stride = 2; p.pad = 0; p.ldc = ldc; p.coff = coff; p.relu = relu;
-    p.OH = 2 * H; p.OW = 2 * W;
-    p.plane = 0;
-    int rc = convf3_check(p, "al3d_deconv2x2_nhwc_f16x3_dma");
-    if (rc) return rc;
-    AL3D_REQUIRE((int64_t)B * H * W * Cin < ((int64_t)1 << 31), "al3d_deconv2x2_nhwc_f16x3_dma: input above 2^31 elements");
-    AL3D_REQUIRE(!gap_part || gap_parts >= al3d_gap_parts_count(p.OH, p.OW, 1),
-                 "al3d_deconv2x2_nhwc_f16x3_dma: gap_parts must be at least al3d_gap_parts_count(OH, OW, 1)");
-    p.tiles_x = (int)al3d_cdiv(W, F3_TW);
-    p.tiles_y = (int)al3d_cdiv(H, F3_TH);
-    p.ntiles = p.tiles_x * p.tiles_y * B; p.nblocks = (int)al3d_cdiv(Cout, F3_BN);
-    launch_dma<1>(p, dim3(f3_grid(p), 1, 4), (hipStream_t)stream);
-    AL3D_CHECK_LAUNCH("conv2d_f16x3_dma_kernel<deconv>");
-    return AL3D_OK;
+    return convf3_launch("al3d_deconv2x2_nhwc_f16x3_dma", "conv2d_f16x3_dma_kernel<deconv>", F3_FAM_DMA, in, wgt_image, scale,
+                         shift, out, B, H, W, Cin, Cout, 2, 2, 0, true, ldc, coff, relu, gap_part, gap_parts, io,
+                         [&](const ConvF3Params& p, dim3 grid) { launch_dma<1>(p, grid, (hipStream_t)stream); });
 }

@@ -4,6 +4,8 @@ Activations are NHWC float32.  Weight packing helpers turn reference-layout
 parameters (``Conv2d.weight [Cout,Cin,k,k]``, ``ConvTranspose2d.weight [Cin,Cout,2,2]``,
 eval ``BatchNorm2d``) into the kernel layouts once, outside the hot loop.
 """
+from typing import NamedTuple
+
 import torch
 
 from . import lib
@@ -179,32 +181,6 @@ def pack_glds_f16x3(planes):
 
 def frag_ok(cout, cin, ksize, stride, pad):
     return ksize == 3 and stride == 1 and pad == 1 and cout % 128 == 0 and cin % 32 == 0
-
-
-def pack_dense(w_packed, scale=None, ksize=None, stride=None, pad=None):
-    """Packed f32 weights + folded-BN scale -> (weights in the dense kernels' format for MATH,
-    the scale to hand them).  With the layer geometry given (``ksize="deconv"`` for the 2x2
-    transposed conv), f16x3 weights are put in fragment order for the streamed-weight kernels."""
-    if MATH == "f16x3":
-        if DENSE == "wino" and ksize not in (None, "deconv") and wino_ok(w_packed.shape[0], w_packed.shape[2], ksize, stride, pad):
-            return pack_wino_f16x3(w_packed, scale)
-        planes, scale = split_f16x3(w_packed, scale)
-        if ksize is not None and DENSE != "lds":
-            if ksize != "deconv" and frag_ok(planes.shape[1], planes.shape[3], ksize, stride, pad):
-                if DENSE == "frag16" and planes.shape[3] % 64 == 0:
-                    return pack_frag16_f16x3(planes), scale
-                return pack_frag_f16x3(planes), scale
-            # streamed weights pay off once a launch has enough steps to amortise the deeper prologue:
-            # stride-2 3x3 (72 steps) -12 %, fused head (32) -5 %, 1x1 deblock (8) +8 % -> LDS-staged
-            if DENSE in ("auto", "dma", "wino"):
-                return pack_dma_f16x3(planes), scale
-            steps = planes.shape[2] * planes.shape[3] // 16
-            if DENSE == "bstream" or (DENSE == "stream" and ksize != "deconv" and steps >= 24):
-                return pack_bstream_f16x3(planes), scale
-        return planes, scale
-    if MATH == "bf16x6":
-        return split_bf16x3(w_packed), scale
-    return w_packed, scale
 
 
 # sparse-conv structure.  f16x3: "auto" = per channel pair whichever kernel measured fastest on the real rulebooks
@@ -528,132 +504,135 @@ def sparse_launch(name, feats, tab, w, cin, cout, scale, shift, residual, relu, 
              1 if relu else 0, _ptr(out), tab["n"], *tail, _stream())
 
 
-# ------------------------------------------------------------------ kernels
-_DENSE_KIND = {torch.float32: "f32", torch.bfloat16: "bf16x6", torch.float16: "f16x3"}
+# ------------------------------------------------------------------ dense-conv dispatch (neck, heads, camera-branch convs)
+def _f16x3_packer(pack=None):
+    """(f32 packed weights, scale) -> (the f16x3 planes, or pack(planes), the scale to hand the kernel)."""
+    def packer(w_packed, scale):
+        planes, scale = split_f16x3(w_packed, scale)
+        return (planes if pack is None else pack(planes)), scale
+    return packer
+
+
+class DenseKind(NamedTuple):
+    conv: str        # al3d_* entry point of the convolution
+    deconv: str      # ... of the 2x2 / stride-2 transposed convolution, None: the structure has none
+    generic: bool    # the launch takes (ksize, stride, pad); False: 3x3 / stride 1 / pad 1 only
+    io: int          # the IO_* bits (pair pixels) the entry points accept; nonzero: they take an io argument
+    gap: object      # fused GAP: None, "entry" (the entry points named ..._gap) or "arg" (a gap argument, may be null)
+    pack: object     # (f32 packed weights [Cout,taps,Cin], scale) -> (weights, scale) for the entry points
+
+
+# structure -> what its launch takes.  "f32" / "bf16x6" / "f16x3" weights are plain tensors (f32 [Cout,taps,Cin], bf16
+# [3,...] planes, f16 [2,...] planes: the LDS-staged kernels), the others F16x3Packed of that kind
+DENSE_KINDS = {
+    "f32": DenseKind("al3d_conv2d_nhwc_f32", "al3d_deconv2x2_nhwc_f32", True, 0, None, lambda w, scale: (w, scale)),
+    "bf16x6": DenseKind("al3d_conv2d_nhwc_bf16x6", "al3d_deconv2x2_nhwc_bf16x6", True, 0, None,
+                        lambda w, scale: (split_bf16x3(w), scale)),
+    "f16x3": DenseKind("al3d_conv2d_nhwc_f16x3", "al3d_deconv2x2_nhwc_f16x3", True, 0, "entry", _f16x3_packer()),
+    "frag3x3": DenseKind("al3d_conv3x3_nhwc_f16x3_frag_io", None, False, IO_OUT_PAIR, None, _f16x3_packer(pack_frag_f16x3)),
+    "frag16": DenseKind("al3d_conv3x3_nhwc_f16x3_frag16", None, False, 0, None, _f16x3_packer(pack_frag16_f16x3)),
+    "wino": DenseKind("al3d_conv3x3_nhwc_f16x3_wino", None, False, IO_OUT_PAIR, None, pack_wino_f16x3),
+    "bstream": DenseKind("al3d_conv2d_nhwc_f16x3_bstream", "al3d_deconv2x2_nhwc_f16x3_bstream", True, 0, None,
+                         _f16x3_packer(pack_bstream_f16x3)),
+    "dma": DenseKind("al3d_conv2d_nhwc_f16x3_dma", "al3d_deconv2x2_nhwc_f16x3_dma", True, IO_IN_PAIR | IO_OUT_PAIR, "arg",
+                     _f16x3_packer(pack_dma_f16x3)),
+}
+
+
+def dense_structure(cout, cin, ksize=None, stride=None, pad=None):
+    """Kind (DENSE_KINDS) of the dense layer cin -> cout under MATH / DENSE.  ksize="deconv": the 2x2 transposed conv;
+    ksize=None (no geometry given): the plain weight format of MATH."""
+    if MATH != "f16x3":
+        return MATH
+    if ksize is None or DENSE == "lds":
+        return "f16x3"
+    conv = ksize != "deconv"
+    if DENSE == "wino" and conv and wino_ok(cout, cin, ksize, stride, pad):
+        return "wino"
+    if conv and frag_ok(cout, cin, ksize, stride, pad):
+        return "frag16" if DENSE == "frag16" and cin % 64 == 0 else "frag3x3"
+    if DENSE in ("auto", "dma", "wino"):
+        return "dma"
+    # streamed weights pay off once a launch has enough steps to amortise the deeper prologue:
+    # stride-2 3x3 (72 steps) -12 %, fused head (32) -5 %, 1x1 deblock (8) +8 % -> LDS-staged
+    if DENSE == "bstream" or (DENSE == "stream" and conv and ksize * ksize * cin // 16 >= 24):
+        return "bstream"
+    return "f16x3"                                # "frag" / "frag16" (and any other value): only the 3x3 layers stream
+
+
+def dense_pack(kind, w_packed, scale=None):
+    """Packed f32 weights [Cout,taps,Cin] + folded-BN scale -> (weights in structure `kind`'s format, the scale to hand it:
+    the f16x3 split folds its weight exponent into it)."""
+    return DENSE_KINDS[kind].pack(w_packed, scale)
+
+
+def pack_dense(w_packed, scale=None, ksize=None, stride=None, pad=None):
+    """dense_pack for the structure the layer takes under MATH / DENSE (``ksize="deconv"`` for the 2x2 transposed conv;
+    no geometry: the plain format of MATH)."""
+    return dense_pack(dense_structure(w_packed.shape[0], w_packed.shape[2], ksize, stride, pad), w_packed, scale)
+
+
+_PLAIN_KIND = {torch.float32: "f32", torch.bfloat16: "bf16x6", torch.float16: "f16x3"}
+
+
+def dense_kind(w_packed):
+    """Kind of a weight object: F16x3Packed, or a plain tensor of one of the three dtypes."""
+    return w_packed.kind if isinstance(w_packed, F16x3Packed) else _PLAIN_KIND[w_packed.dtype]
 
 
 def gap_fusable(w_packed):
     """The fused-GAP epilogue exists in the generic f16x3 kernels (plain f16 planes or LDS-DMA images: the deblock
     launches)."""
+    return DENSE_KINDS[dense_kind(w_packed)].gap is not None
+
+
+def dense_launch(who, x, w_packed, scale, shift, geom, relu, out=None, coff=0, gap=None, io=0):
+    """The one launch of every structure: out[..., coff:coff+Cout] = conv (geom = (ksize, stride, pad)) or 2x2 transposed
+    conv (geom None) of x [B,H,W,Cin], * scale + shift (ReLU).  w_packed, scale: dense_pack's.  out: optional
+    [B,OH,OW,ldc] map.  gap: optional [B, parts, ldc] f32 buffer (parts = gap_parts): the launch also writes its
+    workgroups' channel sums there (see gap_fusable).  io: IO_* flags (pair pixels)."""
+    x = _dev(x, torch.float32, "x")
+    kind = dense_kind(w_packed)
+    row = DENSE_KINDS[kind]
     if isinstance(w_packed, F16x3Packed):
-        return w_packed.kind == "dma"
-    return isinstance(w_packed, torch.Tensor) and w_packed.dtype == torch.float16
+        data, cout, taps, cin = w_packed.data, w_packed.cout, w_packed.taps, w_packed.cin
+    else:
+        data = _dev(w_packed, w_packed.dtype, "w")
+        cout, taps, cin = data.shape[-3:]
+    if data.dtype == torch.float16 and scale is None:
+        raise lib.Al3dError(f"{who}: f16x3 weights need the scale returned by split_f16x3")
+    B, H, W, Cin = x.shape
+    fn = row.conv if geom is not None else row.deconv
+    ksize, stride, pad = geom if geom is not None else (2, 2, 0)
+    if fn is None or cin != Cin or taps != ksize * ksize or not (row.generic or geom == (3, 1, 1)):
+        raise lib.Al3dError(f"{who}: {kind!r} weights [Cout={cout}, taps={taps}, Cin={cin}] do not match this layer's geometry")
+    if io & ~row.io:
+        raise lib.Al3dError(f"{who}: io={io}: the {kind!r} kernel " + (
+            "takes the in / out pair-pixel bits only" if row.io & IO_IN_PAIR else
+            "reads f32 pixels and writes " + ("f32 or pair pixels" if row.io else "f32 pixels")))
+    if gap is not None and row.gap is None:
+        raise lib.Al3dError(f"{who}: {kind!r} weights have no fused GAP (see gap_fusable)")
+    OH, OW = (2 * H, 2 * W) if geom is None else ((H + 2 * pad - ksize) // stride + 1, (W + 2 * pad - ksize) // stride + 1)
+    if out is None:
+        out = torch.empty((B, OH, OW, cout), dtype=torch.float32, device=x.device)
+    assert out.shape[:3] == (B, OH, OW) and out.is_contiguous()
+    tail = ()
+    if row.gap == "arg" or gap is not None:
+        tail += (_ptr(gap), 0 if gap is None else gap.shape[1])
+    if row.io:
+        tail += (io,)
+    lib.call(fn + ("_gap" if gap is not None and row.gap == "entry" else ""), _ptr(x), _ptr(data), _ptr(scale), _ptr(shift),
+             _ptr(out), B, H, W, Cin, cout, *(geom if row.generic and geom is not None else ()), out.shape[3], coff,
+             1 if relu else 0, *tail, _stream())
+    return out
 
 
 def conv2d_nhwc(x, w_packed, scale, shift, ksize, stride, pad, relu, out=None, coff=0, gap=None, io=0):
-    """gap: optional [B, parts, ldc] f32 buffer (parts = al3d_gap_parts_count): the launch also writes its
-    workgroups' channel sums there (f16x3 planes only, see gap_fusable)."""
-    x = _dev(x, torch.float32, "x")
-    # the weight format selects the arithmetic: bf16 [3,Cout,taps,Cin] (split_bf16x3),
-    # f16 [2,Cout,taps,Cin] (split_f16x3, scale required) or plain f32 [Cout,taps,Cin]
-    kind = _DENSE_KIND[w_packed.dtype]
-    if kind == "f16x3" and scale is None:
-        raise lib.Al3dError("conv2d_nhwc: f16x3 weights need the scale returned by split_f16x3")
-    if isinstance(w_packed, F16x3Packed):             # fragment-ordered f16x3
-        pk = w_packed
-        B, H, W, Cin = x.shape
-        if pk.cin != Cin or pk.taps != ksize * ksize or (pk.kind in ("frag3x3", "frag16", "wino") and (stride, pad) != (1, 1)):
-            raise lib.Al3dError("conv2d_nhwc: fragment-ordered weights do not match this layer's geometry")
-        OH = (H + 2 * pad - ksize) // stride + 1
-        OW = (W + 2 * pad - ksize) // stride + 1
-        if out is None:
-            out = torch.empty((B, OH, OW, pk.cout), dtype=torch.float32, device=x.device)
-        assert out.shape[:3] == (B, OH, OW) and out.is_contiguous()
-        if pk.kind == "frag3x3":
-            if io not in (0, IO_OUT_PAIR):
-                raise lib.Al3dError("conv2d_nhwc: the streamed 3x3 kernel reads f32 pixels (it may write pair pixels)")
-            if gap is not None:
-                raise lib.Al3dError("conv2d_nhwc: this weight format has no fused GAP (see gap_fusable)")
-            lib.call("al3d_conv3x3_nhwc_f16x3_frag_io", _ptr(x), _ptr(pk.data), _ptr(scale), _ptr(shift), _ptr(out),
-                     B, H, W, Cin, pk.cout, out.shape[3], coff, 1 if relu else 0, io, _stream())
-            return out
-        if pk.kind == "wino":
-            if io not in (0, IO_OUT_PAIR):
-                raise lib.Al3dError("conv2d_nhwc: the Winograd 3x3 kernel reads f32 pixels (it may write pair pixels)")
-            if gap is not None:
-                raise lib.Al3dError("conv2d_nhwc: this weight format has no fused GAP (see gap_fusable)")
-            lib.call("al3d_conv3x3_nhwc_f16x3_wino", _ptr(x), _ptr(pk.data), _ptr(scale), _ptr(shift), _ptr(out),
-                     B, H, W, Cin, pk.cout, out.shape[3], coff, 1 if relu else 0, io, _stream())
-            return out
-        if pk.kind == "dma":
-            lib.call("al3d_conv2d_nhwc_f16x3_dma", _ptr(x), _ptr(pk.data), _ptr(scale), _ptr(shift), _ptr(out),
-                     B, H, W, Cin, pk.cout, ksize, stride, pad, out.shape[3], coff, 1 if relu else 0,
-                     _ptr(gap), 0 if gap is None else gap.shape[1], io, _stream())
-            return out
-        if io:
-            raise lib.Al3dError("conv2d_nhwc: pair pixels exist for the streamed 3x3 (output) and LDS-DMA kernels only")
-        if gap is not None:
-            raise lib.Al3dError("conv2d_nhwc: this weight format has no fused GAP (see gap_fusable)")
-        if pk.kind == "frag16":
-            lib.call("al3d_conv3x3_nhwc_f16x3_frag16", _ptr(x), _ptr(pk.data), _ptr(scale), _ptr(shift), _ptr(out),
-                     B, H, W, Cin, pk.cout, out.shape[3], coff, 1 if relu else 0, _stream())
-        else:
-            lib.call("al3d_conv2d_nhwc_f16x3_bstream", _ptr(x), _ptr(pk.data), _ptr(scale), _ptr(shift),
-                     _ptr(out), B, H, W, Cin, pk.cout, ksize, stride, pad, out.shape[3], coff,
-                     1 if relu else 0, _stream())
-        return out
-    w_packed = _dev(w_packed, w_packed.dtype, "w")
-    wshape = w_packed.shape[1:] if kind != "f32" else w_packed.shape
-    B, H, W, Cin = x.shape
-    Cout = wshape[0]
-    assert wshape[1] == ksize * ksize and wshape[2] == Cin
-    OH = (H + 2 * pad - ksize) // stride + 1
-    OW = (W + 2 * pad - ksize) // stride + 1
-    if out is None:
-        out = torch.empty((B, OH, OW, Cout), dtype=torch.float32, device=x.device)
-    assert out.shape[:3] == (B, OH, OW) and out.is_contiguous()
-    if io:
-        raise lib.Al3dError("conv2d_nhwc: pair pixels need fragment-ordered / LDS-DMA weights (pack_dense)")
-    if gap is not None:
-        if not gap_fusable(w_packed):
-            raise lib.Al3dError("conv2d_nhwc: the fused GAP needs plain f16x3 planes")
-        lib.call("al3d_conv2d_nhwc_f16x3_gap", _ptr(x), _ptr(w_packed), _ptr(scale), _ptr(shift), _ptr(out),
-                 B, H, W, Cin, Cout, ksize, stride, pad, out.shape[3], coff, 1 if relu else 0, _ptr(gap), gap.shape[1],
-                 _stream())
-        return out
-    lib.call("al3d_conv2d_nhwc_" + kind, _ptr(x), _ptr(w_packed), _ptr(scale), _ptr(shift), _ptr(out),
-             B, H, W, Cin, Cout, ksize, stride, pad, out.shape[3], coff, 1 if relu else 0, _stream())
-    return out
+    return dense_launch("conv2d_nhwc", x, w_packed, scale, shift, (ksize, stride, pad), relu, out, coff, gap, io)
 
 
 def deconv2x2_nhwc(x, w_packed, scale, shift, relu, out=None, coff=0, gap=None, io=0):
-    x = _dev(x, torch.float32, "x")
-    B, H, W, Cin = x.shape
-    kind = _DENSE_KIND[w_packed.dtype]
-    if kind == "f16x3" and scale is None:
-        raise lib.Al3dError("deconv2x2_nhwc: f16x3 weights need the scale returned by split_f16x3")
-    if isinstance(w_packed, F16x3Packed):
-        pk = w_packed
-        if pk.kind not in ("bstream", "dma") or pk.taps != 4 or pk.cin != Cin:
-            raise lib.Al3dError("deconv2x2_nhwc: fragment-ordered weights do not match this layer")
-        if out is None:
-            out = torch.empty((B, 2 * H, 2 * W, pk.cout), dtype=torch.float32, device=x.device)
-        assert out.shape[:3] == (B, 2 * H, 2 * W) and out.is_contiguous()
-        if pk.kind == "dma":
-            lib.call("al3d_deconv2x2_nhwc_f16x3_dma", _ptr(x), _ptr(pk.data), _ptr(scale), _ptr(shift), _ptr(out),
-                     B, H, W, Cin, pk.cout, out.shape[3], coff, 1 if relu else 0,
-                     _ptr(gap), 0 if gap is None else gap.shape[1], io, _stream())
-            return out
-        if io:
-            raise lib.Al3dError("deconv2x2_nhwc: pair pixels exist for the LDS-DMA kernel only")
-        if gap is not None:
-            raise lib.Al3dError("deconv2x2_nhwc: this weight format has no fused GAP (see gap_fusable)")
-        lib.call("al3d_deconv2x2_nhwc_f16x3_bstream", _ptr(x), _ptr(pk.data), _ptr(scale), _ptr(shift),
-                 _ptr(out), B, H, W, Cin, pk.cout, out.shape[3], coff, 1 if relu else 0, _stream())
-        return out
-    Cout = w_packed.shape[1] if kind != "f32" else w_packed.shape[0]
-    if out is None:
-        out = torch.empty((B, 2 * H, 2 * W, Cout), dtype=torch.float32, device=x.device)
-    assert out.shape[:3] == (B, 2 * H, 2 * W) and out.is_contiguous()
-    if gap is not None:
-        if not gap_fusable(w_packed):
-            raise lib.Al3dError("deconv2x2_nhwc: the fused GAP needs plain f16x3 planes")
-        lib.call("al3d_deconv2x2_nhwc_f16x3_gap", _ptr(x), _ptr(w_packed), _ptr(scale), _ptr(shift), _ptr(out),
-                 B, H, W, Cin, Cout, out.shape[3], coff, 1 if relu else 0, _ptr(gap), gap.shape[1], _stream())
-        return out
-    lib.call("al3d_deconv2x2_nhwc_" + kind, _ptr(x), _ptr(w_packed), _ptr(scale), _ptr(shift), _ptr(out),
-             B, H, W, Cin, Cout, out.shape[3], coff, 1 if relu else 0, _stream())
-    return out
+    return dense_launch("deconv2x2_nhwc", x, w_packed, scale, shift, None, relu, out, coff, gap, io)
 
 
 def gap_parts(OH, OW, deconv):
