@@ -26,7 +26,9 @@ __device__ float quad_intersection_area(const float* ax, const float* ay, const 
     int n = 4;
 #pragma unroll
     for (int k = 0; k < 4; ++k) { px[k] = ax[k]; py[k] = ay[k]; }
-    // orientation of the clip polygon
+    // orientation of the clip polygon: only the SIGN of this shoelace is used, so it stays on absolute coordinates -- twice
+    // the area of the smallest real footprint is 0.32 m^2 against ~1e-3 m^2 of rounding at 54 m; a box too small for that
+    // has no area worth clipping
     float barea = 0.f;
 #pragma unroll
     for (int k = 0; k < 4; ++k) { const int k2 = (k + 1) & 3; barea += bx[k] * by[k2] - bx[k2] * by[k]; }
@@ -51,15 +53,19 @@ __device__ float quad_intersection_area(const float* ax, const float* ay, const 
         for (int k = 0; k < n; ++k) { px[k] = qx[k]; py[k] = qy[k]; }
     }
     if (n < 3) return 0.f;
+    // shoelace about the first vertex: see quad_area
     float area = 0.f;
-    for (int k = 0; k < n; ++k) { const int k2 = k + 1 == n ? 0 : k + 1; area += px[k] * py[k2] - px[k2] * py[k]; }
+    for (int k = 1; k + 1 < n; ++k) area += (px[k] - px[0]) * (py[k + 1] - py[0]) - (px[k + 1] - px[0]) * (py[k] - py[0]);
     return 0.5f * fabsf(area);
 }
 
+// Shoelace about the quadrilateral's first vertex, not about the frame's origin: the products are then of the size of the
+// box, not of its distance from the origin.  54 m out a product of absolute coordinates is ~2900 with an ulp of 2.4e-4 m^2,
+// 0.15 % of a traffic cone's footprint: measured IoU error 3e-3 there against 1e-5 in this form (tests/anchorhead_cases.py).
 __device__ __forceinline__ float quad_area(const float* x, const float* y)
 {
     float a = 0.f;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { const int k2 = (k + 1) & 3; a += x[k] * y[k2] - x[k2] * y[k]; }
+    for (int k = 1; k < 3; ++k) a += (x[k] - x[0]) * (y[k + 1] - y[0]) - (x[k + 1] - x[0]) * (y[k] - y[0]);
     return 0.5f * fabsf(a);
 }

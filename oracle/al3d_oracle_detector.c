@@ -196,10 +196,13 @@ static void corners_of(const float* d, float* cx, float* cy)
     }
 }
 
+/* Shoelace about the polygon's first vertex, not about the frame's origin: the products are then of the size of the polygon,
+ * not of its distance from the origin (54 m away a product of absolute coordinates is ~2900 with an ulp of 2.4e-4 m^2, which
+ * is 0.15 % of a traffic cone's footprint). */
 static float poly_area(const float* x, const float* y, int n)
 {
     float a = 0.f;
-    for (int k = 0; k < n; ++k) { int k2 = k + 1 == n ? 0 : k + 1; a += x[k] * y[k2] - x[k2] * y[k]; }
+    for (int k = 1; k + 1 < n; ++k) a += (x[k] - x[0]) * (y[k + 1] - y[0]) - (x[k + 1] - x[0]) * (y[k] - y[0]);
     return 0.5f * fabsf(a);
 }
 
@@ -208,6 +211,7 @@ static float clip_area(const float* ax, const float* ay, const float* bx, const 
     float px[16], py[16], qx[16], qy[16];
     int n = 4;
     for (int k = 0; k < 4; ++k) { px[k] = ax[k]; py[k] = ay[k]; }
+    /* orientation only: the sign of this absolute-coordinate shoelace is all that is used (see poly_area for the areas) */
     float barea = 0.f;
     for (int k = 0; k < 4; ++k) { int k2 = (k + 1) & 3; barea += bx[k] * by[k2] - bx[k2] * by[k]; }
     const float sgn = barea >= 0.f ? 1.f : -1.f;

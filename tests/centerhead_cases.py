@@ -5,8 +5,9 @@ quantity sits on a threshold, so the inputs stay off every threshold BY CONSTRUC
   * scores are planted: background logits below logit(0.05); object cells get scores from a shuffled arithmetic grid in
     (0.1 + 1e-3, 0.99) with spacing >= 1e-5, logits = float32 of the float64 logit (float32 sigmoid error: ~1e-7);
   * geometry is repaired: while the float64 run has a centre within 1e-4 of a range bound, a squared distance within
-    1e-4 of a circle radius or a pair IoU within 1e-5 of nms_thr (float32 IoU error: ~1e-6), the later box of the pair
-    is redrawn.  ``build`` returns the share of redrawn boxes; the tests assert it stays below 1 %.
+    1e-4 of a circle radius or a pair IoU within IOU_BAND = 1e-4 of nms_thr, the later box of the pair is redrawn.  The band is
+    the one MEASURED for the shared geometry (csrc/al3d_rbox.h) in tests/anchorhead_cases.py: float32 IoU error up to 2.5e-5
+    for centres out to +-50 m, as here, times 4.  ``build`` returns the share of redrawn boxes; the tests assert it stays below 1 %.
 """
 import numpy as np
 
@@ -14,6 +15,7 @@ import center_fp64 as C
 
 NUSC_TASKS = [1, 2, 2, 1, 2, 2]
 F32 = lambda v: float(np.float32(v))      # noqa: E731  constants as the kernel holds them
+IOU_BAND = 1e-4                           # 4 x the measured float32 IoU error at range (tests/anchorhead_cases.py)
 
 
 def layout(task_ncls, vel=True, reg=True, novel_tasks=(), noreg_tasks=()):
@@ -118,7 +120,7 @@ def _near_threshold(ref, pairs, p, task_ncls):
             if kinds[t] == "rotate":
                 surv = surv[dec["scores"] >= p["score_threshold"]][:p["pre_max_size"]] if p["score_threshold"] > 0 else surv
                 for i, j, iou in pairs.get((b, t), ()):
-                    if abs(iou - p["nms_thr"]) < 1e-5:
+                    if abs(iou - p["nms_thr"]) < IOU_BAND:
                         bad.add((b, t, int(surv[j])))
             else:
                 for i, j, d2 in pairs.get((b, t), ()):
