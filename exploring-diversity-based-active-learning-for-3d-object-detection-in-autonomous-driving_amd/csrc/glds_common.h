@@ -1,7 +1,10 @@
-// Shared pieces of the LDS-DMA sparse-convolution kernels (spconv_glds.hip, spconv_rng.hip): native vector types
-// for inline-asm operands, the f16x3 split, raw LDS reads fused with their waits, counted vmcnt waits.
+// The single header of the f16x3 sparse-convolution kernels (spconv_wave.hip, spconv_glds.hip, spconv_rng.hip,
+// spconv_blk.hip, spconv_l0.hip).  Device side: native vector types for inline-asm operands, the f16x3 split and lift, the
+// pipelined unit (the three products of a unit in their one summation order), raw LDS reads fused with their waits,
+// counted vmcnt waits, LDS-DMA piece loops, the XCD placement.  Host side: the argument checks and the launch of every entry point.
 #pragma once
 #include "al3d_common.h"
+#include "sp_rows.h"
 #include <stdlib.h>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -28,26 +31,38 @@ template <int N, int I = 0, class F> __device__ __forceinline__ void gl_static_f
     }
 }
 
-// ---- the f16x3 pieces, the same operations as spconv_wave.hip (bit-identical results)
+// ---- XCD-aware placement: workgroups with equal blockIdx.x % 8 share an L2, so each of the eight groups gets one
+// contiguous range of slots (rows are in raster order: the neighbours of a tile live in nearby tiles) instead of every
+// eighth one.  Bijective for any grid size.  A kernel multiplies the slot by the tiles (rows, chunks) of its workgroup.
+__device__ __forceinline__ int gl_xcd_slot()
+{
+    const int nwg = gridDim.x, xcd = blockIdx.x & 7, q8 = nwg >> 3, r8 = nwg & 7;
+    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
+}
+
+// ---- the f16x3 arithmetic (see conv2d_f16x3.hip): x = xh + xl' * 2^-11 with xh = f16(x), xl' = f16((x - xh) * 2^11)
+// (sp_split8, sp_rows.h); x * w = xl' * (wh * 2^-11) + xh * wl + xh * wh, three f16 MFMAs into one fp32 accumulator.
 __device__ __forceinline__ void gl_split8_f16(const gl_f32x4& lo, const gl_f32x4& hi, f16x8& ph, f16x8& pl)
 {
     const float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    unsigned h[4], l[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const gl_f32x2 x = {v[2 * e], v[2 * e + 1]};
-        const gl_f16x2 xh = __builtin_convertvector(x, gl_f16x2);
-        const gl_f32x2 r = {__builtin_fmaf((float)xh[0], -2048.0f, x[0] * 2048.0f),
-                            __builtin_fmaf((float)xh[1], -2048.0f, x[1] * 2048.0f)};
-        h[e] = __builtin_bit_cast(unsigned, xh);
-        l[e] = __builtin_bit_cast(unsigned, __builtin_convertvector(r, gl_f16x2));
-    }
-    ph = __builtin_bit_cast(f16x8, make_uint4(h[0], h[1], h[2], h[3]));
-    pl = __builtin_bit_cast(f16x8, make_uint4(l[0], l[1], l[2], l[3]));
+    uint4 h, l;
+    sp_split8(v, h, l);
+    ph = __builtin_bit_cast(f16x8, h);
+    pl = __builtin_bit_cast(f16x8, l);
 }
 __device__ __forceinline__ f16x8 gl_lift_down(const f16x8& wh)        // wh * 2^-11 (packed multiplies)
 {
     return wh * (_Float16)0.00048828125f;
+}
+// The three products of a unit are issued SMALLEST FIRST -- al * wd (wd = gl_lift_down(wh)), ah * wl, ah * wh -- into
+// one fp32 accumulator, units in tap, channel-unit order: every structure keeps this order (gl_read_next_mfma below and
+// the kernels' own MFMA triples), which is why they all give the same bits.
+__device__ __forceinline__ f32x16 gl_zero()                           // a zeroed accumulator tile
+{
+    f32x16 z;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) z[e] = 0.f;
+    return z;
 }
 
 // ---- raw instructions the compiler must not reason about.  Every LDS read of the main loop is ONE asm block
@@ -100,4 +115,82 @@ template <int N> __device__ __forceinline__ void gl_wait_vm()
 {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
+// N consecutive 1-KiB LDS-DMA pieces (64 lanes x 16 bytes): src is this lane's address in the first piece, dst uniform
+template <int N> __device__ __forceinline__ void gl_dma_pieces(const unsigned char* src, unsigned dst)
+{
+    gl_static_for<N>([&](auto PC) {
+        constexpr int pc = decltype(PC)::value;
+        __builtin_amdgcn_global_load_lds((gbl_void*)(src + pc * 1024), (lds_void*)(size_t)(dst + pc * 1024), 16, 0, 0);
+    });
+}
 
+// One pipelined unit: the ds_reads of the NEXT unit's A / B fragments interleaved with the MFMAs of the current unit
+// (al * wd, ah * wl, ah * wh per tile; wd lifted by the caller), closed by the lgkmcnt wait -- one asm block, so no
+// register is visible to hipcc while it is in flight.  (`s_nop 1`: the operands come from VALU instructions right
+// before the block -- 2 wait states to an MFMA read.)
+template <int TN, int OFF, int PL>
+__device__ __forceinline__ void gl_read_next_mfma(gl_f32x4& nlo, gl_f32x4& nhi, f16x8 (&nwh)[TN], f16x8 (&nwl)[TN],
+                                                  f32x16 (&acc)[TN], const f16x8& al, const f16x8& ah,
+                                                  const f16x8 (&wd)[TN], const f16x8 (&wl)[TN], const f16x8 (&wh)[TN],
+                                                  unsigned a0, unsigned a1, unsigned b)
+{
+    static_assert(TN == 1 || TN == 2, "tile counts of the pipelined channel pairs");
+    if constexpr (TN == 1)
+        asm volatile("s_nop 1\n\t"
+                     "ds_read_b128 %0, %10\n\tds_read_b128 %1, %11\n\t"
+                     "v_mfma_f32_32x32x16_f16 %4, %5, %7, %4\n\t"
+                     "ds_read_b128 %2, %12 offset:%13\n\tds_read_b128 %3, %12 offset:%14\n\t"
+                     "v_mfma_f32_32x32x16_f16 %4, %6, %8, %4\n\t"
+                     "v_mfma_f32_32x32x16_f16 %4, %6, %9, %4\n\t"
+                     "s_waitcnt lgkmcnt(0)"
+                     : "=&v"(nlo), "=&v"(nhi), "=&v"(nwh[0]), "=&v"(nwl[0]), "+v"(acc[0])
+                     : "v"(al), "v"(ah), "v"(wd[0]), "v"(wl[0]), "v"(wh[0]), "v"(a0), "v"(a1), "v"(b), "n"(OFF), "n"(OFF + PL)
+                     : "memory");
+    else
+        asm volatile("s_nop 1\n\t"
+                     "ds_read_b128 %0, %16\n\tds_read_b128 %1, %17\n\t"
+                     "v_mfma_f32_32x32x16_f16 %6, %8, %10, %6\n\t"
+                     "v_mfma_f32_32x32x16_f16 %7, %8, %13, %7\n\t"
+                     "ds_read_b128 %2, %18 offset:%19\n\tds_read_b128 %3, %18 offset:%20\n\t"
+                     "v_mfma_f32_32x32x16_f16 %6, %9, %11, %6\n\t"
+                     "v_mfma_f32_32x32x16_f16 %7, %9, %14, %7\n\t"
+                     "ds_read_b128 %4, %18 offset:%21\n\tds_read_b128 %5, %18 offset:%22\n\t"
+                     "v_mfma_f32_32x32x16_f16 %6, %9, %12, %6\n\t"
+                     "v_mfma_f32_32x32x16_f16 %7, %9, %15, %7\n\t"
+                     "s_waitcnt lgkmcnt(0)"
+                     : "=&v"(nlo), "=&v"(nhi), "=&v"(nwh[0]), "=&v"(nwl[0]), "=&v"(nwh[1]), "=&v"(nwl[1]), "+v"(acc[0]), "+v"(acc[1])
+                     : "v"(al), "v"(ah), "v"(wd[0]), "v"(wl[0]), "v"(wh[0]), "v"(wd[1]), "v"(wl[1]), "v"(wh[1]),
+                       "v"(a0), "v"(a1), "v"(b), "n"(OFF), "n"(OFF + PL), "n"(OFF + 1024), "n"(OFF + PL + 1024)
+                     : "memory");
+}
+
+// ---------------------------------------------------------------------------------------------- host side
+// The argument checks of an f16x3 sparse entry point, in their one order; `name` is the name the messages carry (an
+// _io / _tiles_io entry point checks what is its own under its own name, then shares the plain entry point's checks).
+// sizes_ok / sizes_msg: what the structure asks of K (and Cin); ptrs: every pointer it reads is there; nbr_pitch: of a
+// tiled table, or -1 (the plain rulebook: no pitch rule).  *run = false with AL3D_OK: no rows, nothing to launch --
+// decided before the pointers are looked at.
+static int sp_conv_check(const char* name, bool sizes_ok, const char* sizes_msg, int io, int n_out, bool ptrs,
+                         const float* scale, int nbr_pitch, bool* run)
+{
+    *run = false;
+    AL3D_REQUIRE(sizes_ok && n_out >= 0, "%s: %s", name, sizes_msg);
+    AL3D_REQUIRE(io >= 0 && io < 8, "%s: bad io flags", name);
+    if (n_out == 0) return AL3D_OK;
+    AL3D_REQUIRE(ptrs, "%s: null pointer", name);
+    AL3D_REQUIRE(scale, "%s: scale carries the weight exponent and is required", name);
+    AL3D_REQUIRE(nbr_pitch == -1 || (nbr_pitch >= n_out && nbr_pitch % 256 == 0),
+                 "%s: nbr_pitch must be al3d_sp_table_pitch(n_out)", name);
+    *run = true;
+    return AL3D_OK;
+}
+
+// Launches kernel(args...) -- the arguments converted to the kernel's parameter types -- and reports a launch error under
+// `what`: a row of a file's dispatch table is `if (cin == .. && cout == ..) return sp_launch(..)`
+template <class... KA, class... A>
+static int sp_launch(const char* what, void (*kernel)(KA...), int64_t grid, int block, void* stream, A... args)
+{
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3((unsigned)block), 0, (hipStream_t)stream, (KA)args...);
+    AL3D_CHECK_LAUNCH(what);
+    return AL3D_OK;
+}

@@ -24,8 +24,6 @@
 // Reference semantics: bevfusion/mmdet3d/ops/spconv/include/spconv/spconv_ops.h:260-361 (indice conv),
 // geometry.h:248-298 (submanifold rulebook).
 #include "glds_common.h"
-#include "sp_rows.h"
-#include "../../include/al3d.h"
 
 #define BLK_NWIN 8
 #define BLK_WSPAN 512
@@ -181,44 +179,6 @@ __device__ __forceinline__ void blk_lds_read_u16(unsigned& d, unsigned addr)
     asm volatile("ds_read_u16 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(d) : "v"(addr) : "memory");
 }
 
-// One pipelined unit (as spconv_rng.hip): the ds_reads of the NEXT unit's A / B fragments interleaved with the MFMAs
-// of the current unit, closed by the lgkmcnt wait -- one asm block, so no register is visible to hipcc in flight.
-template <int TN, int OFF, int PL>
-__device__ __forceinline__ void blk_read_next_mfma(gl_f32x4& nlo, gl_f32x4& nhi, f16x8 (&nwh)[TN], f16x8 (&nwl)[TN],
-                                                   f32x16 (&acc)[TN], const f16x8& al, const f16x8& ah,
-                                                   const f16x8 (&wd)[TN], const f16x8 (&wl)[TN], const f16x8 (&wh)[TN],
-                                                   unsigned a0, unsigned a1, unsigned b)
-{
-    static_assert(TN == 1 || TN == 2, "tile counts of the pipelined channel pairs");
-    if constexpr (TN == 1)
-        asm volatile("s_nop 1\n\t"
-                     "ds_read_b128 %0, %10\n\tds_read_b128 %1, %11\n\t"
-                     "v_mfma_f32_32x32x16_f16 %4, %5, %7, %4\n\t"
-                     "ds_read_b128 %2, %12 offset:%13\n\tds_read_b128 %3, %12 offset:%14\n\t"
-                     "v_mfma_f32_32x32x16_f16 %4, %6, %8, %4\n\t"
-                     "v_mfma_f32_32x32x16_f16 %4, %6, %9, %4\n\t"
-                     "s_waitcnt lgkmcnt(0)"
-                     : "=&v"(nlo), "=&v"(nhi), "=&v"(nwh[0]), "=&v"(nwl[0]), "+v"(acc[0])
-                     : "v"(al), "v"(ah), "v"(wd[0]), "v"(wl[0]), "v"(wh[0]), "v"(a0), "v"(a1), "v"(b), "n"(OFF), "n"(OFF + PL)
-                     : "memory");
-    else
-        asm volatile("s_nop 1\n\t"
-                     "ds_read_b128 %0, %16\n\tds_read_b128 %1, %17\n\t"
-                     "v_mfma_f32_32x32x16_f16 %6, %8, %10, %6\n\t"
-                     "v_mfma_f32_32x32x16_f16 %7, %8, %13, %7\n\t"
-                     "ds_read_b128 %2, %18 offset:%19\n\tds_read_b128 %3, %18 offset:%20\n\t"
-                     "v_mfma_f32_32x32x16_f16 %6, %9, %11, %6\n\t"
-                     "v_mfma_f32_32x32x16_f16 %7, %9, %14, %7\n\t"
-                     "ds_read_b128 %4, %18 offset:%21\n\tds_read_b128 %5, %18 offset:%22\n\t"
-                     "v_mfma_f32_32x32x16_f16 %6, %9, %12, %6\n\t"
-                     "v_mfma_f32_32x32x16_f16 %7, %9, %15, %7\n\t"
-                     "s_waitcnt lgkmcnt(0)"
-                     : "=&v"(nlo), "=&v"(nhi), "=&v"(nwh[0]), "=&v"(nwl[0]), "=&v"(nwh[1]), "=&v"(nwl[1]), "+v"(acc[0]), "+v"(acc[1])
-                     : "v"(al), "v"(ah), "v"(wd[0]), "v"(wl[0]), "v"(wh[0]), "v"(wd[1]), "v"(wl[1]), "v"(wh[1]),
-                       "v"(a0), "v"(a1), "v"(b), "n"(OFF), "n"(OFF + PL), "n"(OFF + 1024), "n"(OFF + PL + 1024)
-                     : "memory");
-}
-
 template <int CIN, int COUT, int R, int CAP, int SU, int NB>
 __global__ __launch_bounds__(64 * (R / 32 + 1)) void sp_conv_blk_kernel(const float* __restrict__ fin,
                                                                        const int* __restrict__ nbr, int pitch,
@@ -241,9 +201,7 @@ __global__ __launch_bounds__(64 * (R / 32 + 1)) void sp_conv_blk_kernel(const fl
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 31, fh = lane >> 5;
-    // XCD-aware placement: each XCD gets one contiguous range of chunks
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int chunk = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
+    const int chunk = gl_xcd_slot();                                         // each XCD: one contiguous range of chunks
     const bool consumer = wave < NWC;
 
     const unsigned smem_base = (unsigned)(size_t)(lds_void*)smem;
@@ -261,10 +219,7 @@ __global__ __launch_bounds__(64 * (R / 32 + 1)) void sp_conv_blk_kernel(const fl
         const int sc = s < NSLAB ? s : s - NSLAB;
         const unsigned char* src = wpk + (size_t)sc * C::SLAB_BYTES + lane * 16;
         const unsigned dst = __builtin_amdgcn_readfirstlane(smem_base + (s % NB) * C::SLAB_BYTES);
-        gl_static_for<C::SLAB_PIECES>([&](auto PC) {
-            constexpr int pc = decltype(PC)::value;
-            __builtin_amdgcn_global_load_lds((gbl_void*)(src + pc * 1024), (lds_void*)(size_t)(dst + pc * 1024), 16, 0, 0);
-        });
+        gl_dma_pieces<C::SLAB_PIECES>(src, dst);
     };
     if (!consumer) {
 #pragma unroll
@@ -335,9 +290,7 @@ __global__ __launch_bounds__(64 * (R / 32 + 1)) void sp_conv_blk_kernel(const fl
     const unsigned wmask = __builtin_amdgcn_readfirstlane(tile < ntiles ? tmask[tile] : 0u);
     f32x16 acc[TN];
 #pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
+    for (int j = 0; j < TN; ++j) acc[j] = gl_zero();
     const unsigned offB = smem_base + (2 * fr + (fh ^ ((fr >> 3) & 1))) * 16;  // the weight image's swizzle
     const unsigned priv = a_base + wave * (32 * ROWB);                       // per-tap path: this wave's 32 rows
     const unsigned loc_lane = loc_base + (wave * 32 + fr) * 2;
@@ -378,7 +331,7 @@ __global__ __launch_bounds__(64 * (R / 32 + 1)) void sp_conv_blk_kernel(const fl
 #pragma unroll
         for (int jn = 0; jn < TN; ++jn) {
             const f16x8 wd = gl_lift_down(wh[jn]);
-            acc[jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, wd, acc[jn], 0, 0, 0);              // smallest first
+            acc[jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, wd, acc[jn], 0, 0, 0);              // smallest first: the order of glds_common.h
             acc[jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wl[jn], acc[jn], 0, 0, 0);
             acc[jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wh[jn], acc[jn], 0, 0, 0);
         }
@@ -442,7 +395,7 @@ __global__ __launch_bounds__(64 * (R / 32 + 1)) void sp_conv_blk_kernel(const fl
                     f16x8 wd[TN];
 #pragma unroll
                     for (int jn = 0; jn < TN; ++jn) wd[jn] = gl_lift_down(wh[cur][jn]);
-                    blk_read_next_mfma<TN, (u + 1) * UNIT_BYTES, NROWS * 32>(vh[nxt], vl[nxt], wh[nxt], wl[nxt], acc, al, ah, wd,
+                    gl_read_next_mfma<TN, (u + 1) * UNIT_BYTES, NROWS * 32>(vh[nxt], vl[nxt], wh[nxt], wl[nxt], acc, al, ah, wd,
                                                                              wl[cur], wh[cur], a_addr(tn, kgn, 0),
                                                                              a_addr(tn, kgn, 1), bslab);
                 } else {
@@ -453,7 +406,7 @@ __global__ __launch_bounds__(64 * (R / 32 + 1)) void sp_conv_blk_kernel(const fl
     }
     __builtin_amdgcn_s_barrier();                                            // every wave is done with the staged rows
 
-    // ---- epilogue (as sp_conv_glds_kernel): transpose each 32 x 32 C tile through LDS, BN / residual / ReLU / store
+    // ---- epilogue (see sp_conv_wave2_kernel): transpose each 32 x 32 C tile through LDS, BN / residual / ReLU / store
     float* scr = reinterpret_cast<float*>(smem + C::W_BYTES + wave * (32 * C::EP_PITCH * 4));
     constexpr int EP_PITCH = C::EP_PITCH;
     const int wrow0 = tile * 32;
@@ -511,30 +464,23 @@ extern "C" int al3d_sp_block_plan(const int* nbr, int64_t nbr_pitch, int K, int 
     return AL3D_OK;
 }
 
-#define BLK_DISPATCH(CI, CO, RR, CAPV, SUV, NBV)                                                                     \
-    if (cin == CI && cout == CO) {                                                                              \
-        const int nchunks = (int)al3d_cdiv(n_out, RR);                                                          \
-        hipLaunchKernelGGL((sp_conv_blk_kernel<CI, CO, RR, CAPV, SUV, NBV>), dim3((unsigned)nchunks),               \
-                           dim3(64 * (RR / 32 + 1)), 0, s, fin, nbr, nbr_pitch, tile_mask, ntiles, (const int2*)plan_hdr, \
-                           plan_rows, (const unsigned short*)plan_loc, (const unsigned char*)wgt_image, scale, shift, \
-                           residual, relu, fout, n_out, io, abl);                                               \
-        AL3D_CHECK_LAUNCH("sp_conv_blk_kernel");                                                                \
-        return AL3D_OK;                                                                                         \
-    }
+// one row of the dispatch: the kernel shape of a channel pair (blk_shape's R and cap)
+#define BLK_DISPATCH(CI, CO, RR, CAPV, SUV, NBV)                                                                    \
+    if (cin == CI && cout == CO)                                                                                    \
+        return sp_launch("sp_conv_blk_kernel", sp_conv_blk_kernel<CI, CO, RR, CAPV, SUV, NBV>, al3d_cdiv(n_out, RR), \
+                         64 * (RR / 32 + 1), stream, fin, nbr, nbr_pitch, tile_mask, ntiles, plan_hdr, plan_rows, plan_loc, \
+                         wgt_image, scale, shift, residual, relu, fout, n_out, io, abl);
 
 extern "C" int al3d_sp_conv_blk_f16x3(const float* fin, const int* nbr, int nbr_pitch, const unsigned* tile_mask,
                                       const int* plan_hdr, const int* plan_rows, const void* plan_loc, int K,
                                       const void* wgt_image, int cin, int cout, const float* scale, const float* shift,
                                       const float* residual, int relu, float* fout, int n_out, int io, void* stream)
 {
-    AL3D_REQUIRE(K == 27 && n_out >= 0, "al3d_sp_conv_blk_f16x3: 27-tap submanifold layers only");
-    AL3D_REQUIRE(io >= 0 && io < 8, "al3d_sp_conv_blk_f16x3: bad io flags");
-    if (n_out == 0) return AL3D_OK;
-    AL3D_REQUIRE(fin && nbr && tile_mask && plan_hdr && plan_rows && plan_loc && wgt_image && fout,
-                 "al3d_sp_conv_blk_f16x3: null pointer");
-    AL3D_REQUIRE(scale, "al3d_sp_conv_blk_f16x3: scale carries the weight exponent and is required");
-    AL3D_REQUIRE(nbr_pitch >= n_out && nbr_pitch % 256 == 0, "al3d_sp_conv_blk_f16x3: nbr_pitch must be al3d_sp_table_pitch(n_out)");
-    hipStream_t s = (hipStream_t)stream;
+    bool run;
+    const int rc = sp_conv_check("al3d_sp_conv_blk_f16x3", K == 27, "27-tap submanifold layers only", io, n_out,
+                                 fin && nbr && tile_mask && plan_hdr && plan_rows && plan_loc && wgt_image && fout, scale,
+                                 nbr_pitch, &run);
+    if (!run) return rc;
     const int ntiles = (int)al3d_cdiv(n_out, 32);
     int abl = 0;
 #ifdef AL3D_BLK_ABLATE

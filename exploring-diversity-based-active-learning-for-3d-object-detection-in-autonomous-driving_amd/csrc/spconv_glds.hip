@@ -34,7 +34,6 @@
 // ascending, al*wd then ah*wl then ah*wh into one fp32 accumulator): outputs are bit-identical, which
 // is what tests/test_detector_gpu.py::test_sparse_conv_glds_kernel_is_bit_identical checks.
 #include "glds_common.h"
-#include "sp_rows.h"
 
 template <int CIN, int COUT, int NW, int R, int UPS, int P, int NB>
 struct GldsCfg {
@@ -101,10 +100,7 @@ __global__ __launch_bounds__(64 * (NW + 1)) void sp_conv_glds_kernel(const float
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 31, fh = lane >> 5;
-    // XCD-aware placement (as sp_conv_wave2_kernel): each XCD gets one contiguous range of row tiles
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int wgt = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
-    const int tile0 = wgt * T;
+    const int tile0 = gl_xcd_slot() * T;                                     // each XCD: one contiguous range of row tiles
     const bool consumer = wave < NW;
 
     const unsigned smem_base = (unsigned)(size_t)(lds_void*)smem;
@@ -141,11 +137,7 @@ __global__ __launch_bounds__(64 * (NW + 1)) void sp_conv_glds_kernel(const float
                 const int tap = rem ? __builtin_ctz(rem) : 0;
                 const unsigned char* src = wpk + (size_t)(tap * KG + (rem ? g : 0)) * UNIT_BYTES + lane * 16;
                 const unsigned dst = __builtin_amdgcn_readfirstlane(smem_base + buf * C::SLAB_BYTES + q * UNIT_BYTES);
-                gl_static_for<C::UNIT_PIECES>([&](auto PC) {
-                    constexpr int pc = decltype(PC)::value;
-                    __builtin_amdgcn_global_load_lds((gbl_void*)(src + pc * 1024), (lds_void*)(size_t)(dst + pc * 1024),
-                                                     16, 0, 0);
-                });
+                gl_dma_pieces<C::UNIT_PIECES>(src, dst);
                 if (rem && ++g == KG) { g = 0; rem &= rem - 1u; }
             });
         };
@@ -203,9 +195,7 @@ __global__ __launch_bounds__(64 * (NW + 1)) void sp_conv_glds_kernel(const float
 #pragma unroll
     for (int r = 0; r < R; ++r)
 #pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[r][j][e] = 0.f;
+        for (int j = 0; j < TN; ++j) acc[r][j] = gl_zero();
 
     // gather side: this lane fetches chunk (s ^ f(row)) of rows NP*jg + i, i = 0..NP-1
     const int jg = lane / LPR, sg = lane % LPR;
@@ -310,7 +300,7 @@ __global__ __launch_bounds__(64 * (NW + 1)) void sp_conv_glds_kernel(const float
 #pragma unroll
                     for (int jn = 0; jn < TN; ++jn) {
                         const f16x8 wd = gl_lift_down(wh[ua][jn]);
-                        acc[r][jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, wd, acc[r][jn], 0, 0, 0);     // smallest first
+                        acc[r][jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, wd, acc[r][jn], 0, 0, 0);     // smallest first: the order of glds_common.h
                         acc[r][jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wl[ua][jn], acc[r][jn], 0, 0, 0);
                         acc[r][jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wh[ua][jn], acc[r][jn], 0, 0, 0);
                     }
@@ -323,7 +313,7 @@ __global__ __launch_bounds__(64 * (NW + 1)) void sp_conv_glds_kernel(const float
     }
     gl_wait_vm<0>();                                                         // the tail's dummy gathers
 
-    // ---- epilogue (as sp_conv_wave2_kernel): transpose each 32 x 32 C tile through the wave's own LDS
+    // ---- epilogue (see sp_conv_wave2_kernel): transpose each 32 x 32 C tile through the wave's own LDS
     // (its gather slots: wave-private, no barrier) and move float4s over the contiguous 32-row block
     float* scr = reinterpret_cast<float*>(smem + C::W_BYTES + wave * C::A_WAVE_BYTES);
     constexpr int EP_PITCH = C::EP_PITCH;
@@ -384,48 +374,22 @@ extern "C" int al3d_sp_pack_glds_f16x3(const void* planes_f16x2, int cout, int K
     return AL3D_OK;
 }
 
-#define GLDS_DISPATCH_ABL(CI, CO, NW, R, UPS, P, NB, ABL)                                              \
-    if (cin == CI && cout == CO) {                                                                      \
-        hipLaunchKernelGGL((sp_conv_glds_kernel<CI, CO, NW, R, UPS, P, NB, ABL>),                       \
-                           dim3((unsigned)al3d_cdiv(ntiles, NW * R)), dim3(64 * (NW + 1)), 0, s, fin, nbr, nbr_pitch, \
-                           tile_mask, ntiles, (const unsigned char*)wgt_image, scale, shift, residual, relu, fout, n_out, io); \
-        AL3D_CHECK_LAUNCH("sp_conv_glds_kernel");                                                       \
-        return AL3D_OK;                                                                                 \
-    }
+// one row of the dispatch: the kernel shape of a channel pair
+#define GLDS_DISPATCH_ABL(CI, CO, NW, R, UPS, P, NB, ABL)                                                         \
+    if (cin == CI && cout == CO)                                                                                   \
+        return sp_launch("sp_conv_glds_kernel", sp_conv_glds_kernel<CI, CO, NW, R, UPS, P, NB, ABL>,               \
+                         al3d_cdiv(ntiles, NW * R), 64 * (NW + 1), stream, fin, nbr, nbr_pitch, tile_mask, ntiles,  \
+                         wgt_image, scale, shift, residual, relu, fout, n_out, io);
 #define GLDS_DISPATCH(CI, CO, NW, R, UPS, P, NB) GLDS_DISPATCH_ABL(CI, CO, NW, R, UPS, P, NB, 0)
 
-static int sp_conv_glds_impl(const float* fin, const int* nbr, int nbr_pitch, const unsigned* tile_mask, int K,
-                             const void* wgt_image, int cin, int cout, const float* scale, const float* shift,
-                             const float* residual, int relu, float* fout, int n_out, int io, void* stream);
-
-extern "C" int al3d_sp_conv_glds_f16x3(const float* fin, const int* nbr, int nbr_pitch, const unsigned* tile_mask, int K,
-                                       const void* wgt_image, int cin, int cout, const float* scale, const float* shift,
-                                       const float* residual, int relu, float* fout, int n_out, void* stream)
+static int sp_conv_glds(const float* fin, const int* nbr, int nbr_pitch, const unsigned* tile_mask, int K,
+                        const void* wgt_image, int cin, int cout, const float* scale, const float* shift,
+                        const float* residual, int relu, float* fout, int n_out, int io, void* stream)
 {
-    return sp_conv_glds_impl(fin, nbr, nbr_pitch, tile_mask, K, wgt_image, cin, cout, scale, shift, residual, relu, fout, n_out,
-                             0, stream);
-}
-
-// ... with the row formats of sp_rows.h: io bit 0 = input pair rows, bit 1 = write pair rows, bit 2 = residual pair rows
-extern "C" int al3d_sp_conv_glds_f16x3_io(const float* fin, const int* nbr, int nbr_pitch, const unsigned* tile_mask, int K,
-                                          const void* wgt_image, int cin, int cout, const float* scale, const float* shift,
-                                          const float* residual, int relu, float* fout, int n_out, int io, void* stream)
-{
-    AL3D_REQUIRE(io >= 0 && io < 8 && cout % 8 == 0, "al3d_sp_conv_glds_f16x3_io: bad io flags / channels");
-    return sp_conv_glds_impl(fin, nbr, nbr_pitch, tile_mask, K, wgt_image, cin, cout, scale, shift, residual, relu, fout, n_out,
-                             io, stream);
-}
-
-static int sp_conv_glds_impl(const float* fin, const int* nbr, int nbr_pitch, const unsigned* tile_mask, int K,
-                             const void* wgt_image, int cin, int cout, const float* scale, const float* shift,
-                             const float* residual, int relu, float* fout, int n_out, int io, void* stream)
-{
-    AL3D_REQUIRE(K >= 1 && K <= 27 && n_out >= 0, "al3d_sp_conv_glds_f16x3: bad sizes");
-    if (n_out == 0) return AL3D_OK;
-    AL3D_REQUIRE(fin && nbr && tile_mask && wgt_image && fout, "al3d_sp_conv_glds_f16x3: null pointer");
-    AL3D_REQUIRE(scale, "al3d_sp_conv_glds_f16x3: scale carries the weight exponent and is required");
-    AL3D_REQUIRE(nbr_pitch >= n_out && nbr_pitch % 256 == 0, "al3d_sp_conv_glds_f16x3: nbr_pitch must be al3d_sp_table_pitch(n_out)");
-    hipStream_t s = (hipStream_t)stream;
+    bool run;
+    const int rc = sp_conv_check("al3d_sp_conv_glds_f16x3", K >= 1 && K <= 27, "bad sizes", io, n_out,
+                                 fin && nbr && tile_mask && wgt_image && fout, scale, nbr_pitch, &run);
+    if (!run) return rc;
     const int ntiles = (int)al3d_cdiv(n_out, 32);
 #ifdef AL3D_GLDS_ABLATE
     // tuning build only (make EXTRA=-DAL3D_GLDS_ABLATE): AL3D_GLDS_ABL / AL3D_GLDS_CFG pick an ablation / a shape
@@ -450,4 +414,22 @@ static int sp_conv_glds_impl(const float* fin, const int* nbr, int nbr_pitch, co
     GLDS_DISPATCH(16, 16, 8, 1, 4, 3, 2) GLDS_DISPATCH(16, 32, 8, 1, 4, 3, 2) GLDS_DISPATCH(32, 32, 7, 1, 4, 2, 2) GLDS_DISPATCH(32, 64, 7, 1, 2, 2, 2)
     GLDS_DISPATCH(64, 64, 7, 1, 2, 2, 2) GLDS_DISPATCH(64, 128, 5, 1, 2, 2, 2) GLDS_DISPATCH(128, 128, 5, 1, 2, 2, 2)
     return al3d_fail(AL3D_EINVAL, "al3d_sp_conv_glds_f16x3: unsupported channel pair %d -> %d", cin, cout);
+}
+
+extern "C" int al3d_sp_conv_glds_f16x3(const float* fin, const int* nbr, int nbr_pitch, const unsigned* tile_mask, int K,
+                                       const void* wgt_image, int cin, int cout, const float* scale, const float* shift,
+                                       const float* residual, int relu, float* fout, int n_out, void* stream)
+{
+    return sp_conv_glds(fin, nbr, nbr_pitch, tile_mask, K, wgt_image, cin, cout, scale, shift, residual, relu, fout, n_out, 0,
+                        stream);
+}
+
+// ... with the row formats of sp_rows.h: io bit 0 = input pair rows, bit 1 = write pair rows, bit 2 = residual pair rows
+extern "C" int al3d_sp_conv_glds_f16x3_io(const float* fin, const int* nbr, int nbr_pitch, const unsigned* tile_mask, int K,
+                                          const void* wgt_image, int cin, int cout, const float* scale, const float* shift,
+                                          const float* residual, int relu, float* fout, int n_out, int io, void* stream)
+{
+    AL3D_REQUIRE(io >= 0 && io < 8 && cout % 8 == 0, "al3d_sp_conv_glds_f16x3_io: bad io flags / channels");
+    return sp_conv_glds(fin, nbr, nbr_pitch, tile_mask, K, wgt_image, cin, cout, scale, shift, residual, relu, fout, n_out, io,
+                        stream);
 }

@@ -24,7 +24,6 @@
 // Arithmetic and summation order are sp_conv_wave2's (tap ascending; per tap xl' wd, xh wl, xh wh into one fp32
 // accumulator of v_mfma_f32_32x32x16_f16): outputs are bit-identical to it row for row.
 #include "glds_common.h"
-#include "sp_rows.h"
 #include "al3d_scan.h"
 
 // =====================================================================================================
@@ -616,6 +615,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 ? 3 : 1)) void sp_conv_r16_kernel
     }
     __syncthreads();
 
+    // XCD placement: glds_common.h's gl_xcd_slot spelled out (calling it changes this kernel's register allocation)
     const int nwg = gridDim.x, xcd = blockIdx.x & 7, q8 = nwg >> 3, r8 = nwg & 7;
     const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
     const int tile0 = (wg * NW + wave) * tpw;
@@ -689,7 +689,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 ? 3 : 1)) void sp_conv_r16_kernel
             gl_split8_f16(vlo, vhi, ah, al);
         }
         const f16x8 wd = gl_lift_down(wh);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, wd, acc, 0, 0, 0);       // smallest first
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, wd, acc, 0, 0, 0);       // smallest first: the order of glds_common.h
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wl, acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wh, acc, 0, 0, 0);
     };
@@ -868,15 +868,10 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 ? 3 : 1)) void sp_conv_r16_kernel
     }
 }
 
-#define R16_LAUNCH(CO, NW, P, CAP, RES)                                                                            \
-    do {                                                                                                             \
-        const int per_wg = (NW) * tpw;                                                                               \
-        hipLaunchKernelGGL((sp_conv_r16_kernel<CO, NW, P, CAP, RES>), dim3((unsigned)al3d_cdiv(ntiles, per_wg)),     \
-                           dim3(64 * (NW)), 0, s, fin, nbr, nbr_pitch, (const int4*)items, first, ntiles, tpw,         \
-                           (const unsigned char*)wgt_image, scale, shift, residual, relu, fout, n_out, io, abl);      \
-        AL3D_CHECK_LAUNCH("sp_conv_r16_kernel");                                                                   \
-        return AL3D_OK;                                                                                              \
-    } while (0)
+#define R16_LAUNCH(CO, NW, P, CAP, RES)                                                                              \
+    return sp_launch("sp_conv_r16_kernel", sp_conv_r16_kernel<CO, NW, P, CAP, RES>, al3d_cdiv(ntiles, (NW) * tpw), 64 * (NW), \
+                     stream, fin, nbr, nbr_pitch, items, first, ntiles, tpw, wgt_image, scale, shift, residual, relu, fout,    \
+                     n_out, io, abl)
 
 // Same contract as al3d_sp_conv_rng_f16x3 for Cin = 16: a tiled 27-tap table (submanifold or strided) + its item list
 // (al3d_sp_tile_items), weight image of al3d_sp_pack_r16_f16x3.  Rows of the INPUT level should be in raster order for the
@@ -886,13 +881,10 @@ extern "C" int al3d_sp_conv_r16_f16x3(const float* fin, const int* nbr, int nbr_
                                       const float* residual, int relu, float* fout, int n_out, int io, int tiles_per_wave,
                                       void* stream)
 {
-    AL3D_REQUIRE(K == 27 && cin == 16 && n_out >= 0, "al3d_sp_conv_r16_f16x3: 27-tap layers with 16 input channels only");
-    AL3D_REQUIRE(io >= 0 && io < 8, "al3d_sp_conv_r16_f16x3: bad io flags");
-    if (n_out == 0) return AL3D_OK;
-    AL3D_REQUIRE(fin && nbr && items && first && wgt_image && fout, "al3d_sp_conv_r16_f16x3: null pointer");
-    AL3D_REQUIRE(scale, "al3d_sp_conv_r16_f16x3: scale carries the weight exponent and is required");
-    AL3D_REQUIRE(nbr_pitch >= n_out && nbr_pitch % 256 == 0, "al3d_sp_conv_r16_f16x3: nbr_pitch must be al3d_sp_table_pitch(n_out)");
-    hipStream_t s = (hipStream_t)stream;
+    bool run;
+    const int rc = sp_conv_check("al3d_sp_conv_r16_f16x3", K == 27 && cin == 16, "27-tap layers with 16 input channels only", io,
+                                 n_out, fin && nbr && items && first && wgt_image && fout, scale, nbr_pitch, &run);
+    if (!run) return rc;
     const int ntiles = (int)al3d_cdiv(n_out, 32);
     // tiles per wave: longer item streams amortise the pipeline's fill (8: -1.5 % at 240k tiles), shorter ones keep small
     // launches balanced over the CUs (4: -7 % at 60k tiles); AL3D_R16_TPW (dev knob) overrides: 4 / 8 / 16 / 32 measure

@@ -23,7 +23,6 @@
 // Accumulation order per output row: group, channel chunk, kx, unit -- for Cin = 32 (one chunk) exactly the tap,
 // unit order of sp_conv_wave2 / sp_conv_glds: bit-identical.
 #include "glds_common.h"
-#include "sp_rows.h"
 
 template <int CIN, int COUT, int NW, int P, int CAP>
 struct RngCfg {
@@ -66,45 +65,6 @@ __device__ __forceinline__ void rg_lds_read_idx1(int& i0, unsigned addr)
     asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(i0) : "v"(addr) : "memory");
 }
 
-// One pipelined unit: the ds_reads of the NEXT unit's A / B fragments interleaved with the MFMAs of the current
-// unit, closed by the lgkmcnt wait -- one asm block, so no register is visible to hipcc while it is in flight.
-// (`s_nop 1`: the operands come from VALU instructions right before the block -- 2 wait states to an MFMA read.)
-template <int TN, int OFF, int PL>
-__device__ __forceinline__ void rg_read_next_mfma(gl_f32x4& nlo, gl_f32x4& nhi, f16x8 (&nwh)[TN], f16x8 (&nwl)[TN],
-                                                  f32x16 (&acc)[TN], const f16x8& al, const f16x8& ah,
-                                                  const f16x8 (&wd)[TN], const f16x8 (&wl)[TN], const f16x8 (&wh)[TN],
-                                                  unsigned a0, unsigned a1, unsigned b)
-{
-    static_assert(TN == 1 || TN == 2, "tile counts of the built channel pairs");
-    if constexpr (TN == 1)
-        asm volatile("s_nop 1\n\t"
-                     "ds_read_b128 %0, %10\n\tds_read_b128 %1, %11\n\t"
-                     "v_mfma_f32_32x32x16_f16 %4, %5, %7, %4\n\t"
-                     "ds_read_b128 %2, %12 offset:%13\n\tds_read_b128 %3, %12 offset:%14\n\t"
-                     "v_mfma_f32_32x32x16_f16 %4, %6, %8, %4\n\t"
-                     "v_mfma_f32_32x32x16_f16 %4, %6, %9, %4\n\t"
-                     "s_waitcnt lgkmcnt(0)"
-                     : "=&v"(nlo), "=&v"(nhi), "=&v"(nwh[0]), "=&v"(nwl[0]), "+v"(acc[0])
-                     : "v"(al), "v"(ah), "v"(wd[0]), "v"(wl[0]), "v"(wh[0]), "v"(a0), "v"(a1), "v"(b), "n"(OFF), "n"(OFF + PL)
-                     : "memory");
-    else
-        asm volatile("s_nop 1\n\t"
-                     "ds_read_b128 %0, %16\n\tds_read_b128 %1, %17\n\t"
-                     "v_mfma_f32_32x32x16_f16 %6, %8, %10, %6\n\t"
-                     "v_mfma_f32_32x32x16_f16 %7, %8, %13, %7\n\t"
-                     "ds_read_b128 %2, %18 offset:%19\n\tds_read_b128 %3, %18 offset:%20\n\t"
-                     "v_mfma_f32_32x32x16_f16 %6, %9, %11, %6\n\t"
-                     "v_mfma_f32_32x32x16_f16 %7, %9, %14, %7\n\t"
-                     "ds_read_b128 %4, %18 offset:%21\n\tds_read_b128 %5, %18 offset:%22\n\t"
-                     "v_mfma_f32_32x32x16_f16 %6, %9, %12, %6\n\t"
-                     "v_mfma_f32_32x32x16_f16 %7, %9, %15, %7\n\t"
-                     "s_waitcnt lgkmcnt(0)"
-                     : "=&v"(nlo), "=&v"(nhi), "=&v"(nwh[0]), "=&v"(nwl[0]), "=&v"(nwh[1]), "=&v"(nwl[1]), "+v"(acc[0]), "+v"(acc[1])
-                     : "v"(al), "v"(ah), "v"(wd[0]), "v"(wl[0]), "v"(wh[0]), "v"(wd[1]), "v"(wl[1]), "v"(wh[1]),
-                       "v"(a0), "v"(a1), "v"(b), "n"(OFF), "n"(OFF + PL), "n"(OFF + 1024), "n"(OFF + PL + 1024)
-                     : "memory");
-}
-
 template <int CIN, int COUT, int NW, int P, int CAP>
 __global__ __launch_bounds__(64 * (NW + 1)) void sp_conv_rng_kernel(const float* __restrict__ fin,
                                                                    const int* __restrict__ nbr, int pitch,
@@ -124,10 +84,7 @@ __global__ __launch_bounds__(64 * (NW + 1)) void sp_conv_rng_kernel(const float*
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 31, fh = lane >> 5;
-    // XCD-aware placement (as sp_conv_glds_kernel): each XCD gets one contiguous range of row tiles
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int wgt = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
-    const int tile0 = wgt * NW;
+    const int tile0 = gl_xcd_slot() * NW;                                    // each XCD: one contiguous range of row tiles
     const bool consumer = wave < NW;
 
     const unsigned smem_base = (unsigned)(size_t)(lds_void*)smem;
@@ -162,11 +119,7 @@ __global__ __launch_bounds__(64 * (NW + 1)) void sp_conv_rng_kernel(const float*
                 constexpr int kx = decltype(KX)::value;
                 const unsigned char* src = wpk + (size_t)((3 * g + kx) * KG + (rem ? cc : 0) * UA) * UNIT_BYTES + lane * 16;
                 const unsigned dst = __builtin_amdgcn_readfirstlane(smem_base + buf * C::SLAB_BYTES + kx * UA * UNIT_BYTES);
-                gl_static_for<UA * C::UNIT_PIECES>([&](auto PC) {
-                    constexpr int pc = decltype(PC)::value;
-                    __builtin_amdgcn_global_load_lds((gbl_void*)(src + pc * 1024), (lds_void*)(size_t)(dst + pc * 1024),
-                                                     16, 0, 0);
-                });
+                gl_dma_pieces<UA * C::UNIT_PIECES>(src, dst);
             });
             if (rem && ++cc == NCC) { cc = 0; rem &= rem - 1u; }
         };
@@ -192,9 +145,7 @@ __global__ __launch_bounds__(64 * (NW + 1)) void sp_conv_rng_kernel(const float*
 
     f32x16 acc[TN];
 #pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
+    for (int j = 0; j < TN; ++j) acc[j] = gl_zero();
 
     // DMA side of a range: lane (j, s) of piece i fetches chunk s ^ f(r) of staged row r = 8 i + j
     const int jd = lane >> 3, sd = lane & 7;
@@ -310,12 +261,12 @@ __global__ __launch_bounds__(64 * (NW + 1)) void sp_conv_rng_kernel(const float*
 #pragma unroll
                 for (int jn = 0; jn < TN; ++jn) wd[jn] = gl_lift_down(wh[cur][jn]);
                 if constexpr (u + 1 < 3 * UA) {
-                    rg_read_next_mfma<TN, (u + 1) * UNIT_BYTES, NROWS * 32>(vlo[nxt], vhi[nxt], wh[nxt], wl[nxt], acc, al, ah, wd,
+                    gl_read_next_mfma<TN, (u + 1) * UNIT_BYTES, NROWS * 32>(vlo[nxt], vhi[nxt], wh[nxt], wl[nxt], acc, al, ah, wd,
                                                                            wl[cur], wh[cur], ua0[u + 1], ua1[u + 1], bslab);
                 } else {
 #pragma unroll
                     for (int jn = 0; jn < TN; ++jn) {
-                        acc[jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, wd[jn], acc[jn], 0, 0, 0);     // smallest first
+                        acc[jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, wd[jn], acc[jn], 0, 0, 0);     // smallest first: the order of glds_common.h
                         acc[jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wl[cur][jn], acc[jn], 0, 0, 0);
                         acc[jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wh[cur][jn], acc[jn], 0, 0, 0);
                     }
@@ -429,14 +380,12 @@ extern "C" int al3d_sp_tile_ranges(const int* nbr, int64_t nbr_pitch, int K, int
     return AL3D_OK;
 }
 
-#define RNG_DISPATCH(CI, CO, NW, P, CAP)                                                                      \
-    if (cin == CI && cout == CO) {                                                                              \
-        hipLaunchKernelGGL((sp_conv_rng_kernel<CI, CO, NW, P, CAP>), dim3((unsigned)al3d_cdiv(ntiles, NW)),     \
-                           dim3(64 * (NW + 1)), 0, s, fin, nbr, nbr_pitch, tile_mask, (const int2*)tile_rng, ntiles, \
-                           (const unsigned char*)wgt_image, scale, shift, residual, relu, fout, n_out, io);     \
-        AL3D_CHECK_LAUNCH("sp_conv_rng_kernel");                                                                \
-        return AL3D_OK;                                                                                         \
-    }
+// one row of the dispatch: the kernel shape of a channel pair
+#define RNG_DISPATCH(CI, CO, NW, P, CAP)                                                                            \
+    if (cin == CI && cout == CO)                                                                                    \
+        return sp_launch("sp_conv_rng_kernel", sp_conv_rng_kernel<CI, CO, NW, P, CAP>, al3d_cdiv(ntiles, NW),       \
+                         64 * (NW + 1), stream, fin, nbr, nbr_pitch, tile_mask, tile_rng, ntiles, wgt_image, scale, shift, \
+                         residual, relu, fout, n_out, io);
 
 // Same contract as al3d_sp_conv_glds_f16x3 (tiled 27-tap SubM table, weight image of al3d_sp_pack_glds_f16x3) plus
 // tile_rng from al3d_sp_tile_ranges on the same table.  Rows of the level must be in raster order for the ranges to
@@ -446,13 +395,10 @@ extern "C" int al3d_sp_conv_rng_f16x3(const float* fin, const int* nbr, int nbr_
                                       const float* scale, const float* shift, const float* residual, int relu,
                                       float* fout, int n_out, int io, void* stream)
 {
-    AL3D_REQUIRE(K == 27 && n_out >= 0, "al3d_sp_conv_rng_f16x3: 27-tap submanifold layers only");
-    AL3D_REQUIRE(io >= 0 && io < 8, "al3d_sp_conv_rng_f16x3: bad io flags");
-    if (n_out == 0) return AL3D_OK;
-    AL3D_REQUIRE(fin && nbr && tile_mask && tile_rng && wgt_image && fout, "al3d_sp_conv_rng_f16x3: null pointer");
-    AL3D_REQUIRE(scale, "al3d_sp_conv_rng_f16x3: scale carries the weight exponent and is required");
-    AL3D_REQUIRE(nbr_pitch >= n_out && nbr_pitch % 256 == 0, "al3d_sp_conv_rng_f16x3: nbr_pitch must be al3d_sp_table_pitch(n_out)");
-    hipStream_t s = (hipStream_t)stream;
+    bool run;
+    const int rc = sp_conv_check("al3d_sp_conv_rng_f16x3", K == 27, "27-tap submanifold layers only", io, n_out,
+                                 fin && nbr && tile_mask && tile_rng && wgt_image && fout, scale, nbr_pitch, &run);
+    if (!run) return rc;
     const int ntiles = (int)al3d_cdiv(n_out, 32);
     // shapes: as many consumer waves as the LDS holds with two slots each -- the kernel is bound by the latency chain
     // of a wave's item times the resident waves (7 -> 10 -> 12 waves: 968 -> 852 -> 795 us on the 32 -> 32 layers),

@@ -10,10 +10,8 @@
 // waves of the workgroup, double-buffered, one barrier per slab.  Waves skip the offsets that
 // are empty for their own 32 rows and otherwise run unsynchronised, so gather latency is hidden
 // by the other waves on the SIMD instead of by a software pipeline.
-#include "al3d_common.h"
-#include "sp_rows.h"
+#include "glds_common.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 #define SW_ROWS 128                 // rows per workgroup (4 waves x 32)
@@ -210,30 +208,19 @@ __global__ __launch_bounds__(256) void sp_conv_wave_kernel(const float* __restri
 __device__ __attribute__((aligned(256))) float g_sw_zero[128];   // stays zero: target of masked gathers
 __device__ int g_sw_neg1 = -1;                                    // "no neighbour" for masked index loads
 
-// ---- f16x3 arithmetic (see conv2d_f16x3.hip): x = xh + xl' * 2^-11 with xh = f16(x),
-// xl' = f16((x - xh) * 2^11); x*w = xh*wh + xh*wl + xl'*(wh * 2^-11), three f16 MFMAs per tile.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 sw_f16x2 __attribute__((ext_vector_type(2)));
+// ---- f16x3 arithmetic: the split, the lift and the order of a unit's three products are glds_common.h's; here on the
+// operand types of this kernel's plain loads (float4 fragments, uint4 weight pieces)
 __device__ __forceinline__ void sw_split8_f16(const float4& lo, const float4& hi, f16x8& ph, f16x8& pl)
 {
     const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    unsigned h[4], l[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const sw_f32x2 x = {v[2 * e], v[2 * e + 1]};
-        const sw_f16x2 xh = __builtin_convertvector(x, sw_f16x2);
-        // (x - xh) * 2^11 == fma(xh, -2^11, x * 2^11) exactly (power-of-two scalings, exact residual)
-        const sw_f32x2 r = {__builtin_fmaf((float)xh[0], -2048.0f, x[0] * 2048.0f),
-                            __builtin_fmaf((float)xh[1], -2048.0f, x[1] * 2048.0f)};
-        h[e] = __builtin_bit_cast(unsigned, xh);
-        l[e] = __builtin_bit_cast(unsigned, __builtin_convertvector(r, sw_f16x2));
-    }
-    ph = __builtin_bit_cast(f16x8, make_uint4(h[0], h[1], h[2], h[3]));
-    pl = __builtin_bit_cast(f16x8, make_uint4(l[0], l[1], l[2], l[3]));
+    uint4 h, l;
+    sp_split8(v, h, l);
+    ph = __builtin_bit_cast(f16x8, h);
+    pl = __builtin_bit_cast(f16x8, l);
 }
 __device__ __forceinline__ uint4 sw_lift_down(const uint4& wh)       // 8 f16 * 2^-11 (packed multiplies)
 {
-    return __builtin_bit_cast(uint4, __builtin_bit_cast(f16x8, wh) * (_Float16)0.00048828125f);
+    return __builtin_bit_cast(uint4, gl_lift_down(__builtin_bit_cast(f16x8, wh)));
 }
 
 template <int CIN, int COUT, int NW, int UPS, int P, int NPL>
@@ -275,11 +262,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 8)))
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fr = lane & 31, fh = lane >> 5;
-    // XCD-aware placement: blocks with equal blockIdx % 8 share an L2, so give each of the eight
-    // groups one contiguous range of row tiles (rows are in raster order, neighbours of a tile
-    // live in nearby tiles) instead of every eighth tile.  Bijective for any grid size.
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
+    const int tile = gl_xcd_slot();                      // each XCD: one contiguous range of row tiles
     const int row0 = tile * (32 * NW);
     const int my_row = row0 + wave * 32 + fr;
     const bool row_ok = my_row < n_out;
@@ -326,9 +309,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 8)))
 
     f32x16 acc[TN];
 #pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+    for (int j = 0; j < TN; ++j) acc[j] = gl_zero();
 
     // every global load in the main loop is unconditional (clamped or redirected addresses): a
     // branch around a VMEM op makes hipcc fall back to vmcnt(0) at each consume, which would
@@ -445,7 +426,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 8)))
                             const f16x8 wh = *reinterpret_cast<const f16x8*>(live ? ub + (0 * NROWS + n) * SW_PITCH + 16 * fh : zrow);
                             const f16x8 wl = *reinterpret_cast<const f16x8*>(live ? ub + (1 * NROWS + n) * SW_PITCH + 16 * fh : zrow);
                             const f16x8 wd = *reinterpret_cast<const f16x8*>(live ? ub + (2 * NROWS + n) * SW_PITCH + 16 * fh : zrow);
-                            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, wd, acc[j], 0, 0, 0);     // smallest first
+                            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, wd, acc[j], 0, 0, 0);     // smallest first: the order of glds_common.h
                             acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wl, acc[j], 0, 0, 0);
                             acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wh, acc[j], 0, 0, 0);
                         }
@@ -495,15 +476,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 8)))
     }
 }
 
-#define SW2_DISPATCH(CI, CO, NW, UPS, P, NPL)                                                         \
-    if (cin == CI && cout == CO) {                                                                    \
-        hipLaunchKernelGGL((sp_conv_wave2_kernel<CI, CO, NW, UPS, P, NPL>),                           \
-                           dim3((unsigned)al3d_cdiv(n_out, 32 * NW)), dim3(64 * NW), 0, s, fin, nbr, K, \
-                           (const unsigned short*)wgt, scale, shift, residual, relu, fout, n_out,     \
-                           (int64_t)nbr_pitch, tile_mask, io);                                        \
-        AL3D_CHECK_LAUNCH("sp_conv_wave2_kernel");                                                    \
-        return AL3D_OK;                                                                               \
-    }
+#define SW2_DISPATCH(CI, CO, NW, UPS, P, NPL)                                                                       \
+    if (cin == CI && cout == CO)                                                                                    \
+        return sp_launch("sp_conv_wave2_kernel", sp_conv_wave2_kernel<CI, CO, NW, UPS, P, NPL>, al3d_cdiv(n_out, 32 * NW), \
+                         64 * NW, s, fin, nbr, K, wgt, scale, shift, residual, relu, fout, n_out, nbr_pitch, tile_mask, io);
 
 extern "C" int al3d_sp_conv_wave2_bf16x6(const float* fin, const int* nbr, int K, const void* wgt_bf16x3,
                                          int cin, int cout, const float* scale, const float* shift,
@@ -522,54 +498,16 @@ extern "C" int al3d_sp_conv_wave2_bf16x6(const float* fin, const int* nbr, int K
     return al3d_fail(AL3D_EINVAL, "al3d_sp_conv_wave2_bf16x6: unsupported channel pair %d -> %d", cin, cout);
 }
 
-static int sp_conv_wave2_f16x3_impl(const float* fin, const int* nbr, int nbr_pitch, const unsigned* tile_mask, int K,
-                                    const void* wgt_f16x2, int cin, int cout, const float* scale, const float* shift,
-                                    const float* residual, int relu, float* fout, int n_out, int io, void* stream);
-
-extern "C" int al3d_sp_conv_wave2_f16x3(const float* fin, const int* nbr, int K, const void* wgt_f16x2,
-                                        int cin, int cout, const float* scale, const float* shift,
-                                        const float* residual, int relu, float* fout, int n_out,
-                                        void* stream)
+// the f16x3 entry points: the plain rulebook (tile_mask null, pitch = n_out) or a tiled one
+static int sp_conv_wave2_f16x3(const float* fin, const int* nbr, int nbr_pitch, const unsigned* tile_mask, int K,
+                               const void* wgt, int cin, int cout, const float* scale, const float* shift,
+                               const float* residual, int relu, float* fout, int n_out, int io, void* stream)
 {
-    return sp_conv_wave2_f16x3_impl(fin, nbr, n_out, nullptr, K, wgt_f16x2, cin, cout, scale, shift, residual, relu, fout,
-                                    n_out, 0, stream);
-}
-
-// the same kernel on a tiled rulebook (al3d_sp_*_table_tiles): pitched table, per-tile tap masks read instead of scanned
-extern "C" int al3d_sp_conv_wave2_f16x3_tiles(const float* fin, const int* nbr, int nbr_pitch, const unsigned* tile_mask,
-                                              int K, const void* wgt_f16x2, int cin, int cout, const float* scale,
-                                              const float* shift, const float* residual, int relu, float* fout, int n_out,
-                                              void* stream)
-{
-    AL3D_REQUIRE(tile_mask && nbr_pitch >= n_out && nbr_pitch % 256 == 0,
-                 "al3d_sp_conv_wave2_f16x3_tiles: needs a tiled rulebook (pitch = al3d_sp_table_pitch(n_out), tile masks)");
-    return sp_conv_wave2_f16x3_impl(fin, nbr, nbr_pitch, tile_mask, K, wgt_f16x2, cin, cout, scale, shift, residual, relu,
-                                    fout, n_out, 0, stream);
-}
-
-// ... with the row formats of sp_rows.h: io bit 0 = input pair rows, bit 1 = write pair rows, bit 2 = residual pair rows
-extern "C" int al3d_sp_conv_wave2_f16x3_tiles_io(const float* fin, const int* nbr, int nbr_pitch, const unsigned* tile_mask,
-                                                 int K, const void* wgt_f16x2, int cin, int cout, const float* scale,
-                                                 const float* shift, const float* residual, int relu, float* fout, int n_out,
-                                                 int io, void* stream)
-{
-    AL3D_REQUIRE(tile_mask && nbr_pitch >= n_out && nbr_pitch % 256 == 0,
-                 "al3d_sp_conv_wave2_f16x3_tiles_io: needs a tiled rulebook (pitch = al3d_sp_table_pitch(n_out), tile masks)");
-    AL3D_REQUIRE(io >= 0 && io < 8 && cin % 8 == 0 && cout % 8 == 0, "al3d_sp_conv_wave2_f16x3_tiles_io: bad io flags / channels");
-    return sp_conv_wave2_f16x3_impl(fin, nbr, nbr_pitch, tile_mask, K, wgt_f16x2, cin, cout, scale, shift, residual, relu,
-                                    fout, n_out, io, stream);
-}
-
-static int sp_conv_wave2_f16x3_impl(const float* fin, const int* nbr, int nbr_pitch, const unsigned* tile_mask, int K,
-                                    const void* wgt_f16x2, int cin, int cout, const float* scale, const float* shift,
-                                    const float* residual, int relu, float* fout, int n_out, int io, void* stream)
-{
-    AL3D_REQUIRE(K >= 1 && K <= 27 && n_out >= 0, "al3d_sp_conv_wave2_f16x3: bad sizes");
-    if (n_out == 0) return AL3D_OK;
-    AL3D_REQUIRE(fin && nbr && wgt_f16x2 && fout, "al3d_sp_conv_wave2_f16x3: null pointer");
-    AL3D_REQUIRE(scale, "al3d_sp_conv_wave2_f16x3: scale carries the weight exponent and is required");
+    bool run;
+    const int rc = sp_conv_check("al3d_sp_conv_wave2_f16x3", K >= 1 && K <= 27, "bad sizes", io, n_out, fin && nbr && wgt && fout,
+                                 scale, -1, &run);
+    if (!run) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const void* wgt = wgt_f16x2;
     // f16x3 halves the MFMA time of a unit, so the 32-channel layers take four units per slab (one barrier
     // per 12 MFMAs instead of 6: -3 %); the LDS this needs is below the epilogue scratch anyway
     // 128 output channels: two 8-wave workgroups per CU (default) instead of one of 16 waves (AL3D_SW2_NW128=16, round 1's
@@ -584,6 +522,40 @@ static int sp_conv_wave2_f16x3_impl(const float* fin, const int* nbr, int nbr_pi
     SW2_DISPATCH(16, 16, 4, 4, 4, 2) SW2_DISPATCH(16, 32, 8, 4, 2, 2) SW2_DISPATCH(32, 32, 8, 4, 2, 2) SW2_DISPATCH(32, 64, 8, 4, 2, 2)
     SW2_DISPATCH(64, 64, 8, 4, 2, 2) SW2_DISPATCH(64, 128, 16, 2, 2, 2) SW2_DISPATCH(128, 128, 16, 2, 2, 2)
     return al3d_fail(AL3D_EINVAL, "al3d_sp_conv_wave2_f16x3: unsupported channel pair %d -> %d", cin, cout);
+}
+
+extern "C" int al3d_sp_conv_wave2_f16x3(const float* fin, const int* nbr, int K, const void* wgt_f16x2,
+                                        int cin, int cout, const float* scale, const float* shift,
+                                        const float* residual, int relu, float* fout, int n_out,
+                                        void* stream)
+{
+    return sp_conv_wave2_f16x3(fin, nbr, n_out, nullptr, K, wgt_f16x2, cin, cout, scale, shift, residual, relu, fout, n_out, 0,
+                               stream);
+}
+
+// the same kernel on a tiled rulebook (al3d_sp_*_table_tiles): pitched table, per-tile tap masks read instead of scanned
+extern "C" int al3d_sp_conv_wave2_f16x3_tiles(const float* fin, const int* nbr, int nbr_pitch, const unsigned* tile_mask,
+                                              int K, const void* wgt_f16x2, int cin, int cout, const float* scale,
+                                              const float* shift, const float* residual, int relu, float* fout, int n_out,
+                                              void* stream)
+{
+    AL3D_REQUIRE(tile_mask && nbr_pitch >= n_out && nbr_pitch % 256 == 0,
+                 "al3d_sp_conv_wave2_f16x3_tiles: needs a tiled rulebook (pitch = al3d_sp_table_pitch(n_out), tile masks)");
+    return sp_conv_wave2_f16x3(fin, nbr, nbr_pitch, tile_mask, K, wgt_f16x2, cin, cout, scale, shift, residual, relu, fout,
+                               n_out, 0, stream);
+}
+
+// ... with the row formats of sp_rows.h: io bit 0 = input pair rows, bit 1 = write pair rows, bit 2 = residual pair rows
+extern "C" int al3d_sp_conv_wave2_f16x3_tiles_io(const float* fin, const int* nbr, int nbr_pitch, const unsigned* tile_mask,
+                                                 int K, const void* wgt_f16x2, int cin, int cout, const float* scale,
+                                                 const float* shift, const float* residual, int relu, float* fout, int n_out,
+                                                 int io, void* stream)
+{
+    AL3D_REQUIRE(tile_mask && nbr_pitch >= n_out && nbr_pitch % 256 == 0,
+                 "al3d_sp_conv_wave2_f16x3_tiles_io: needs a tiled rulebook (pitch = al3d_sp_table_pitch(n_out), tile masks)");
+    AL3D_REQUIRE(io >= 0 && io < 8 && cin % 8 == 0 && cout % 8 == 0, "al3d_sp_conv_wave2_f16x3_tiles_io: bad io flags / channels");
+    return sp_conv_wave2_f16x3(fin, nbr, nbr_pitch, tile_mask, K, wgt_f16x2, cin, cout, scale, shift, residual, relu, fout,
+                               n_out, io, stream);
 }
 
 #define SW_DISPATCH(CI, CO)                                                                           \
