@@ -635,6 +635,91 @@ def deconv2x2_nhwc(x, w_packed, scale, shift, relu, out=None, coff=0, gap=None, 
     return dense_launch("deconv2x2_nhwc", x, w_packed, scale, shift, None, relu, out, coff, gap, io)
 
 
+# ------------------------------------------------------------------ camera-only BEV decoder (csrc/conv2d_res.hip)
+# conv2 + bn2 + shortcut + ReLU of the BEV decoder's BasicBlocks under f16x3: "fused" = one launch of
+# al3d_conv3x3_res_nhwc_f16x3, "two-step" = the dense dispatch's convolution, then al3d_add_relu_nhwc_f32 (the same
+# arithmetic class; the same bits where the dispatch picks the LDS-DMA kernel).  Default two-step: measured 1.8-2.4 x faster
+# per layer and 1.3 x on the whole decoder (profiles/camera_decoder.txt); the fused launch is opt-in
+RES = _os.environ.get("AL3D_RES", "two-step")
+if RES not in ("fused", "two-step"):
+    raise lib.Al3dError(f"AL3D_RES={RES!r}: expected fused or two-step")
+
+
+def pack_res3x3(w_packed, scale=None):
+    """Packed f32 weights [Cout,9,Cin] + folded-BN scale -> (weights, scale) for ``conv3x3_res_nhwc`` under MATH: the
+    LDS-DMA images of the f16x3 split (``pack_dma_f16x3``), the plain format of the other arithmetics."""
+    if MATH == "f16x3":
+        return dense_pack("dma", w_packed, scale)
+    return dense_pack(MATH, w_packed, scale)
+
+
+def add_relu_nhwc(x, res, relu=True, out=None):
+    """relu(x + res[..., :C]) on channels-last maps (``al3d_add_relu_nhwc_f32``); res may be wider than x; out: an
+    optional [..., >= C] map whose first C channels are written (may be x)."""
+    x, res = _dev(x, torch.float32, "x"), _dev(res, torch.float32, "res")
+    C = x.shape[-1]
+    if tuple(res.shape[:-1]) != tuple(x.shape[:-1]):
+        raise lib.Al3dError(f"add_relu_nhwc: map sizes {tuple(x.shape)} / {tuple(res.shape)} do not match")
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.shape[:-1] == x.shape[:-1] and out.is_contiguous() and out.dtype == torch.float32
+    lib.call("al3d_add_relu_nhwc_f32", _ptr(x), _ptr(res), _ptr(out), x.numel() // max(C, 1), C, C, res.shape[-1],
+             out.shape[-1], 1 if relu else 0, _stream())
+    return out
+
+
+def conv3x3_res_nhwc(x, w_packed, scale, shift, res, relu=True, out=None, coff=0):
+    """out[..., coff:coff+Cout] = relu((conv3x3/s1/p1(x) * scale + shift) + res[..., :Cout]): conv2 + bn2 + shortcut + ReLU
+    of a ResNet BasicBlock.  w_packed, scale: ``pack_res3x3``'s.  f16x3 (LDS-DMA weight images): ONE launch of
+    ``al3d_conv3x3_res_nhwc_f16x3``; the other arithmetics: their convolution, then ``al3d_add_relu_nhwc_f32`` (the same
+    bits as the fused launch gives on the f16x3 weights).  A geometry the kernels do not serve raises ``Al3dError``."""
+    x = _dev(x, torch.float32, "x")
+    kind = dense_kind(w_packed)
+    B, H, W, Cin = x.shape
+    if res is not None:
+        res = _dev(res, torch.float32, "res")
+        if tuple(res.shape[:3]) != (B, H, W):
+            raise lib.Al3dError(f"conv3x3_res_nhwc: residual {tuple(res.shape)} does not match the map {tuple(x.shape)}")
+    if kind == "dma":
+        cout = w_packed.cout
+        if w_packed.taps != 9 or w_packed.cin != Cin:
+            raise lib.Al3dError(f"conv3x3_res_nhwc: weights [Cout={cout}, taps={w_packed.taps}, Cin={w_packed.cin}] do not "
+                                f"match a 3x3 layer over {Cin} channels")
+        if scale is None:
+            raise lib.Al3dError("conv3x3_res_nhwc: f16x3 weights need the scale returned by split_f16x3")
+        if out is None:
+            out = torch.empty((B, H, W, cout), dtype=torch.float32, device=x.device)
+        assert out.shape[:3] == (B, H, W) and out.is_contiguous() and out.dtype == torch.float32
+        lib.call("al3d_conv3x3_res_nhwc_f16x3", _ptr(x), _ptr(w_packed.data), _ptr(scale), _ptr(shift), _ptr(res), _ptr(out),
+                 B, H, W, Cin, cout, 0 if res is None else res.shape[3], out.shape[3], coff, 1 if relu else 0, _stream())
+        return out
+    if kind not in ("f32", "bf16x6"):
+        raise lib.Al3dError(f"conv3x3_res_nhwc: {kind!r} weights; expected pack_res3x3's (LDS-DMA images under f16x3)")
+    if res is None:
+        raise lib.Al3dError("conv3x3_res_nhwc: null residual")
+    y = conv2d_nhwc(x, w_packed, scale, shift, 3, 1, 1, False)
+    if out is None:
+        return add_relu_nhwc(y, res, relu, out=y)
+    if out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or tuple(out.shape[:3]) != (B, H, W):
+        raise lib.Al3dError(f"conv3x3_res_nhwc: out must be a contiguous float32 device map [{B},{H},{W},ldc]")
+    if coff < 0 or coff % 4 or coff + y.shape[3] > out.shape[3]:
+        raise lib.Al3dError(f"conv3x3_res_nhwc: channel window [{coff},{coff + y.shape[3]}) exceeds ldc={out.shape[3]} "
+                            "(or coff is not a multiple of 4)")
+    lib.call("al3d_add_relu_nhwc_f32", _ptr(y), _ptr(res), out.data_ptr() + 4 * coff, B * H * W, y.shape[3], y.shape[3],
+             res.shape[3], out.shape[3], 1 if relu else 0, _stream())
+    return out
+
+
+def upsample_bilinear_ac_nhwc(x, size):
+    """Bilinear resize of a channels-last map to ``size`` = (H, W), align_corners=True (``al3d_upsample_bilinear_ac_nhwc_f32``)."""
+    x = _dev(x, torch.float32, "x")
+    N, h, w, C = x.shape
+    H, W = int(size[0]), int(size[1])
+    out = torch.empty((N, H, W, C), dtype=torch.float32, device=x.device)
+    lib.call("al3d_upsample_bilinear_ac_nhwc_f32", _ptr(x), N, h, w, C, H, W, _ptr(out), _stream())
+    return out
+
+
 def gap_parts(OH, OW, deconv):
     return int(lib.load().al3d_gap_parts_count(int(OH), int(OW), 1 if deconv else 0))
 

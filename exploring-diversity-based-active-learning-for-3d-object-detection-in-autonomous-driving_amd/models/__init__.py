@@ -12,6 +12,7 @@ from .transfusion_head import TransFusionHead
 from .center_head import CenterHead, SeparateHead
 from .swin import SwinTransformer
 from .bevfusion_model import BEVFusion, BEVFusionCameraLidar
+from .bevfusion_camera_only import BEVFusionCameraOnly, GeneralizedResNet, LSSFPN, LSSTransform
 
 __all__ = ["READERS", "BACKBONES", "NECKS", "HEADS", "DETECTORS", "build_detector",
            "build_reader", "build_backbone", "build_neck", "build_head", "build_box_coder"]

@@ -857,6 +857,27 @@ int al3d_center_decode_nms_f32(const float* hout, int B, int D0, int D1, int CH,
 int al3d_conv3x3_grouped_nhwc_f32(const float* x, const float* w, const float* bias, float* out, int B, int H, int W,
                                   int G, const int* cout, const int* coff, int ldc, void* stream);
 
+/* ---------------------------------------------------------------- camera-only BEV decoder (csrc/conv2d_res.hip)
+ * The second half of a ResNet BasicBlock as one launch (GeneralizedResNet, bevfusion/mmdet3d/models/backbones/
+ * resnet.py:12-40): out[..., coff:coff+Cout] = relu((conv3x3/s1/p1(in) * scale + shift) + res), f16x3 products, f32
+ * epilogue in exactly that order.  in [B][H][W][Cin] f32; wgt_image = al3d_pack_f16x3_dma's output for taps = 9 (scale
+ * carries the split's exponent); res [B][H][W][ldr] f32 (its first Cout channels), out [B][H][W][ldc].  Cin % 16 == 0,
+ * Cout % 32 == 0, ldr >= Cout.  Bit-identical to al3d_conv2d_nhwc_f16x3_dma (relu = 0) followed by
+ * al3d_add_relu_nhwc_f32: same product order per accumulator. */
+int al3d_conv3x3_res_nhwc_f16x3(const float* in, const void* wgt_image, const float* scale, const float* shift,
+                                const float* res, float* out, int B, int H, int W, int Cin, int Cout, int ldr, int ldc,
+                                int coff, int relu, void* stream);
+/* out[p][c] = relu(x[p][c] + res[p][c]) for n_pixels rows of C channels (C % 4 == 0; row strides ldx, ldr, ldc
+ * multiples of 4, 16-byte aligned bases; relu = 0: the sum alone): the residual step behind a convolution of the other
+ * arithmetics.  out may be x. */
+int al3d_add_relu_nhwc_f32(const float* x, const float* res, float* out, int64_t n_pixels, int C, int ldx, int ldr,
+                           int ldc, int relu, void* stream);
+/* Bilinear resize of a channels-last map, align_corners = True (nn.Upsample in necks/lss.py:36-41): src [N][h][w][C]
+ * -> out [N][H][W][C], C % 4 == 0; source position o * (in - 1) / (out - 1) in f32 and the blend
+ * h0 (w0 v00 + w1 v01) + h1 (w0 v10 + w1 v11), as al3d_lss_upsample_cat_mode_f32 computes its upsampled channels. */
+int al3d_upsample_bilinear_ac_nhwc_f32(const float* src, int N, int h, int w, int C, int H, int W, float* out,
+                                       void* stream);
+
 /* ---------------------------------------------------------------- runtime
  * A HIP stream restricted to n_cus compute units starting at first_cu (hipExtStreamCreateWithCUMask); the
  * reference has no analogue (its loader workers are host processes, det3d/datasets/loader/build_loader.py:23-59):
