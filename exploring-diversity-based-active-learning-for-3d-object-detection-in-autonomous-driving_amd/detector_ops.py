@@ -720,6 +720,83 @@ def upsample_bilinear_ac_nhwc(x, size):
     return out
 
 
+def bev_grid_axis(in_scope, out_scope, size):
+    """One axis of ``BEVGridTransform`` (heads/segm/vanilla.py:69-75) on the host, in float64 -> (source indices [n, 2]
+    int32, weights [n, 2] float32, rounded once).  Output coordinate k: ``v = omin + ostep / 2 + k * ostep``, as many as
+    ``torch.arange(omin + ostep / 2, omax, ostep)`` holds (``ceil((omax - start) / ostep)`` in double, ATen's rule);
+    ``g = (v - imin) / (imax - imin) * 2 - 1``; source position ``((g + 1) * size - 1) / 2`` (``F.grid_sample``,
+    align_corners=False); neighbours ``floor(pos)`` and the next with weights ``(i0 + 1) - pos`` and ``pos - i0``.  An
+    index outside [0, size) is stored as -1 with weight 0 (zero padding)."""
+    import math
+
+    import numpy as np
+    imin, imax = float(in_scope[0]), float(in_scope[1])
+    omin, omax, ostep = float(out_scope[0]), float(out_scope[1]), float(out_scope[2])
+    start = omin + ostep / 2
+    n = max(0, int(math.ceil((omax - start) / ostep)))
+    v = start + np.arange(n, dtype=np.float64) * ostep
+    g = (v - imin) / (imax - imin) * 2 - 1
+    pos = ((g + 1) * size - 1) / 2
+    i0 = np.floor(pos)
+    idx = np.stack([i0, i0 + 1], axis=1)
+    wgt = np.stack([(i0 + 1) - pos, pos - i0], axis=1)
+    outside = (idx < 0) | (idx >= size)
+    idx[outside], wgt[outside] = -1, 0.0
+    return idx.astype(np.int32), wgt.astype(np.float32)
+
+
+_GRID_TABLES = {}
+
+
+def bev_grid_tables(input_scope, output_scope, in_hw, device):
+    """The four device tables of ``al3d_bev_grid_resample_nhwc_f32`` for a source map of ``in_hw`` = (rows, columns) whose
+    rows run along scope 0 and columns along scope 1; kept per device, scopes and size."""
+    key = (torch.device(device), tuple(map(tuple, input_scope)), tuple(map(tuple, output_scope)), tuple(in_hw))
+    if key not in _GRID_TABLES:
+        tabs = []
+        for i_s, o_s, size in zip(input_scope, output_scope, in_hw):
+            idx, wgt = bev_grid_axis(i_s, o_s, int(size))
+            if len(idx) == 0:
+                raise lib.Al3dError(f"bev_grid_tables: the output scope {tuple(o_s)} holds no sample")
+            tabs += [torch.from_numpy(idx).to(device), torch.from_numpy(wgt).to(device)]
+        _GRID_TABLES[key] = tuple(tabs)
+    return _GRID_TABLES[key]
+
+
+def bev_grid_resample_nhwc(x, input_scope, output_scope, out_hw_swapped=False):
+    """``BEVGridTransform.forward`` on a channels-last map [N, h, w, C] whose rows run along scope 0 and columns along
+    scope 1 -> [N, H, W, C] (``al3d_bev_grid_resample_nhwc_f32``); ``out_hw_swapped``: -> [N, W, H, C], written
+    transposed by the same launch."""
+    x = _dev(x, torch.float32, "x")
+    N, h, w, C = x.shape
+    ri, rw, ci, cw = bev_grid_tables(input_scope, output_scope, (h, w), x.device)
+    H, W = ri.shape[0], ci.shape[0]
+    out = torch.empty((N, W, H, C) if out_hw_swapped else (N, H, W, C), dtype=torch.float32, device=x.device)
+    lib.call("al3d_bev_grid_resample_nhwc_f32", _ptr(x), N, h, w, C, _ptr(ri), _ptr(rw), _ptr(ci), _ptr(cw), H, W,
+             1 if out_hw_swapped else 0, _ptr(out), _stream())
+    return out
+
+
+def seg_classify(x, weight, bias, with_stats=False):
+    """sigmoid(Conv2d(C, K, 1)) of a channels-last map [N, H, W, C] with weight [K, C] and bias [K] -> probabilities
+    [N, K, H, W] (``al3d_seg_classify_f32``); ``with_stats``: also (entropy_sum [N, K] float32 -- the binary entropy summed
+    over the pixels -- and area [N, K] int32 -- the pixels with p > 0.5)."""
+    x, weight, bias = _dev(x, torch.float32, "x"), _dev(weight, torch.float32, "weight"), _dev(bias, torch.float32, "bias")
+    N, H, W, C = x.shape
+    K = weight.shape[0]
+    if tuple(weight.shape) != (K, C) or tuple(bias.shape) != (K,):
+        raise lib.Al3dError(f"seg_classify: weight {tuple(weight.shape)} / bias {tuple(bias.shape)} do not match C={C}")
+    prob = torch.empty((N, K, H, W), dtype=torch.float32, device=x.device)
+    ent = area = ws = None
+    if with_stats:
+        ent = torch.empty((N, K), dtype=torch.float32, device=x.device)
+        area = torch.empty((N, K), dtype=torch.int32, device=x.device)
+        ws = torch.empty(max(1, int(lib.load().al3d_seg_classify_workspace_bytes(N, H, W))), dtype=torch.uint8, device=x.device)
+    lib.call("al3d_seg_classify_f32", _ptr(x), _ptr(weight), _ptr(bias), N, H, W, C, K, _ptr(prob), _ptr(ent), _ptr(area),
+             _ptr(ws), _stream())
+    return (prob, ent, area) if with_stats else prob
+
+
 def gap_parts(OH, OW, deconv):
     return int(lib.load().al3d_gap_parts_count(int(OH), int(OW), 1 if deconv else 0))
 

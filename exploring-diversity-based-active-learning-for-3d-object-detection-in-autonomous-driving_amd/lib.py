@@ -200,6 +200,10 @@ SIGNATURES = {
     "al3d_conv3x3_res_nhwc_f16x3": (c_int, [c_p, c_p, c_p, c_p, c_p, c_p] + [c_int] * 9 + [c_p]),
     "al3d_add_relu_nhwc_f32": (c_int, [c_p, c_p, c_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_p]),
     "al3d_upsample_bilinear_ac_nhwc_f32": (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_p, c_p]),
+    "al3d_bev_grid_resample_nhwc_f32": (c_int, [c_p, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_p,
+                                               c_p]),
+    "al3d_seg_classify_workspace_bytes": (c_i64, [c_int, c_int, c_int]),
+    "al3d_seg_classify_f32": (c_int, [c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p]),
     "al3d_pack_f16x3_wino": (c_int, [c_p, c_int, c_int, c_p, c_p]),
     "al3d_conv3x3_nhwc_f16x3_wino": (c_int, [c_p, c_p, c_p, c_p, c_p] + [c_int] * 9 + [c_p]),
     "al3d_tok_patch_rows_f32": (c_int, [c_p, c_int, c_int, c_int, c_int, c_p, c_p]),

@@ -13,6 +13,7 @@ from .center_head import CenterHead, SeparateHead
 from .swin import SwinTransformer
 from .bevfusion_model import BEVFusion, BEVFusionCameraLidar
 from .bevfusion_camera_only import BEVFusionCameraOnly, GeneralizedResNet, LSSFPN, LSSTransform
+from .bev_seg_head import BEVGridTransform, BEVSegmentationHead
 
 __all__ = ["READERS", "BACKBONES", "NECKS", "HEADS", "DETECTORS", "build_detector",
            "build_reader", "build_backbone", "build_neck", "build_head", "build_box_coder"]

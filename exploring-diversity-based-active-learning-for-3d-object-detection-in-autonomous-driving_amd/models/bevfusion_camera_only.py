@@ -218,12 +218,16 @@ class BEVFusionCameraOnly(nn.Module):
     """The camera-only model behind the det3d detector contract (same contract as ``BEVFusion.forward``).
 
     ``BEVFusionCameraOnly(camera=dict(backbone=..., neck=..., vtransform=...), decoder=dict(backbone=..., neck=...),
-    bbox_head=<CenterHead cfg or None>)``; ``detector(example, return_loss=False, estimate=True)`` ->
+    bbox_head=<CenterHead cfg or None>, map_head=<BEVSegmentationHead cfg or None>)``;
+    ``detector(example, return_loss=False, estimate=True)`` ->
     ``(list[dict(box3d_lidar, scores, label_preds, metadata)], [middle])`` with ``middle[-1]`` the decoder neck's map
     ([B, C, x, y]-shaped view) and its global average the embedding.  ``example``: the batch of
-    ``CameraLidarSweepLoader`` / ``CameraLidarFileLoader``; its lidar keys are not read."""
+    ``CameraLidarSweepLoader`` / ``CameraLidarFileLoader``; its lidar keys are not read.  With a ``map_head``
+    (``heads.map.*``, the reference's seg models) every output dict also holds ``masks_bev`` [K, X, Y] (probabilities),
+    ``map_entropy`` [K] (mean binary entropy per class) and ``map_area`` [K] (cells above 0.5), and the plain
+    ``return_loss=False`` call works without a ``bbox_head``."""
 
-    def __init__(self, camera, decoder, bbox_head=None, train_cfg=None, test_cfg=None, pretrained=None):
+    def __init__(self, camera, decoder, bbox_head=None, train_cfg=None, test_cfg=None, pretrained=None, map_head=None):
         super().__init__()
         vt = camera["vtransform"]
         self.encoders = nn.ModuleDict(dict(camera=nn.ModuleDict(dict(
@@ -235,12 +239,18 @@ class BEVFusionCameraOnly(nn.Module):
             neck=builder.build_neck(decoder["neck"]) if isinstance(decoder["neck"], dict) else decoder["neck"]))
         head = builder.build_head(bbox_head) if isinstance(bbox_head, dict) else bbox_head
         self.heads = nn.ModuleDict({} if head is None else dict(object=head))
+        if map_head is not None:
+            self.heads["map"] = builder.build_head(map_head) if isinstance(map_head, dict) else map_head
         self.train_cfg, self.test_cfg = train_cfg, test_cfg
         self.stage_ms = None
 
     @property
     def bbox_head(self):
         return self.heads["object"] if "object" in self.heads else None
+
+    @property
+    def map_head(self):
+        return self.heads["map"] if "map" in self.heads else None
 
     def prepare(self, example):
         """No index work to run ahead: there is no sparse encoder."""
@@ -292,14 +302,18 @@ class BEVFusionCameraOnly(nn.Module):
         from .detectors import NHWCFeature
         emb, dec, preds = self._run(example, timed=kwargs.get("timed", False))
         metas = example.get("metadata", None) or [None] * dec.shape[0]
-        head = self.bbox_head
+        head, map_head = self.bbox_head, self.map_head
         if head is None:
-            if not kwargs.get("estimate", False):
+            if map_head is None and not kwargs.get("estimate", False):
                 raise RuntimeError("this detector was built without a bbox_head: only the estimate=True embedding sweep "
                                    "is available")
             out = [dict(metadata=m) for m in metas]
         else:
             out = head.predict(example, preds, self.test_cfg)
+        if map_head is not None:
+            prob, ent, area = map_head(dec, with_stats=True)
+            for i, o in enumerate(out):
+                o.update(masks_bev=prob[i], map_entropy=ent[i], map_area=area[i])
         if kwargs.get("estimate", False):
             return out, [NHWCFeature(dec, emb)]
         return out

@@ -136,11 +136,15 @@ class BEVFusion(BEVFusionCameraLidar):
     the lidar batch of ``DeviceSweepLoader`` plus the camera side (``CAMERA_KEYS``: channels-last images ``[B,N,H,W,3]``,
     per-sample point clouds, the 4 x 4 calibration / augmentation matrices; ``al3d.datasets.CameraLidarSweepLoader``)."""
 
-    def __init__(self, lidar, bbox_head=None, train_cfg=None, test_cfg=None, pretrained=None, **kwargs):
+    def __init__(self, lidar, bbox_head=None, train_cfg=None, test_cfg=None, pretrained=None, map_head=None, **kwargs):
         lidar_det = builder.build_detector(lidar, train_cfg=train_cfg, test_cfg=test_cfg) if isinstance(lidar, dict) else lidar
         head = builder.build_head(bbox_head) if isinstance(bbox_head, dict) else bbox_head
         super().__init__(lidar_det, head=head, **kwargs)
         self.train_cfg, self.test_cfg = train_cfg, test_cfg
+        # the reference's ``heads.map.*`` (seg/fusion-bev256d2-lss.yaml); the decoder map here is [H = y, W = x], so the head
+        # is built with transpose_input=True.  Without a map head the module tree is what it was
+        if map_head is not None:
+            self.heads = nn.ModuleDict(dict(map=builder.build_head(map_head) if isinstance(map_head, dict) else map_head))
 
     @property
     def bbox_head(self):
@@ -161,13 +165,18 @@ class BEVFusion(BEVFusionCameraLidar):
                                     example["camera_intrinsics"], example["camera2lidar"], example["img_aug_matrix"],
                                     example["lidar_aug_matrix"], book=book)
         metas = example.get("metadata", None) or [None] * dec.shape[0]
+        map_head = self.heads["map"] if "heads" in self._modules else None
         if self.head is None:
-            if not kwargs.get("estimate", False):
+            if map_head is None and not kwargs.get("estimate", False):
                 raise RuntimeError("this detector was built without a bbox_head: only the estimate=True embedding sweep "
                                    "is available")
             out = [dict(metadata=m) for m in metas]
         else:
             out = self.head.predict(example, preds, self.test_cfg)
+        if map_head is not None:
+            prob, ent, area = map_head(dec, with_stats=True)
+            for i, o in enumerate(out):
+                o.update(masks_bev=prob[i], map_entropy=ent[i], map_area=area[i])
         if kwargs.get("estimate", False):
             return out, [NHWCFeature(dec, emb)]
         return out

@@ -878,6 +878,31 @@ int al3d_add_relu_nhwc_f32(const float* x, const float* res, float* out, int64_t
 int al3d_upsample_bilinear_ac_nhwc_f32(const float* src, int N, int h, int w, int C, int H, int W, float* out,
                                        void* stream);
 
+/* ---------------------------------------------------------------- BEV map segmentation head (csrc/bev_seg.hip)
+ * BEVGridTransform.forward (bevfusion/mmdet3d/models/heads/segm/vanilla.py:60-87): F.grid_sample(bilinear, padding zeros,
+ * align_corners = False) on the axis-aligned grid of lines 69-79, which is a meshgrid of two coordinate vectors: the
+ * sample is separable and the host supplies it as tables.  src [N][h][w][C] -> out [N][H][W][C] f32, C % 4 == 0, 16-byte
+ * aligned bases.  row_idx [H][2] int32 / row_w [H][2] f32: the two source rows of an output row and their weights;
+ * col_idx [W][2] / col_w [W][2] likewise for columns (device memory, 8-byte aligned; H, N <= 65535).  An index outside [0, size) contributes zero
+ * whatever the map holds.  Blend, each operation rounded to f32: r0 (c0 v00 + c1 v01) + r1 (c0 v10 + c1 v11), v_ij = src[row i][col j].
+ * out_hw_swapped = 1: the pixel (row y, column x) is written to out [N][W][H][C] at [x][y] -- a map stored [y, x] is
+ * resampled straight into [x, y]. */
+int al3d_bev_grid_resample_nhwc_f32(const float* src, int N, int h, int w, int C, const int* row_idx,
+                                    const float* row_w, const int* col_idx, const float* col_w, int H, int W,
+                                    int out_hw_swapped, float* out, void* stream);
+/* The classifier's last layer and the head's return value (vanilla.py:112, 124, 138): prob [N][K][H][W] =
+ * sigmoid(Conv2d(C, K, 1)(in) + b), in [N][H][W][C] f32, w [K][C], b [K], 1 <= K <= 16, C % 4 == 0, in and w 16-byte
+ * aligned, 512 + 4 * Kp * (C + 256) <= 65536 with Kp = K rounded up to 4, 8 or 16 (LDS).  Logit: eight f32 FMA chains per
+ * pixel and class -- chain q over the channel quads q, q + 8, ... in ascending channel order from 0 -- added as
+ * ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7)), then + b; p = 1 / (1 + expf(-z)).  Optional (null = skipped; either
+ * one needs workspace): entropy_sum [N][K] = sum over pixels of -(p logf(p) + (1 - p) logf(1 - p)), a pixel's term exactly
+ * 0 where p is 0 or 1; area [N][K] int32 = pixels with p > 0.5.  The sums run in a fixed order (64-pixel butterfly, four
+ * waves, the 256-pixel workgroups in 16 interleaved ascending runs): two calls give the same bits.  No analogue in the reference: the acquisition
+ * functions consume them. */
+int64_t al3d_seg_classify_workspace_bytes(int N, int H, int W);
+int al3d_seg_classify_f32(const float* in, const float* w, const float* b, int N, int H, int W, int C, int K,
+                          float* prob, float* entropy_sum, int* area, void* workspace, void* stream);
+
 /* ---------------------------------------------------------------- runtime
  * A HIP stream restricted to n_cus compute units starting at first_cu (hipExtStreamCreateWithCUMask); the
  * reference has no analogue (its loader workers are host processes, det3d/datasets/loader/build_loader.py:23-59):
