@@ -98,6 +98,11 @@ struct ConvF3Params {
     int gap_parts;
     int xmap = f3_knobs().xmap;    // workgroup -> (pixel tile, column block) order, see f3_tile_of_block
     int io = 0;             // row formats of in / out (sp_rows.h: bit 0 = in pair pixels, bit 1 = write pair pixels); DMA kernel only
+    // conv3x3_f16x3_frag_kernel, SRC = 1: the input map is given as sparse rows.  rows [n][rows_pitch] f32 (C = Cin / 2
+    // channels used), bev [B,H,W,2] i32 = row of (pixel, z) or -1 (al3d_sp_bev_index); map channel c * 2 + z = rows[row][c]
+    const float* rows = nullptr;
+    const int* bev = nullptr;
+    int rows_pitch = 0;
 };
 
 // 1-D grid -> (pixel tile, column block).  Blocks with equal blockIdx % 8 share an XCD and its L2,
@@ -554,9 +559,16 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_halo_kernel(ConvF3Params
 // SHAPE 1 (round 5): a wave owns all FOUR image rows of the tile x ONE 32-channel tile instead of two rows x two tiles, so
 // every weight fragment is loaded by exactly one wave of the workgroup (half the L2 -> CU weight traffic: 11.5 instead of
 // 23 TB/s chip-wide on the 256 -> 256 layers) at twice the LDS fragment reads; same MFMA sequence per accumulator.
-template <int IO = 0, int SHAPE = 0>
+// SRC 1 (SHAPE 2 only): the input map is the sparse encoder's last level, read from its rows through a BEV row index
+// (p.rows, p.bev) instead of from a dense map that is 3/4 zeros.  A 16-byte halo piece {r0[c], r1[c], r0[c+1], r1[c+1]} is
+// two 8-byte loads from the pixel's two rows (z = 0, 1), a missing row reads the zero block; the LDS image is the one the
+// dense map gives.  The workgroup also knows which of its six halo rows are entirely empty and skips the MFMAs whose A
+// operand is such a row: they would add products of +0 to the accumulator, which leaves every accumulator (+0 at the
+// start, or already non-zero) bit for bit as it was.
+template <int IO = 0, int SHAPE = 0, int SRC = 0>
 __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_frag_kernel(ConvF3Params p)
 {
+    static_assert(SRC == 0 || SHAPE == 2, "the rows input is built for wave shape 2 only");
     constexpr int NI = SHAPE ? 4 : 2, NJ = SHAPE ? 1 : 2;      // M tiles (image rows) x N tiles (32 channels) per wave
     constexpr bool HALO_FAR = SHAPE == 2;
     constexpr int NHB = 2;                                    // halo buffers (a third one, dropping the tap-1 barrier, measured a tie)
@@ -582,15 +594,45 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_frag_kernel(ConvF3Params
     // between its request and its store (two before: a step apart is ~1.5k cycles of wall time at two waves per SIMD, less than
     // an HBM round trip under load, and vmcnt retires in order, so the wait also held the weight stream back)
     float4 rh[HALO_FAR ? 4 : 2];
+    int2 hrow[SRC ? 4 : 1];                                   // SRC 1: the rows (z = 0, 1) of this thread's four halo pixels
+    unsigned live = 0x3f;                                     // SRC 1: bit r = halo row r holds a row (wave-uniform)
+    if constexpr (SRC != 0) {
+        __shared__ unsigned live_s;
+        if (tid == 0) live_s = 0;
+        unsigned mine = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int hp = (tid + 256 * k) >> 2;
+            const int iy = y0 + hp / G3_HW, ix = x0 + hp % G3_HW;
+            const bool ok = hp < G3_HP && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
+            const int* src = p.bev + (((int64_t)b * p.H + iy) * p.W + ix) * 2;
+            hrow[k] = ok ? *reinterpret_cast<const int2*>(src) : make_int2(-1, -1);
+            if (hrow[k].x >= 0 || hrow[k].y >= 0) mine |= 1u << (hp / G3_HW);
+        }
+        __syncthreads();
+        if (mine) atomicOr(&live_s, mine);
+        __syncthreads();
+        live = __builtin_amdgcn_readfirstlane(live_s);
+    }
     auto load_halo = [&](int chunk, int half) {
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             const int piece = tid + 256 * (2 * half + k);
             const int hp = piece >> 2, q = piece & 3;
-            const int iy = y0 + hp / G3_HW, ix = x0 + hp % G3_HW;
-            const bool ok = hp < G3_HP && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-            const float* src = p.in + (((int64_t)b * p.H + iy) * p.W + ix) * p.Cin + chunk * F3_BK + 4 * q;
-            rh[(HALO_FAR ? 2 * half : 0) + k] = *reinterpret_cast<const float4*>(ok ? src : zero);
+            if constexpr (SRC != 0) {
+                const int2 r = hrow[2 * half + k];
+                const int c0 = chunk * (F3_BK / 2) + 2 * q;
+                const float* s0 = p.rows + (int64_t)r.x * p.rows_pitch + c0;
+                const float* s1 = p.rows + (int64_t)r.y * p.rows_pitch + c0;
+                const float2 a0 = *reinterpret_cast<const float2*>(r.x >= 0 ? s0 : zero);
+                const float2 a1 = *reinterpret_cast<const float2*>(r.y >= 0 ? s1 : zero);
+                rh[(HALO_FAR ? 2 * half : 0) + k] = make_float4(a0.x, a1.x, a0.y, a1.y);
+            } else {
+                const int iy = y0 + hp / G3_HW, ix = x0 + hp % G3_HW;
+                const bool ok = hp < G3_HP && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
+                const float* src = p.in + (((int64_t)b * p.H + iy) * p.W + ix) * p.Cin + chunk * F3_BK + 4 * q;
+                rh[(HALO_FAR ? 2 * half : 0) + k] = *reinterpret_cast<const float4*>(ok ? src : zero);
+            }
         }
     };
     auto store_halo = [&](int buf, int half) {
@@ -647,10 +689,32 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_frag_kernel(ConvF3Params
             fa[set][pl][t] = *reinterpret_cast<const f16x8*>(
                 &Ah[hbuf][pl][a_off + ((t + ky) * G3_HW + kx) * F3_LDB]);
     };
-    auto mfma_step = [&](int set, const f16x8 (&fb)[2][NJ], auto&& between0, auto&& between1) {
+    auto mfma_step = [&](int set, auto ky_, const f16x8 (&fb)[2][NJ], auto&& between0, auto&& between1) {
         f16x8 wd[NJ];
 #pragma unroll
         for (int j = 0; j < NJ; ++j) wd[j] = lift_down(fb[0][j]);
+        if constexpr (SRC != 0) {
+            // the same three products per accumulator in the same order; image row i at tap row ky reads halo row i + ky
+            constexpr int ky = decltype(ky_)::value;
+#pragma unroll
+            for (int i = 0; i < NI; ++i)
+                if ((live >> (row0 + i + ky)) & 1)
+#pragma unroll
+                    for (int j = 0; j < NJ; ++j) acc[i][j] = F3_MFMA(fa[set][1][i], wd[j], acc[i][j]);
+            between0();
+#pragma unroll
+            for (int i = 0; i < NI; ++i)
+                if ((live >> (row0 + i + ky)) & 1)
+#pragma unroll
+                    for (int j = 0; j < NJ; ++j) acc[i][j] = F3_MFMA(fa[set][0][i], fb[1][j], acc[i][j]);
+#pragma unroll
+            for (int i = 0; i < NI; ++i)
+                if ((live >> (row0 + i + ky)) & 1)
+#pragma unroll
+                    for (int j = 0; j < NJ; ++j) acc[i][j] = F3_MFMA(fa[set][0][i], fb[0][j], acc[i][j]);
+            between1();
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < NI; ++i)
 #pragma unroll
@@ -692,9 +756,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_frag_kernel(ConvF3Params
         const int nh = tap < 8 ? hb : hbn;
         auto b0 = [&]() { read_a(q ^ 1, 1, nh, nt); };
         auto b1 = [&]() { read_a(q ^ 1, 0, nh, nt); };
-        if constexpr (ring == 0) mfma_step(q, fb0, b0, b1);
-        else if constexpr (ring == 1) mfma_step(q, fb1, b0, b1);
-        else mfma_step(q, fb2, b0, b1);
+        if constexpr (ring == 0) mfma_step(q, F3_IC(tap / 3), fb0, b0, b1);
+        else if constexpr (ring == 1) mfma_step(q, F3_IC(tap / 3), fb1, b0, b1);
+        else mfma_step(q, F3_IC(tap / 3), fb2, b0, b1);
         if (tap == (HALO_FAR ? 4 : 2)) store_halo(hbn, 0);
         if (tap == 5) store_halo(hbn, 1);
         // tap 1: every wave is past the previous chunk's tap 7, the last reader of halo buffer cp^1,
@@ -710,7 +774,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_frag_kernel(ConvF3Params
         step(cp_, F3_IC(3), chunk, cn, hb, hbn); step(cp_, F3_IC(4), chunk, cn, hb, hbn); step(cp_, F3_IC(5), chunk, cn, hb, hbn);
         step(cp_, F3_IC(6), chunk, cn, hb, hbn); step(cp_, F3_IC(7), chunk, cn, hb, hbn); step(cp_, F3_IC(8), chunk, cn, hb, hbn);
     };
-    for (int chunk0 = 0; chunk0 < nchunks; chunk0 += 2) {       // nchunks is even (checked by the launcher)
+    // (SRC 1: a workgroup whose whole halo is empty has nothing to add to its zero accumulators)
+    for (int chunk0 = SRC != 0 && live == 0 ? nchunks : 0; chunk0 < nchunks; chunk0 += 2) {       // nchunks is even (checked by the launcher)
         chunk_body(F3_IC(0), chunk0);
         chunk_body(F3_IC(1), chunk0 + 1);
     }
@@ -1321,8 +1386,10 @@ extern "C" int al3d_conv3x3_nhwc_f16x3_frag16(const float* in, const void* wgt_f
 // 4 / 5); 1 = the same wave shape with the halves sharing two registers (requested at 0 / 3, stored at 2 / 5); 0 = round 1's
 // two rows x two tiles (AL3D_FRAG_SHAPE=0|1 for A/B).  Same bits; the nine `<0>` launches of the neck: 1,670 (shape 0) ->
 // 1,607 (1) -> 1,597 us (2) on one box
+// bev != null: `in` is the sparse rows [n][rows_pitch] of the map and bev its row index (SRC 1; wave shape 2 only)
 static int conv3x3_frag_impl(const float* in, const void* wgt_frag, const float* scale, const float* shift, float* out,
-                             int B, int H, int W, int Cin, int Cout, int ldc, int coff, int relu, int io, void* stream)
+                             int B, int H, int W, int Cin, int Cout, int ldc, int coff, int relu, int io, void* stream,
+                             const int* bev = nullptr, int rows_pitch = 0)
 {
     const bool vec_ok = ldc % 4 == 0 && coff % 4 == 0 && ((uintptr_t)out & 15) == 0;
     const int epi = (io & SP_IO_OUT_PAIR) ? 2 : (f3_knobs().frag_direct || !vec_ok) ? 1 : 0;
@@ -1330,6 +1397,15 @@ static int conv3x3_frag_impl(const float* in, const void* wgt_frag, const float*
     return convf3_launch("al3d_conv3x3_nhwc_f16x3_frag", "conv3x3_f16x3_frag_kernel", F3_FAM_FRAG, in, wgt_frag, scale, shift,
                          out, B, H, W, Cin, Cout, 3, 1, 1, false, ldc, coff, relu, nullptr, 0, 0,
                          [&](const ConvF3Params& p, dim3 grid) {
+        if (bev) {
+            ConvF3Params r = p;
+            r.rows = in; r.bev = bev; r.rows_pitch = rows_pitch;
+            f3_switch<2, 1, 0>(epi, [&](auto epi_) {
+                hipLaunchKernelGGL((conv3x3_f16x3_frag_kernel<decltype(epi_)::value, 2, 1>), grid, dim3(256), 0,
+                                   (hipStream_t)stream, r);
+            });
+            return;
+        }
         f3_switch<2, 1, 0>(shape, [&](auto shape_) { f3_switch<2, 1, 0>(epi, [&](auto epi_) {
             hipLaunchKernelGGL((conv3x3_f16x3_frag_kernel<decltype(epi_)::value, decltype(shape_)::value>), grid, dim3(256), 0,
                                (hipStream_t)stream, p);
@@ -1352,6 +1428,22 @@ extern "C" int al3d_conv3x3_nhwc_f16x3_frag_io(const float* in, const void* wgt_
     AL3D_REQUIRE(io == 0 || (io == 2 && ldc % 8 == 0 && coff % 8 == 0),
                  "al3d_conv3x3_nhwc_f16x3_frag_io: io must be 0 or 2 (pair output; ldc, coff multiples of 8)");
     return conv3x3_frag_impl(in, wgt_frag, scale, shift, out, B, H, W, Cin, Cout, ldc, coff, relu, io, stream);
+}
+
+// ... reading the map from the sparse encoder's last level (D = 2) instead of a dense tensor: rows [n][rows_pitch] f32 and
+// their BEV index bev [B,H,W,2] i32 (al3d_sp_bev_index; -1 = no row); map channel c * 2 + z = rows[bev[b][y][x][z]][c],
+// Cin = 2 * (channels per row).  The same bits as the call above on the dense map
+extern "C" int al3d_conv3x3_nhwc_f16x3_frag_rows(const float* rows, int rows_pitch, const int* bev, const void* wgt_frag,
+                                                 const float* scale, const float* shift, float* out, int B, int H, int W,
+                                                 int Cin, int Cout, int ldc, int coff, int relu, int io, void* stream)
+{
+    AL3D_REQUIRE(io == 0 || (io == 2 && ldc % 8 == 0 && coff % 8 == 0),
+                 "al3d_conv3x3_nhwc_f16x3_frag_rows: io must be 0 or 2 (pair output; ldc, coff multiples of 8)");
+    AL3D_REQUIRE(bev && ((uintptr_t)bev & 7) == 0, "al3d_conv3x3_nhwc_f16x3_frag_rows: bev must be non-null and 8-byte aligned");
+    AL3D_REQUIRE(Cin >= 2 && rows_pitch >= Cin / 2 && rows_pitch % 2 == 0,
+                 "al3d_conv3x3_nhwc_f16x3_frag_rows: rows_pitch=%d must be even and at least Cin/2=%d", rows_pitch, Cin / 2);
+    AL3D_REQUIRE(f3_knobs().frag_shape == 2, "al3d_conv3x3_nhwc_f16x3_frag_rows: built for AL3D_FRAG_SHAPE=2 only");
+    return conv3x3_frag_impl(rows, wgt_frag, scale, shift, out, B, H, W, Cin, Cout, ldc, coff, relu, io, stream, bev, rows_pitch);
 }
 
 // one-off weight split: f32 [count] * 2^sexp -> f16 [2][count] (wh, wl)

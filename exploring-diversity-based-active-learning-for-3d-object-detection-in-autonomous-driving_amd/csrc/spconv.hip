@@ -535,6 +535,19 @@ __global__ void sp_to_dense_nhwc_kernel(const float* __restrict__ feat, const in
     out[((((int64_t)q[0] * g.H + q[2]) * g.W + q[3]) * C + c) * g.D + q[1]] = feat[e];
 }
 
+// BEV row index of the encoder's last level (D = 2): idx[b][y][x][z] = row, for the dense neck's first 3x3 to read the
+// sparse rows in place of the dense map above (conv3x3_f16x3_frag_kernel, SRC = 1).  `idx` is pre-filled with -1; the rows
+// of one level have distinct coordinates, so no two threads write the same word.
+__global__ void sp_bev_index_kernel(const int* __restrict__ coords, int n, SpDims g, int* __restrict__ idx)
+{
+    const int row = blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= n) return;
+    const int* q = coords + 4 * (int64_t)row;
+    if ((unsigned)q[0] >= (unsigned)g.B || (unsigned)q[1] >= (unsigned)g.D || (unsigned)q[2] >= (unsigned)g.H ||
+        (unsigned)q[3] >= (unsigned)g.W) return;
+    idx[((((int64_t)q[0] * g.H + q[2]) * g.W + q[3])) * g.D + q[1]] = row;
+}
+
 // ------------------------------------------------------------------ C ABI
 static inline unsigned blocks_for(int64_t n, int per) { return (unsigned)al3d_cdiv(n > 0 ? n : 1, per); }
 
@@ -744,6 +757,18 @@ extern "C" int al3d_sp_conv_f32(const float* fin, const int* nbr, int K, const f
     SP_DISPATCH(5, 16) SP_DISPATCH(4, 16) SP_DISPATCH(16, 16) SP_DISPATCH(16, 32) SP_DISPATCH(32, 32)
     SP_DISPATCH(32, 64) SP_DISPATCH(64, 64) SP_DISPATCH(64, 128) SP_DISPATCH(128, 128)
     return al3d_fail(AL3D_EINVAL, "al3d_sp_conv_f32: unsupported channel pair %d -> %d", cin, cout);
+}
+
+extern "C" int al3d_sp_bev_index(const int* coords, int n, int B, int D, int H, int W, int* idx, void* stream)
+{
+    AL3D_REQUIRE(D == 2, "al3d_sp_bev_index: built for two z levels (got D=%d)", D);
+    AL3D_REQUIRE(n >= 0 && B >= 1 && H >= 1 && W >= 1 && idx, "al3d_sp_bev_index: bad arguments");
+    if (n == 0) return AL3D_OK;
+    AL3D_REQUIRE(coords, "al3d_sp_bev_index: null coords");
+    SpDims g = {B, D, H, W};
+    hipLaunchKernelGGL(sp_bev_index_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, coords, n, g, idx);
+    AL3D_CHECK_LAUNCH("sp_bev_index_kernel");
+    return AL3D_OK;
 }
 
 extern "C" int al3d_sp_to_dense_nhwc(const float* feat, const int* coords, int n, int C, int B, int D,

@@ -201,6 +201,47 @@ SPROWS = _os.environ.get("AL3D_SPROWS", "pair")
 # deblocks, concat map -> fused head): "pair" | "f32"
 DPIX = _os.environ.get("AL3D_DPIX", "pair")
 IO_IN_PAIR, IO_OUT_PAIR, IO_RES_PAIR = 1, 2, 4
+# what the sparse encoder hands the dense neck: "rows" = its last level's rows + a BEV row index (BevRows; the neck's
+# first 3x3 reads them in place and skips its empty halo rows), where neck_rows_ok allows it; "dense" = always the
+# zero-filled [B,H,W,C*D] map.  The same bits
+NECK_IN = _os.environ.get("AL3D_NECK_IN", "rows")
+if NECK_IN not in ("rows", "dense"):
+    raise lib.Al3dError(f"AL3D_NECK_IN={NECK_IN!r}: expected rows or dense")
+
+
+def neck_rows_ok(kind, depth=2, channels=8):
+    """May the neck's first conv (dense structure ``kind``) read the encoder's last level (``depth`` z levels of
+    ``channels``-wide rows) as BevRows?  Only the streamed 3x3 f16x3 kernel has the rows input, for two z levels."""
+    return NECK_IN == "rows" and MATH == "f16x3" and kind == "frag3x3" and depth == 2 and channels % 8 == 0
+
+
+class BevRows:
+    """The sparse encoder's last level in place of its dense BEV map: ``rows`` [n, C] f32, ``coords`` [n, 4] i32
+    (b, z, y, x), ``index`` [B, H, W, D] i32 (row of (pixel, z), -1 = none; ``bev_index``).  ``shape`` is the map's,
+    (B, H, W, C*D) with channel = c*D + z; ``dense()`` materialises it.  ``conv2d_nhwc`` takes it where
+    ``neck_rows_ok`` holds."""
+
+    def __init__(self, rows, coords, index):
+        self.rows, self.coords, self.index = rows, coords, index
+        B, H, W, Dz = index.shape
+        self.shape = (B, H, W, rows.shape[1] * Dz)
+        self.device = rows.device
+
+    def dense(self):
+        B, H, W, Dz = self.index.shape
+        out = torch.zeros(self.shape, dtype=torch.float32, device=self.device)
+        lib.call("al3d_sp_to_dense_nhwc", _ptr(self.rows), _ptr(self.coords), self.rows.shape[0], self.rows.shape[1],
+                 B, Dz, H, W, _ptr(out), _stream())
+        return out
+
+
+def bev_index(coords, n, batch_size, shape):
+    """[B, H, W, D] i32 row index of a level's n rows (coords [n, 4] i32; shape = (D, H, W), D = 2)."""
+    Dz, H, W = (int(s) for s in shape)
+    idx = torch.empty((batch_size, H, W, Dz), dtype=torch.int32, device=coords.device)
+    lib.call("al3d_sp_fill_i32", _ptr(idx), idx.numel(), -1, _stream())
+    lib.call("al3d_sp_bev_index", _ptr(coords), n, batch_size, Dz, H, W, _ptr(idx), _stream())
+    return idx
 
 
 def rows_convert(x, to_pair):
@@ -591,9 +632,18 @@ def dense_launch(who, x, w_packed, scale, shift, geom, relu, out=None, coff=0, g
     conv (geom None) of x [B,H,W,Cin], * scale + shift (ReLU).  w_packed, scale: dense_pack's.  out: optional
     [B,OH,OW,ldc] map.  gap: optional [B, parts, ldc] f32 buffer (parts = gap_parts): the launch also writes its
     workgroups' channel sums there (see gap_fusable).  io: IO_* flags (pair pixels)."""
-    x = _dev(x, torch.float32, "x")
     kind = dense_kind(w_packed)
     row = DENSE_KINDS[kind]
+    bev = x if isinstance(x, BevRows) else None
+    if bev is not None:
+        if geom is None or not neck_rows_ok(kind, bev.index.shape[3], bev.rows.shape[1]):
+            raise lib.Al3dError(f"{who}: BevRows input needs the frag3x3 structure under f16x3, two z levels and "
+                                f"AL3D_NECK_IN=rows (got {kind!r}); pass x.dense()")
+        rows = _dev(bev.rows, torch.float32, "rows")
+        if rows.shape[0] == 0:                    # an empty level: every index entry is -1, no row is read
+            rows = rows.new_zeros((1, rows.shape[1]))
+    else:
+        x = _dev(x, torch.float32, "x")
     if isinstance(w_packed, F16x3Packed):
         data, cout, taps, cin = w_packed.data, w_packed.cout, w_packed.taps, w_packed.cin
     else:
@@ -621,6 +671,11 @@ def dense_launch(who, x, w_packed, scale, shift, geom, relu, out=None, coff=0, g
         tail += (_ptr(gap), 0 if gap is None else gap.shape[1])
     if row.io:
         tail += (io,)
+    if bev is not None:
+        lib.call("al3d_conv3x3_nhwc_f16x3_frag_rows", _ptr(rows), rows.shape[1], _ptr(_dev(bev.index, torch.int32, "index")),
+                 _ptr(data), _ptr(scale), _ptr(shift), _ptr(out), B, H, W, Cin, cout, out.shape[3], coff, 1 if relu else 0,
+                 io, _stream())
+        return out
     lib.call(fn + ("_gap" if gap is not None and row.gap == "entry" else ""), _ptr(x), _ptr(data), _ptr(scale), _ptr(shift),
              _ptr(out), B, H, W, Cin, cout, *(geom if row.generic and geom is not None else ()), out.shape[3], coff,
              1 if relu else 0, *tail, _stream())

@@ -115,6 +115,7 @@ SIGNATURES = {
                                          c_int, c_p, c_p]),
     "al3d_merge_bf16x3": (c_int, [c_p, c_i64, c_p, c_p]),
     "al3d_sp_to_dense_nhwc": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_p, c_p]),
+    "al3d_sp_bev_index": (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p]),
     "al3d_head_decode_nms": (c_int, [c_p, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                      c_flt, c_flt, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "al3d_head_decode_nms_workspace_bytes": (c_i64, [c_int, c_int, c_p]),
@@ -133,6 +134,7 @@ SIGNATURES = {
     "al3d_conv3x3_nhwc_f16x3_frag16": (c_int, [c_p, c_p, c_p, c_p, c_p] + [c_int] * 8 + [c_p]),
     "al3d_conv3x3_nhwc_f16x3_frag": (c_int, [c_p, c_p, c_p, c_p, c_p] + [c_int] * 8 + [c_p]),
     "al3d_conv3x3_nhwc_f16x3_frag_io": (c_int, [c_p, c_p, c_p, c_p, c_p] + [c_int] * 9 + [c_p]),
+    "al3d_conv3x3_nhwc_f16x3_frag_rows": (c_int, [c_p, c_int, c_p, c_p, c_p, c_p, c_p] + [c_int] * 9 + [c_p]),
     "al3d_pack_f16x3_bstream_elems": (c_i64, [c_int, c_int, c_int]),
     "al3d_pack_f16x3_bstream": (c_int, [c_p, c_int, c_int, c_int, c_p, c_p]),
     "al3d_conv2d_nhwc_f16x3_bstream": (c_int, [c_p, c_p, c_p, c_p, c_p] + [c_int] * 11 + [c_p]),

@@ -161,11 +161,13 @@ class _SparseEncoderBase(nn.Module):
     def _out_shape(shape, k, s, p):
         return [(shape[d] + 2 * p[d] - (k[d] - 1) - 1) // s[d] + 1 for d in range(3)]
 
-    def build_rulebook(self, coords, batch_size, spatial_shape, frame_rows_max=0):
+    def build_rulebook(self, coords, batch_size, spatial_shape, frame_rows_max=0, neck_rows=False):
         """All index work of one batch.  It depends on the voxel coordinates only -- level grids,
         output sites of the strided convs (one small D2H each), every layer's tap-major table -- so
         the sweep can run it for batch i+1 on a side stream while batch i is being convolved.
-        Returns ``dict(steps=[...])`` with one entry per item of the layer plan."""
+        Returns ``dict(steps=[...])`` with one entry per item of the layer plan.  ``neck_rows``: the caller's neck can
+        read the last level as ``detector_ops.BevRows``; where ``neck_rows_ok`` agrees the book carries the level's BEV
+        row index (``bev_index``) instead of the zero-filled dense map (``dense``)."""
         if self.training:
             raise RuntimeError("al3d sparse encoder implements the eval() sweep only")
         dev = coords.device
@@ -235,6 +237,9 @@ class _SparseEncoderBase(nn.Module):
         # the zero-filled dense BEV buffer the last stage scatters into (537 MB at batch 32): also
         # coordinate-independent work that can be done ahead
         last_c = [st_["mod"].out_channels for st_ in self._plan if st_["kind"] != "stage_end"][-1]
+        if neck_rows and D.neck_rows_ok("frag3x3", shape[0], last_c):
+            # the index belongs to this batch's book, not to the resident level grids cleaned above: the neck reads it
+            return dict(steps=steps, batch_size=batch_size, bev_index=D.bev_index(coords, n, batch_size, shape), perm=perm)
         dense = torch.zeros((batch_size, shape[1], shape[2], last_c * shape[0]), dtype=torch.float32, device=dev)
         return dict(steps=steps, batch_size=batch_size, dense=dense, perm=perm)
 
@@ -327,16 +332,21 @@ class FPNSpMiddleResNetFHD(_SparseEncoderBase):
     def _stages(self):
         return [self.middle_conv0, self.middle_conv1, self.middle_conv2, self.middle_conv3]
 
-    def rulebook_for(self, coors, batch_size, input_shape, frame_rows_max=0):
-        return self.build_rulebook(coors, batch_size, np.array(input_shape[::-1]) + [1, 0, 0], frame_rows_max)
+    def rulebook_for(self, coors, batch_size, input_shape, frame_rows_max=0, neck_rows=False):
+        return self.build_rulebook(coors, batch_size, np.array(input_shape[::-1]) + [1, 0, 0], frame_rows_max, neck_rows)
 
-    def forward(self, voxel_features, coors, batch_size, input_shape, book=None, frame_rows_max=0):
+    def forward(self, voxel_features, coors, batch_size, input_shape, book=None, frame_rows_max=0, neck_rows=False):
         """-> (dense NHWC [B,128,128,256], middle list of 4 SparseTensor) -- the reference
-        returns NCHW (scn.py:371-392); this build keeps activations channels-last."""
+        returns NCHW (scn.py:371-392); this build keeps activations channels-last.  ``neck_rows=True`` (a caller whose
+        neck takes it): a ``detector_ops.BevRows`` in place of the dense map when the book carries the row index."""
         sparse_shape = np.array(input_shape[::-1]) + [1, 0, 0]
         if book is None:
-            book = self.build_rulebook(coors, batch_size, sparse_shape, frame_rows_max)
+            book = self.build_rulebook(coors, batch_size, sparse_shape, frame_rows_max, neck_rows)
         final, middle = self._run(voxel_features, coors, batch_size, sparse_shape, book=book)
+        index = book.get("bev_index")
+        if index is not None:
+            rows = D.BevRows(final.features, final.indices, index)
+            return (rows if neck_rows else rows.dense()), middle
         return self.dense_nhwc(final, out=book.pop("dense", None)), middle
 
 

@@ -27,6 +27,8 @@ class BEVFusionCameraLidar(nn.Module):
                  lidar_channels=256, head=None):
         super().__init__()
         self.lidar = lidar_detector                                   # sparse encoder + SECOND / SECONDFPN ("neck")
+        if hasattr(lidar_detector, "neck_rows"):
+            lidar_detector.neck_rows = False                          # the fuser reads the encoder's dense map
         self.camera_backbone = SwinTransformer(embed_dims=96, depths=[2, 2, 6, 2], num_heads=[3, 6, 12, 24], window_size=7,
                                                mlp_ratio=4, qkv_bias=True, patch_norm=True, out_indices=[1, 2, 3])
         # upsample_cfg of the swint configs (configs/nuscenes/det/transfusion/secfpn/camera+lidar/default.yaml:16-18)

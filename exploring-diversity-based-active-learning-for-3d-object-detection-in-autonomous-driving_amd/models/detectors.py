@@ -67,6 +67,16 @@ class SingleStageDetector(nn.Module):
 
 @DETECTORS.register_module
 class FPNVoxelNet(SingleStageDetector):
+    # may the encoder hand this detector's own neck its last level as rows (detector_ops.BevRows)?  False where something
+    # else reads the encoder's dense map (BEVFusion's fuser)
+    neck_rows = True
+
+    def _neck_rows(self):
+        """The rows hand-over is possible for this encoder / neck pair under the current arithmetic and knobs."""
+        import inspect
+        return bool(self.neck_rows and self.with_neck and hasattr(self.neck, "rows_input_ok") and
+                    "neck_rows" in inspect.signature(self.backbone.forward).parameters and self.neck.rows_input_ok())
+
     def extract_feat(self, data):
         if data.get("mean_features") is not None:     # device voxelizer already reduced the points
             input_features = data["mean_features"]
@@ -95,10 +105,15 @@ class FPNVoxelNet(SingleStageDetector):
         it one batch ahead on a side stream.  Pass the result as ``book=`` to forward / sparse_stage."""
         if not hasattr(self.backbone, "rulebook_for"):
             return None
-        return self.backbone.rulebook_for(example["coordinates"], len(example["num_voxels"]),
-                                          example["shape"][0], **self._cap_kw(example.get("voxel_cap", 0)))
+        kw = self._cap_kw(example.get("voxel_cap", 0))
+        if self._neck_rows():
+            kw["neck_rows"] = True
+        return self.backbone.rulebook_for(example["coordinates"], len(example["num_voxels"]), example["shape"][0], **kw)
 
-    def sparse_stage(self, example, book=None):
+    def sparse_stage(self, example, book=None, neck_rows=False):
+        """-> (dense BEV map, middle).  ``neck_rows=True`` (the result goes to ``dense_stage``): the map may come as a
+        ``detector_ops.BevRows`` for the neck's first conv to read in place."""
+        rows_kw = {"neck_rows": True} if neck_rows and self._neck_rows() else {}
         num_voxels = example["num_voxels"]
         data = dict(features=example.get("voxels"), num_voxels=example.get("num_points"),
                     mean_features=example.get("voxel_features"), coors=example["coordinates"],
@@ -108,9 +123,10 @@ class FPNVoxelNet(SingleStageDetector):
         else:
             input_features = self.reader(data["features"], data["num_voxels"])
         if book is not None:
-            return self.backbone(input_features, data["coors"], data["batch_size"], data["input_shape"], book=book)
+            return self.backbone(input_features, data["coors"], data["batch_size"], data["input_shape"], book=book,
+                                 **rows_kw)
         return self.backbone(input_features, data["coors"], data["batch_size"], data["input_shape"],
-                             **self._cap_kw(data["voxel_cap"]))
+                             **self._cap_kw(data["voxel_cap"]), **rows_kw)
 
     def dense_stage(self, example, x, middle, finetune=False, **kwargs):
         pair = False
@@ -141,7 +157,7 @@ class FPNVoxelNet(SingleStageDetector):
     def forward(self, example, return_loss=True, finetune=False, **kwargs):
         if return_loss:
             raise NotImplementedError("al3d implements the inference sweep, not training")
-        x, middle = self.sparse_stage(example, book=kwargs.pop("book", None))
+        x, middle = self.sparse_stage(example, book=kwargs.pop("book", None), neck_rows=True)
         return self.dense_stage(example, x, middle, finetune=finetune, **kwargs)
 
 
@@ -182,7 +198,7 @@ class PointPillars(FPNVoxelNet):
             middle.append(NHWCFeature(x, getattr(self.neck, "embedding", None)))
         return x, middle
 
-    def sparse_stage(self, example, book=None):
+    def sparse_stage(self, example, book=None, neck_rows=False):       # the canvas is dense: neck_rows does not apply
         voxels = example.get("voxels")
         if voxels is None:
             raise RuntimeError("PointPillars needs the padded point slots: build the loader with with_points=True")

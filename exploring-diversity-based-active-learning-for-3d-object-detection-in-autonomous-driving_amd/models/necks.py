@@ -113,8 +113,18 @@ class RPN(nn.Module):
     def _kind(self, w):
         return getattr(w, "kind", None)
 
+    def rows_input_ok(self):
+        """Can ``forward`` take the sparse encoder's last level as ``detector_ops.BevRows`` (two z levels) right now?
+        It needs the first conv on the streamed 3x3 f16x3 kernel; decided from the module, before any packing."""
+        conv = next((m for m in self.blocks[0] if isinstance(m, nn.Conv2d)), None)
+        if conv is None or conv.in_channels % 2:
+            return False
+        kind = D.dense_structure(conv.out_channels, conv.in_channels, conv.kernel_size[0], conv.stride[0], 1)
+        return D.neck_rows_ok(kind, 2, conv.in_channels // 2)
+
     def forward(self, x, out_pair=False):
-        """x NHWC [B,H,W,Cin] -> NHWC [B,H',W',sum(us_num_filters)].
+        """x NHWC [B,H,W,Cin] (or the encoder's ``detector_ops.BevRows``: the first conv then reads the sparse rows)
+        -> NHWC [B,H',W',sum(us_num_filters)].
 
         Pair pixels (csrc/sp_rows.h, ``AL3D_DPIX``): a block's output whose consumers all run on the LDS-DMA kernel (the
         next block's strided entry conv, the block's deblock) is written as pair pixels by the block's last 3x3 launch
@@ -124,6 +134,9 @@ class RPN(nn.Module):
         if self.training:
             raise RuntimeError("al3d RPN implements the eval() sweep only")
         self._prepare(x.device)
+        if isinstance(x, D.BevRows) and not D.neck_rows_ok(self._kind(self._blocks_p[0][0]["w"]), x.index.shape[3],
+                                                           x.rows.shape[1]):
+            x = x.dense()                                 # the first conv has no rows input under this arithmetic / structure
         pairing = D.MATH == "f16x3" and D.DPIX == "pair"
         out, coff = None, 0
         ctot = sum(self._num_upsample_filters)

@@ -133,8 +133,17 @@ def _side_stream(device):
     return _SIDE[key]
 
 
+def _sparse_stage(detector, example, book=None):
+    """``detector.sparse_stage`` for a result that goes to its ``dense_stage``: a detector that can hand its neck the
+    encoder's rows instead of the dense map (``neck_rows``) is asked to."""
+    import inspect
+    kw = {"neck_rows": True} if "neck_rows" in inspect.signature(detector.sparse_stage).parameters else {}
+    return detector.sparse_stage(example, **kw) if book is None else detector.sparse_stage(example, book=book, **kw)
+
+
 def _tensors_of(obj):
-    """Every CUDA tensor reachable from a nest of dicts / lists / tuples / objects with tensor fields."""
+    """Every CUDA tensor reachable from a nest of dicts / lists / tuples / objects with tensor fields (a sparse stage's
+    ``SparseTensor`` / ``detector_ops.BevRows`` results among them)."""
     if isinstance(obj, torch.Tensor):
         if obj.is_cuda:
             yield obj
@@ -300,7 +309,7 @@ def sweep_embeddings(detector, dataloader, device, num_frames=None, with_entropy
                           # the next batch's index work (random grid traffic) is released only once this batch's
                           # sparse convolutions -- the gather-bound kernels it would slow down -- are through: it
                           # then runs beside the matrix-core-bound neck, which does not notice it
-                          x, middle = detector.sparse_stage(example, book=ahead)
+                          x, middle = _sparse_stage(detector, example, book=ahead)
                           sparse_done = torch.cuda.Event()
                           sparse_done.record(main)
                           side.wait_event(sparse_done)
@@ -343,7 +352,7 @@ def sweep_embeddings(detector, dataloader, device, num_frames=None, with_entropy
                       except StopIteration:
                           break
                       example = example_to_device(data_batch, device, non_blocking=False)
-                      ahead = detector.prepare(example) if mode == "ahead" else detector.sparse_stage(example)
+                      ahead = detector.prepare(example) if mode == "ahead" else _sparse_stage(detector, example)
                       for t in _tensors_of((example, ahead)):
                           t.record_stream(main)   # produced on the side stream, consumed on the main one
                       ev = torch.cuda.Event()

@@ -425,6 +425,11 @@ int al3d_merge_bf16x3(const void* planes_bf16x3, int64_t count, float* out, void
 int al3d_sp_to_dense_nhwc(const float* feat, const int* coords, int n, int C, int B, int D, int H,
                           int W, float* out, void* stream);
 
+/* The same hand-over without the dense map (D = 2 only, AL3D_EINVAL otherwise): idx [B,H,W,D] i32, pre-filled with -1,
+ * receives idx[b][y][x][z] = row for each of the n rows (no atomics: the rows of a level have distinct coordinates).
+ * al3d_conv3x3_nhwc_f16x3_frag_rows reads the rows through it (replaces scn.py:387-390 together with that call). */
+int al3d_sp_bev_index(const int* coords, int n, int B, int D, int H, int W, int* idx, void* stream);
+
 /* ---------------------------------------------------------------- detector: dense */
 
 /* NHWC f32 convolution on the fp32 matrix cores with fused per-channel
@@ -494,6 +499,13 @@ int al3d_conv3x3_nhwc_f16x3_frag(const float* in, const void* wgt_frag, const fl
 int al3d_conv3x3_nhwc_f16x3_frag_io(const float* in, const void* wgt_frag, const float* scale,
                                     const float* shift, float* out, int B, int H, int W, int Cin, int Cout,
                                     int ldc, int coff, int relu, int io, void* stream);
+/* ... reading its input map from the sparse encoder's last level instead of a dense tensor (scn.py:387-390 `ret.dense()`
+ * + view, then the first Conv2d of rpn.py's first block): rows [n][rows_pitch] f32 and bev [B,H,W,2] i32 from
+ * al3d_sp_bev_index; map channel c * 2 + z = rows[bev[b][y][x][z]][c] (0 where bev is -1), Cin = 2 * channels per row.
+ * MFMAs whose whole 34-pixel halo row is empty are skipped; the output equals the dense call's word for word. */
+int al3d_conv3x3_nhwc_f16x3_frag_rows(const float* rows, int rows_pitch, const int* bev, const void* wgt_frag,
+                                      const float* scale, const float* shift, float* out, int B, int H, int W,
+                                      int Cin, int Cout, int ldc, int coff, int relu, int io, void* stream);
 /* Every other geometry (stride-2 block entry, 1x1 deblock, 2x2 deconvolution, fused 1x1 head:
  * rpn.py:66-113, mg_head.py:215-231) with the weights streamed the same way: activations staged
  * through LDS per (tap, 16-channel chunk), B fragments from al3d_pack_f16x3_bstream(): planes

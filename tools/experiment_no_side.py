@@ -28,7 +28,9 @@ ex = next(iter(loader))
 with torch.no_grad():
     book = model.prepare(ex)
     def once():
-        bk = dict(book); bk["dense"] = torch.zeros_like(book["dense"])
+        bk = dict(book)
+        if "dense" in book:                # AL3D_NECK_IN=dense: a fresh zero-filled map per use (rows: the index is reusable)
+            bk["dense"] = torch.zeros_like(book["dense"])
         preds, middle = model(ex, return_loss=False, estimate=True, book=bk)
         return middle[-1].mean(-1).mean(-1)
     once(); torch.cuda.synchronize()
@@ -38,7 +40,9 @@ with torch.no_grad():
         torch.cuda.synchronize(); t = time.perf_counter() - t0
         print(f"main stream alone ({mode}): {t / NB * 1e3:.2f} ms per batch  ({B * NB / t:.0f} frames/s)")
     def once_no_nms():
-        bk = dict(book); bk["dense"] = torch.zeros_like(book["dense"])
+        bk = dict(book)
+        if "dense" in book:                # AL3D_NECK_IN=dense: a fresh zero-filled map per use (rows: the index is reusable)
+            bk["dense"] = torch.zeros_like(book["dense"])
         x, middle = model.sparse_stage(ex, book=bk)
         x = model.neck(x)
         model.bbox_head(x)
