@@ -10,7 +10,12 @@
 //                 edge rules of the library (first / last column special cases, the rows above the first and below the last
 //                 REAL chroma row are replicas of it -- not the padding rows the blocks carry);
 //   * jdcolor.c   YCbCr -> RGB with the 16-bit fixed-point tables (FIX(1.40200) etc., ONE_HALF folded into the Cb term).
-// Integer arithmetic throughout: bit-identical to Pillow on every image tests/test_jpeg_gpu.py decodes.
+// Integer arithmetic throughout: bit-identical to Pillow on every image tests/test_jpeg_gpu.py decodes -- Pillow-written
+// 4:4:4 / 4:2:2 / 4:2:0 / grey files, and every other layout the host half accepts from a baseline writer of the tests' own:
+// 4:4:0 (h1v2), Cb 2x1 + Cr 1x2 and Cb 2x2 + Cr 1x1 under a 2x2 luma, Cb 1x1 + Cr 2x1 under a 2x1 luma; at 61 x 83 and at
+// the smallest frames that reach every branch of jp_upsample (H = 1, 2, 3, 4 under a vertical ratio of 2; W = 5, 6, i.e. 3 real
+// chroma columns, under a horizontal one; W = 1 at 4:4:0).  Narrower horizontally subsampled frames never arrive: libjpeg
+// replicates where a component has at most 2 real columns, and the host half refuses them.
 #include "al3d_common.h"
 #include "../../include/al3d.h"
 

@@ -11,7 +11,11 @@
 //
 // Scope: 8-bit baseline (SOF0) Huffman, one interleaved scan, 1 or 3 components (YCbCr / grayscale), sampling factors 1 or
 // 2 with the luma at the maximum, restart intervals.  Anything else (progressive, arithmetic, 12-bit, CMYK, RGB component
-// ids, multiple scans) returns AL3D_EINVAL with the reason; the loader then hands that file to Pillow.
+// ids, multiple scans, 16-bit quantisation tables) returns AL3D_EINVAL with the reason; the loader then hands that file to
+// Pillow.  So do two things libjpeg treats differently from the restatement here: a three-component frame whose horizontally
+// subsampled component has at most two real columns (libjpeg replicates there instead of its fancy upsampling), and a scan
+// that ends early -- a marker or the end of the data inside the scan, after which libjpeg leaves the remaining MCUs zero, or
+// no EOI after the last MCU, on which Pillow raises "image file is truncated".
 #include "al3d_common.h"
 #include "../../include/al3d.h"
 #include <cstring>
@@ -59,6 +63,8 @@ struct Bits {
     unsigned long long acc = 0;     // bits left-aligned at bit 63
     int n = 0;                      // valid bits in acc
     bool marker = false;            // a marker was reached: zeros are fed from here on (as libjpeg does)
+    int zeros = 0;                  // how many of the n valid bits, at the low end, are such zeros
+    bool starved = false;           // the decoder has consumed some of them: the scan's data ended early
 
     inline void fill()
     {
@@ -75,12 +81,17 @@ struct Bits {
             } else {
                 marker = true;
             }
+            if (marker) zeros += 8;
             acc |= (unsigned long long)b << (56 - n);
             n += 8;
         }
     }
     inline unsigned peek(int k) { return (unsigned)(acc >> (64 - k)); }
-    inline void skip(int k) { acc <<= k; n -= k; }
+    inline void skip(int k)
+    {
+        acc <<= k; n -= k;
+        if (n < zeros) { zeros = n; starved = true; }
+    }
     inline int receive_extend(int s)
     {
         if (s == 0) return 0;
@@ -104,7 +115,7 @@ struct Bits {
     // after an MCU row / restart interval: drop the partial byte, expect RSTn
     bool restart(int expect)
     {
-        acc = 0; n = 0;
+        acc = 0; n = 0; zeros = 0;
         // the reader stopped AT the 0xff of the marker (marker == true) or must skip fill bytes up to it
         while (p + 1 < end && !(p[0] == 0xff && p[1] != 0 && p[1] != 0xff)) ++p;
         if (p + 1 >= end) return false;
@@ -112,6 +123,12 @@ struct Bits {
         p += 2;
         marker = false;
         return true;
+    }
+    // after the last MCU: fill bytes and stray bytes are passed over (as libjpeg passes them), then EOI must follow
+    bool at_eoi()
+    {
+        while (p + 1 < end && !(p[0] == 0xff && p[1] != 0 && p[1] != 0xff)) ++p;
+        return p + 1 < end && p[1] == 0xd9;
     }
 };
 
@@ -165,6 +182,9 @@ int parse(const unsigned char* d, int64_t n, Parsed& P)
                 const int pq = s[k] >> 4, tq = s[k] & 15;
                 ++k;
                 if (tq > 3 || (pq != 0 && pq != 1) || k + 64 * (pq + 1) > sl) return al3d_fail(AL3D_EINVAL, "jpeg: bad DQT");
+                // baseline allows 8-bit tables only; with entries above 255 libjpeg's range-limit table wraps where the
+                // device half clamps
+                if (pq) return al3d_fail(AL3D_EINVAL, "jpeg: 16-bit quantisation table (8-bit only in a baseline frame)");
                 for (int z = 0; z < 64; ++z) {
                     const int v = pq ? be16(s + k + 2 * z) : s[k + z];
                     P.quant[tq][kZigzag[z]] = (unsigned short)v;
@@ -217,6 +237,11 @@ int parse(const unsigned char* d, int64_t n, Parsed& P)
     if (P.ncomp == 3) {
         if (P.hs[0] != mh || P.vs[0] != mv) return al3d_fail(AL3D_EINVAL, "jpeg: subsampled luma");
         if (P.cid[0] == 'R' && P.cid[1] == 'G' && P.cid[2] == 'B') return al3d_fail(AL3D_EINVAL, "jpeg: RGB component ids");
+        // libjpeg takes its fancy h2v1 / h2v2 upsamplers only when the component's downsampled_width > 2 and replicates
+        // otherwise; frames that narrow go to Pillow
+        for (int c = 1; c < 3; ++c)
+            if (mh / P.hs[c] == 2 && (P.width * P.hs[c] + mh - 1) / mh <= 2)
+                return al3d_fail(AL3D_EINVAL, "jpeg: %d px wide with horizontally subsampled chroma", P.width);
     }
     return AL3D_OK;
 }
@@ -308,8 +333,10 @@ extern "C" int al3d_jpeg_entropy_decode(const unsigned char* data, int64_t nbyte
                     }
                 }
             }
+            if (B.starved) return al3d_fail(AL3D_EINVAL, "jpeg: premature end of scan");
             if (ri) --left;
         }
     }
+    if (!B.at_eoi()) return al3d_fail(AL3D_EINVAL, "jpeg: no EOI after the scan");
     return AL3D_OK;
 }

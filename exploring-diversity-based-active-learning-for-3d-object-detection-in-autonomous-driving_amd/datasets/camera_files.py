@@ -22,7 +22,7 @@ more and test_mode is unset: not reproducible, like det3d's loader).
 """
 import ctypes
 import os
-from concurrent.futures import ThreadPoolExecutor
+from concurrent.futures import ThreadPoolExecutor, wait as futures_wait
 
 import numpy as np
 import torch
@@ -239,18 +239,28 @@ class CameraLidarFileLoader(FileSweepLoader):
         st.extra = dict(mode="split", jobs=jobs, info=info, nimg=nimg)
         return st
 
+    @staticmethod
+    def _settle(jobs):
+        """Cancel the decode jobs that have not started and wait for the ones that have: a running job writes through a raw
+        pointer into its slot's pinned coefficient buffer, which the next iteration reuses or frees."""
+        running = [f for cam_jobs in jobs for f in cam_jobs if not f.cancel()]
+        if running:
+            futures_wait(running)
+
     def _abandon(self, st):
-        """Iteration ended before this batch was finished: cancel the decode jobs that have not started, drop the rest."""
-        for cam_jobs in (getattr(st, "extra", None) or {}).get("jobs", []):
-            for f in cam_jobs:
-                f.cancel()
+        """Iteration ended before this batch was finished: cancel the decode jobs that have not started, wait out the rest."""
+        self._settle((getattr(st, "extra", None) or {}).get("jobs", []))
         st.extra = None
 
     def _finish(self, st):
-        ex = super()._finish(st)
         extra, st.extra = st.extra, None
         jobs = extra["jobs"]
-        results = [[f.result() for f in cam_jobs] for cam_jobs in jobs]
+        try:
+            ex = super()._finish(st)
+            results = [[f.result() for f in cam_jobs] for cam_jobs in jobs]
+        except BaseException:
+            self._settle(jobs)                               # no sibling job outlives the batch it was writing for
+            raise
         B, N = len(results), len(results[0])
         if any(len(fr) != N for fr in results):
             raise lib.Al3dError("CameraLidarFileLoader: every sample of a batch must list the same number of cameras")
