@@ -31,13 +31,10 @@
 // Nothing here calls a BLAS / MIOpen routine.  gfx950 only.
 #include "al3d_common.h"
 #include "sp_rows.h"
+#include "tok_shared.h"
 #include <type_traits>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float tk_f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void tk_lds_void;
-typedef const __attribute__((address_space(1))) void tk_gbl_void;
 
 #define TK_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0)
 #define TK_STAGE 16384      // bytes per ring stage: A 8 KB (128 rows x 16 channels f32 / pair) + B 8 KB
@@ -46,10 +43,6 @@ typedef const __attribute__((address_space(1))) void tk_gbl_void;
 
 __device__ __attribute__((aligned(256))) float g_tok_zero[64];     // stays zero: source of rows beyond M
 
-template <int N> __device__ __forceinline__ void tk_wait_vm()
-{
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 __device__ __forceinline__ int tk_swz(int r) { return (r & 1) | (((r >> 3) & 1) << 1); }
 
 __device__ __forceinline__ void tk_split(float x, _Float16& h, _Float16& l)
@@ -245,38 +238,6 @@ __device__ __forceinline__ bool tk_tile_of_block(const TokGemmParams& p, int& ti
     nblk = rem >> 3;
     tile = grp * 8 + (rem & 7);
     return tile < p.ntiles;
-}
-
-// erf to fp32 rounding level, branch-free: the two minimax pieces of N. Juffa's single-precision erf (x + x P(x^2) below
-// 475/512, 1 - exp(Q(|x|)) above; each < 1 ulp with an exact exp) are both evaluated and one is selected -- the library erff
-// costs ~45 vector instructions and a divergent branch per element, and the GELU epilogues are bound by exactly that.
-// exp through v_exp_f32 (2^x): its argument is <= -0.9, so the result is <= 0.41 and the error it adds to 1 - exp stays
-// below 1e-7.  Measured against float64 over [-8, 8]: see tests/test_swin_gpu.py::test_gelu_epilogue_accuracy.
-__device__ __forceinline__ float tk_erf(float a)
-{
-    const float t = fabsf(a), s = a * a;
-    float r = __builtin_fmaf(-1.72853470e-5f, t, 3.83197126e-4f);
-    const float u = __builtin_fmaf(-3.88396438e-3f, t, 2.42546219e-2f);
-    r = __builtin_fmaf(r, s, u);
-    r = __builtin_fmaf(r, t, -1.06777877e-1f);
-    r = __builtin_fmaf(r, t, -6.34846687e-1f);
-    r = __builtin_fmaf(r, t, -1.28717512e-1f);
-    r = __builtin_fmaf(r, t, -t);
-    float big = 1.0f - __builtin_amdgcn_exp2f(r * 1.44269504088896340736f);
-    big = __builtin_copysignf(big, a);
-    float q = -5.96761703e-4f;
-    q = __builtin_fmaf(q, s, 4.99119423e-3f);
-    q = __builtin_fmaf(q, s, -2.67681349e-2f);
-    q = __builtin_fmaf(q, s, 1.12819925e-1f);
-    q = __builtin_fmaf(q, s, -3.76125336e-1f);
-    q = __builtin_fmaf(q, s, 1.28379166e-1f);
-    q = __builtin_fmaf(q, a, a);
-    return t > 0.927734375f ? big : q;
-}
-
-__device__ __forceinline__ float tk_gelu(float v)
-{
-    return (v * 0.5f) * (1.0f + tk_erf(v * 0.70710678118654752440f));
 }
 
 struct TkOps {
@@ -904,28 +865,6 @@ extern "C" int al3d_tok_mlp_f16x3(float* x, int64_t T, int C, int hidden, const 
 }
 
 // ------------------------------------------------------------------ 7 x 7 window attention, head dim 32
-struct TokAttnParams {
-    const float* qkv;       // [nwin * 49][3 C]: q | k | v, each [heads][32]
-    const float* table;     // [169][heads] relative position bias table
-    float* out;             // [nwin * 49][C] f32 or pair rows
-    int nwin, C, heads;
-    int nwy, nwx;           // windows per image (rows, columns)
-    int shift;              // cyclic shift of the block (0: no mask)
-    float scale;
-    int pair;
-    // token-order mode (bias != null): qkv / out rows are the B maps' H x W tokens; the cyclic shift, the padding and the
-    // window partition are evaluated from the window's position, a padded position's q / k / v row is the qkv bias
-    const float* bias;      // [3 C] or null (window-order mode: rows win * 49 + position)
-    int H, W;
-};
-
-#define TK_WS 7
-#define TK_NT 49
-
-__device__ __forceinline__ int tk_region1(int v, int n, int shift)
-{
-    return (v >= n - TK_WS ? 1 : 0) + (v >= n - shift ? 1 : 0);
-}
 
 // the f16x3 split of 8 values with the packed conversions of sp_split8 (3 instructions per element instead of 5); the
 // inputs are pinned first (see tk_split: the high part and the residual must see the same rounded fp32 value)
@@ -938,8 +877,6 @@ __device__ __forceinline__ void tk_split8p(float (&v)[8], f16x8& ph, f16x8& pl)
     ph = __builtin_bit_cast(f16x8, hi);
     pl = __builtin_bit_cast(f16x8, lo);
 }
-// 13 y + x of key position min(key, 48) in the 7 x 7 window: the key's part of the relative position index
-__host__ __device__ constexpr int tk_kcode(int key) { return (key < TK_NT ? key : TK_NT - 1) + 6 * ((key < TK_NT ? key : TK_NT - 1) / TK_WS); }
 
 // Two waves (= one 128-thread workgroup) per (window, head), one 32-query tile each.  The head's q, k, v rows (49 x 128 B each, 1152+ B apart in
 // the qkv matrix) come in by LDS-DMA, eight whole rows per instruction (every 128-byte line fetched once, by one
@@ -951,14 +888,6 @@ __host__ __device__ constexpr int tk_kcode(int key) { return (key < TK_NT ? key 
 // 8 s .. 8 s + 7 of a tile are k-step s, in the order key = 16 s + 8 (j >> 2) + 4 h + (j & 3) -- the V^T fragment
 // is read in that same order.  Both operands of both products are activations: each is split (xh, xl' = residual
 // x 2^11) and the product is  xh yh  +  2^-11 (xh yl' + xl' yh)  with the two brackets in separate accumulators.
-#define TK_AROWS 56                   // rows staged per array: 7 DMA instructions of 8 rows; rows 49 .. 55 are zero
-#define TK_ABYTES (TK_AROWS * 128)
-
-__device__ __forceinline__ unsigned tk_arow_off(int row, int chunk)      // byte offset of 16-byte chunk `chunk` of a staged row
-{
-    const int r = row < TK_AROWS ? row : TK_AROWS - 1;                   // rows 56 .. 63 of a tile read a zero row
-    return (unsigned)(r * 128 + ((chunk ^ ((r >> 1) & 7)) << 4));
-}
 
 __global__ __launch_bounds__(128, 3) void tok_window_attention_kernel(TokAttnParams p)
 {
@@ -1233,15 +1162,6 @@ extern "C" int al3d_tok_window_attention_tokens_f32(const float* qkv, const floa
 // = per lane), and O^T += V^T P^T with P taken from the accumulators as the B operand (rows of O^T = the 16 channels;
 // the upper half of the 32-row tile is idle).  Both operands split as in the window kernel (main + 2^-11 correction
 // accumulators).  Each wave writes (max, sum, O[16]) of its chunk; tok_mha16_combine_kernel merges the chunks.
-struct TokMhaParams {
-    const float* q;         // [B][Pq][ldq], this head's 16 channels at column head * 16
-    const float* k;         // [B][Pk][ldk]
-    const float* v;         // [B][Pk][ldv]
-    float* part;            // [B][heads][chunks][qtiles * 32][18]: running max, sum, O[16]
-    int B, heads, Pq, Pk, ldq, ldk, ldv;
-    int qtiles, chunks, keys_per_chunk;          // keys_per_chunk: a multiple of 32
-    float scale;
-};
 
 __global__ __launch_bounds__(64) void tok_mha16_kernel(TokMhaParams p)
 {
@@ -1339,30 +1259,6 @@ __global__ __launch_bounds__(64) void tok_mha16_kernel(TokMhaParams p)
     if (h == 0) { o[0] = run_max; o[1] = run_sum; }
 #pragma unroll
     for (int r = 0; r < 8; ++r) o[2 + (r & 3) + 8 * (r >> 2) + 4 * h] = om[r] + oc[r] * 0.00048828125f;
-}
-
-// out[b][query][head * 16 + d] = sum_c e^(m_c - M) O_c[d] / sum_c e^(m_c - M) l_c
-__global__ __launch_bounds__(256) void tok_mha16_combine_kernel(const float* __restrict__ part, int B, int heads, int chunks,
-                                                                int qrows, int Pq, float* __restrict__ out, int ldo)
-{
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (int64_t)B * heads * Pq * 16) return;
-    const int d = (int)(t & 15);
-    int64_t r = t >> 4;
-    const int query = (int)(r % Pq); r /= Pq;
-    const int head = (int)(r % heads);
-    const int b = (int)(r / heads);
-    const float* base = part + (((int64_t)b * heads + head) * chunks * qrows + query) * 18;
-    float M = -INFINITY;
-    for (int c = 0; c < chunks; ++c) M = fmaxf(M, base[(int64_t)c * qrows * 18]);
-    float num = 0.f, den = 0.f;
-    for (int c = 0; c < chunks; ++c) {
-        const float* q = base + (int64_t)c * qrows * 18;
-        const float w = expf(q[0] - M);
-        num += w * q[2 + d];
-        den += w * q[1];
-    }
-    out[((int64_t)b * Pq + query) * ldo + head * 16 + d] = num / den;
 }
 
 extern "C" int64_t al3d_tok_mha16_workspace_bytes(int B, int heads, int Pq, int Pk)

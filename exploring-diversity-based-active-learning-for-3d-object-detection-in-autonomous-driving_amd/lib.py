@@ -226,6 +226,12 @@ SIGNATURES = {
                                               c_p]),
     "al3d_tok_window_attention_tokens_f32": (c_int, [c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_flt, c_int, c_p,
                                                      c_p]),
+    "al3d_tok_linear_bf16x6": (c_int, [c_p, c_p, c_p, c_p, c_i64, c_int, c_int, c_int, c_p, c_int, c_p, c_p, c_int, c_p]),
+    "al3d_tok_window_attention_bf16x6": (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_flt, c_p, c_p]),
+    "al3d_tok_window_attention_tokens_bf16x6": (c_int, [c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_flt, c_p,
+                                                        c_p]),
+    "al3d_tok_mha16_bf16x6": (c_int, [c_p, c_int, c_p, c_int, c_p, c_int, c_int, c_int, c_int, c_int, c_flt, c_p, c_int, c_p,
+                                      c_p]),
 }
 
 _lib = None

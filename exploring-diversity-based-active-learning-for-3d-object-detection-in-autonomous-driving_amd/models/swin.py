@@ -11,6 +11,11 @@ relative_position_bias_table}, norm2, ffn.layers.0.0, ffn.layers.1}``; ``stages.
 with the ``nn.Unfold`` channel order (c * 4 + kh * 2 + kw); ``norm<i>`` on the output levels; the relative position
 index built by mmdet's ``double_step_seq``.  **Parity unpinned** (no source, no checkpoint, no fixture).
 
+Arithmetic (``AL3D_MATH``, read per call): under ``f16x3`` the activations between the kernels of a block travel as pair rows
+and embed dims 96 / 192 run the fused kernels; under ``bf16x6`` / ``f32`` (and in the batches that ``AL3D_MATH=auto`` re-runs)
+every block takes the split form below on f32 rows, with the GEMMs and the attention on csrc/tokens_bf16x6.hip.  The packed
+weights (``token_ops.PackedLinear``) hold one image per arithmetic, so the per-module caches need no arithmetic in their key.
+
 How a block runs (seven launches -- five at embed dim 96, where LN2 / fc1 / fc2 are ONE kernel, al3d_tok_mlp_f16x3 --; no torch
 op touches an activation):
   LN1 gathered into (shifted) window order, padding rows zero, pair rows   al3d_tok_layernorm_f32
@@ -159,33 +164,36 @@ class SwinBlock(nn.Module):
         """x [B * H * W, C] f32 token rows, updated IN PLACE; geom = _Geometry of the stage."""
         msa = self.attn.w_msa
         n1, n2 = self.norm1, self.norm2
-        if FUSED_ATTN and x.shape[-1] in FUSED_ATTN_DIMS:
+        # pair rows and the fused kernels are f16x3: under bf16x6 / f32 (also the AL3D_MATH=auto re-run, which flips
+        # detector_ops.MATH under a live model) every half takes its split form on f32 rows
+        pr = T.pair_rows()
+        if pr and FUSED_ATTN and x.shape[-1] in FUSED_ATTN_DIMS:
             # LN1 + qkv + attention + proj + residual as one kernel: q, k, v and the attention output stay on the CU
             T.attn_block(x, geom.B, geom.H, geom.W, msa.packed_fused(x.device, n1), self.attn.shift_size, msa.scale)
         elif TOKEN_ORDER:
             # LN1, qkv and proj on the map's own tokens; the attention kernel gathers its windows (shift, padding: a padded
             # position's q / k / v is the qkv bias) and writes token order back -- no GEMM row for the window padding
             qkv_w, proj_w, table = msa.packed(x.device)
-            xw = T.layernorm(x, n1.weight, n1.bias, n1.eps, pair=True)
-            qkv = T.linear(xw, qkv_w, a_pair=True)
+            xw = T.layernorm(x, n1.weight, n1.bias, n1.eps, pair=pr)
+            qkv = T.linear(xw, qkv_w, a_pair=pr)
             ao = T.window_attention_tokens(qkv, msa.qkv_bias_rows(x.device), table, geom.B, geom.H, geom.W, msa.num_heads,
-                                           self.attn.shift_size, msa.scale, pair=True)
-            T.linear(ao, proj_w, a_pair=True, residual=x, out=x)
+                                           self.attn.shift_size, msa.scale, pair=pr)
+            T.linear(ao, proj_w, a_pair=pr, residual=x, out=x)
         else:
             rowmap, (nwy, nwx) = geom.window_map(self.attn.shift_size)
             qkv_w, proj_w, table = msa.packed(x.device)
-            xw = T.layernorm(x, n1.weight, n1.bias, n1.eps, rowmap=rowmap, zero_out=True, pair=True)
-            qkv = T.linear(xw, qkv_w, a_pair=True)
-            ao = T.window_attention(qkv, table, msa.num_heads, nwy, nwx, self.attn.shift_size, msa.scale, pair=True)
-            T.linear(ao, proj_w, a_pair=True, residual=x, rowmap=rowmap, out=x)
-        if FUSED_MLP and x.shape[-1] in FUSED_MLP_DIMS:
+            xw = T.layernorm(x, n1.weight, n1.bias, n1.eps, rowmap=rowmap, zero_out=True, pair=pr)
+            qkv = T.linear(xw, qkv_w, a_pair=pr)
+            ao = T.window_attention(qkv, table, msa.num_heads, nwy, nwx, self.attn.shift_size, msa.scale, pair=pr)
+            T.linear(ao, proj_w, a_pair=pr, residual=x, rowmap=rowmap, out=x)
+        if pr and FUSED_MLP and x.shape[-1] in FUSED_MLP_DIMS:
             # stages 0-1: LN2 + fc1 + GELU + fc2 + residual as one kernel (the hidden activation stays in registers)
             T.mlp(x, self.ffn.packed_fused(x.device, n2))
             return x
         fc1_w, fc2_w = self.ffn.packed(x.device)
-        xn = T.layernorm(x, n2.weight, n2.bias, n2.eps, pair=True)
-        hid = T.linear(xn, fc1_w, a_pair=True, act="gelu", out_pair=True)
-        T.linear(hid, fc2_w, a_pair=True, residual=x, out=x)
+        xn = T.layernorm(x, n2.weight, n2.bias, n2.eps, pair=pr)
+        hid = T.linear(xn, fc1_w, a_pair=pr, act="gelu", out_pair=pr)
+        T.linear(hid, fc2_w, a_pair=pr, residual=x, out=x)
         return x
 
 
@@ -213,8 +221,9 @@ class PatchMerging(nn.Module):
     def forward(self, x, geom):
         rowmap, out_hw = geom.merge_map()
         w, g, b = self.packed(x.device)
-        xm = T.layernorm(x, g, b, self.norm.eps, rowmap=rowmap, G=4, pair=True)
-        return T.linear(xm, w, a_pair=True), out_hw
+        pr = T.pair_rows()
+        xm = T.layernorm(x, g, b, self.norm.eps, rowmap=rowmap, G=4, pair=pr)
+        return T.linear(xm, w, a_pair=pr), out_hw
 
 
 class _Geometry:
@@ -280,7 +289,7 @@ class _PatchEmbed(nn.Module):
     def forward(self, x):
         """x channels-last [B,H,W,3] -> token rows [B * H/4 * W/4, C], (H/4, W/4)."""
         pr = self.projection
-        if FUSED_PATCH_EMBED and pr.out_channels == 96 and x.shape[2] % 4 == 0:
+        if T.pair_rows() and FUSED_PATCH_EMBED and pr.out_channels == 96 and x.shape[2] % 4 == 0:
             # projection + LayerNorm as one kernel: the image is read once, the tokens are written once
             if getattr(self, "_pkf", None) is None:
                 object.__setattr__(self, "_pkf", _Packed())
@@ -291,8 +300,8 @@ class _PatchEmbed(nn.Module):
             return T.patch_embed(x, pk)
         w = self._pk.get(x.device, (pr,), lambda: T.PackedLinear(
             pr.weight.detach().permute(0, 2, 3, 1).reshape(pr.out_channels, -1), pr.bias))      # [C, (ky, kx, c)]
-        rows, hw = T.patch_rows(x, pair=True)
-        y = T.linear(rows, w, a_pair=True)
+        rows, hw = T.patch_rows(x, pair=T.pair_rows())
+        y = T.linear(rows, w, a_pair=T.pair_rows())
         if self.norm is not None:
             y = T.layernorm(y, self.norm.weight, self.norm.bias, self.norm.eps)
         return y, hw

@@ -73,7 +73,8 @@ class TransformerDecoderLayer(nn.Module):
     """transformer.py:33-112 (``cross_only=False``).  ``self_attn`` / ``multihead_attn`` are ``nn.MultiheadAttention``
     modules only as PARAMETER containers (in_proj_weight / in_proj_bias / out_proj: the reference's names); the
     computation runs on the token kernels: input projections and out_proj as token GEMMs (residual fused), the
-    attention core on ``al3d_tok_mha16_f32``, LayerNorm on ``al3d_tok_layernorm_f32``."""
+    attention core on ``al3d_tok_mha16_f32``, LayerNorm on ``al3d_tok_layernorm_f32``; under ``AL3D_MATH=bf16x6`` / ``f32``
+    the GEMMs and the attention core are the ``_bf16x6`` entries (``token_ops`` reads the arithmetic per call)."""
 
     def __init__(self, d_model, nhead, dim_feedforward=2048, dropout=0.1, activation="relu", self_posembed=None,
                  cross_posembed=None):
@@ -89,7 +90,7 @@ class TransformerDecoderLayer(nn.Module):
         self.activation = activation
         self.self_posembed, self.cross_posembed = self_posembed, cross_posembed
         object.__setattr__(self, "_pk", _Packed())
-        object.__setattr__(self, "_kpe", _Packed())
+        object.__setattr__(self, "_kpe", {})
 
     def packed(self, device):
         sa, ca = self.self_attn, self.multihead_attn
@@ -114,7 +115,11 @@ class TransformerDecoderLayer(nn.Module):
         def build():
             kpe = self.cross_posembed(key_pos_rows)
             return T.linear(kpe, T.PackedLinear(ca.in_proj_weight[C:], ca.in_proj_bias[C:]))
-        return self._kpe.get((key_pos_rows.device, key_pos_rows.data_ptr(), key_pos_rows.shape[0]), mods, build)
+        # an ACTIVATION cache: one per arithmetic (a sweep that re-runs a batch under bf16x6 must not read f16x3 rows, nor
+        # rebuild them when it flips back)
+        arith = T.arithmetic()
+        kpe = self._kpe.setdefault(arith, _Packed())
+        return kpe.get((key_pos_rows.device, key_pos_rows.data_ptr(), key_pos_rows.shape[0]), mods, build)
 
     def forward(self, query, key, query_pos, key_pos, B):
         """query rows [B*Pq, C], key rows [B*Pk, C], query_pos rows [B*Pq, 2], key_pos rows [Pk, 2] (shared by the samples)

@@ -399,7 +399,8 @@ def _check_range(local, recovered=False):
         if recovered:
             rows = (~torch.isfinite(local).all(dim=1)).nonzero().flatten().tolist()
             raise Al3dError(f"{len(rows)} frame embedding(s) are not finite and not recoverable: they stay non-finite "
-                            f"under AL3D_MATH=bf16x6 too (non-finite input, or a module without bf16x6 kernels); "
+                            f"under AL3D_MATH=bf16x6 too, where every conv and token kernel covers the fp32 range (non-finite "
+                            f"input or weights, or an activation beyond fp32 itself); "
                             f"frames {rows}")
         bad = int((~torch.isfinite(local).all(dim=1)).sum())
         raise Al3dError(f"{bad} frame embedding(s) are not finite: an activation left the f16x3 range "

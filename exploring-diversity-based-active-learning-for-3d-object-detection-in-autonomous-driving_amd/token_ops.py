@@ -1,23 +1,54 @@
-"""Device-side token-matrix primitives of the Swin-T image backbone (csrc/tokens.hip behind include/al3d.h's
-``al3d_tok_*``): LayerNorm over gathered rows, the f16x3 token GEMM with its fused epilogues, and 7 x 7 window
-attention.  torch tensors in, HIP kernels underneath; no CPU fallback.
+"""Device-side token-matrix primitives of the Swin-T image backbone and the TransFusion decoder (csrc/tokens.hip and
+csrc/tokens_bf16x6.hip behind include/al3d.h's ``al3d_tok_*``): LayerNorm over gathered rows, the token GEMM with its
+fused epilogues, 7 x 7 window attention and 16-channel-head attention.  torch tensors in, HIP kernels underneath; no CPU
+fallback.
+
+Arithmetic: ``linear``, ``window_attention``, ``window_attention_tokens`` and ``mha16`` read ``detector_ops.MATH`` at
+CALL time (``sweep_embeddings`` flips it when it re-runs a batch that left the f16x3 range).  ``f16x3`` runs the kernels
+of tokens.hip; ``bf16x6`` AND ``f32`` run those of tokens_bf16x6.hip -- there is no fp32-input token kernel, so on the
+token path ``AL3D_MATH=f32`` means bf16x6 (fp32-class accuracy over the full fp32 range).  The fused Swin kernels
+(``attn_block``, ``mlp``, ``patch_embed``) exist in f16x3 only: callers take the split forms under the other arithmetics.
 
 Activations are row matrices ``[rows, C]`` float32; "pair rows" (``pair=True``) hold the same bytes per row as the
 two f16 planes the f16x3 products multiply with (csrc/sp_rows.h) and only ever travel from a producing kernel to the
-GEMM that consumes them.
+GEMM that consumes them.  They exist under f16x3 only: ask ``pair_rows()`` instead of hard-coding ``pair=True``.
 """
 import numpy as np
 import torch
 
+from . import detector_ops as D
 from . import lib
-from .detector_ops import pack_dma_f16x3, split_f16x3
+from .detector_ops import pack_dma_f16x3, split_bf16x3, split_f16x3
 from .selector_ops import _dev, _ptr, _stream
 
 
+def arithmetic():
+    """The token kernels' arithmetic for ``detector_ops.MATH`` as it reads now: "f16x3" or "bf16x6" (also for "f32")."""
+    return "f16x3" if D.MATH == "f16x3" else "bf16x6"
+
+
+def pair_rows():
+    """Whether the token kernels can produce / consume pair rows now (f16 planes: f16x3 only)."""
+    return D.MATH == "f16x3"
+
+
+def _f16x3_only(what):
+    if D.MATH != "f16x3":
+        raise lib.Al3dError(f"{what}: the fused Swin kernels exist in f16x3 only (MATH={D.MATH}); take the split form")
+
+
+def _no_pair(what, *flags):
+    if any(flags) and not pair_rows():
+        raise lib.Al3dError(f"{what}: pair rows are f16 planes and exist under AL3D_MATH=f16x3 only (MATH={D.MATH}); "
+                            "ask token_ops.pair_rows()")
+
+
 class PackedLinear:
-    """``nn.Linear`` / 1x1 ``Conv1d`` weights in the token GEMM's format: LDS-DMA image of the (wh, wl) f16 planes, the
-    2^-s scale of the split (times ``scale``, e.g. a folded BatchNorm), the bias / shift.  ``pad_k`` / ``pad_n``
-    zero-pad the input / output channels (K must be a multiple of 16, N of 4)."""
+    """``nn.Linear`` / 1x1 ``Conv1d`` weights for the token GEMM.  Keeps the (padded) f32 weight and builds each
+    arithmetic's image on first use, once: f16x3 = LDS-DMA image of the (wh, wl) f16 planes + the 2^-s scale of the split
+    (times ``scale``, e.g. a folded BatchNorm); bf16x6 = ``split_bf16x3`` planes ``[3, N, K]`` + ``scale`` as given (or
+    none).  A sweep that flips ``detector_ops.MATH`` and back re-packs nothing.  ``pad_k`` / ``pad_n`` zero-pad the input /
+    output channels (K must be a multiple of 16, N of 4)."""
 
     def __init__(self, weight, bias=None, scale=None, pad_k=None, pad_n=None):
         w = weight.detach().float().reshape(weight.shape[0], -1)
@@ -31,12 +62,32 @@ class PackedLinear:
             raise lib.Al3dError(f"PackedLinear: in_features={self.k} must be a multiple of 16 (use pad_k)")
         if scale is not None:
             scale = torch.nn.functional.pad(scale.detach().float(), (0, pad_n - n)).to(w.device)
-        planes, sc = split_f16x3(w.view(self.n, 1, self.k), scale)
-        self.image = pack_dma_f16x3(planes).data
-        self.scale = sc
+            scale = scale.contiguous()
+        self.weight, self.scale_in = w, scale
+        self._images = {}
         self.bias = None
         if bias is not None:
             self.bias = torch.nn.functional.pad(bias.detach().float(), (0, pad_n - n)).to(w.device).contiguous()
+
+    def packed(self, arith):
+        """(weight image, per-channel scale or None) of ``arith`` ("f16x3" / "bf16x6"), built on first use."""
+        if arith not in self._images:
+            if arith == "f16x3":
+                planes, sc = split_f16x3(self.weight.view(self.n, 1, self.k), self.scale_in)
+                self._images[arith] = (pack_dma_f16x3(planes).data, sc)
+            elif arith == "bf16x6":
+                self._images[arith] = (split_bf16x3(self.weight), self.scale_in)
+            else:
+                raise lib.Al3dError(f"PackedLinear: no token GEMM in {arith!r} arithmetic")
+        return self._images[arith]
+
+    @property
+    def image(self):
+        return self.packed("f16x3")[0]
+
+    @property
+    def scale(self):
+        return self.packed("f16x3")[1]
 
 
 class PackedMlp:
@@ -114,6 +165,7 @@ class PackedAttnBlock:
 def attn_block(x, B, H, W, packed, shift, scale):
     """``x += proj(shifted_window_attention(LN(x)))`` in place on the f32 token rows ``[B * H * W, C]`` of ``B`` maps
     (7 x 7 windows, cyclic shift ``shift``, padding to multiples of 7 after the norm; one launch)."""
+    _f16x3_only("attn_block")
     x = _dev(x, torch.float32, "x")
     if x.dim() != 2 or x.shape[-1] != packed.C:
         raise lib.Al3dError(f"attn_block: x {tuple(x.shape)}, the weights have {packed.C} channels")
@@ -127,6 +179,7 @@ def attn_block(x, B, H, W, packed, shift, scale):
 
 def mlp(x, packed):
     """``x += fc2(gelu(fc1(LN(x))))`` in place on f32 token rows ``[T, 96]`` (one launch)."""
+    _f16x3_only("mlp")
     x = _dev(x, torch.float32, "x")
     if x.shape[-1] != packed.C:
         raise lib.Al3dError(f"mlp: x has {x.shape[-1]} channels, the weights {packed.C}")
@@ -157,6 +210,7 @@ class PackedPatchEmbed:
 def patch_embed(img, packed):
     """img ``[B, H, W, 3]`` channels-last (W a multiple of 4) -> token rows ``[B * ceil(H/4) * (W/4), 96]`` f32: projection
     (+ LayerNorm) in one launch."""
+    _f16x3_only("patch_embed")
     img = _dev(img, torch.float32, "img")
     B, H, W, ch = img.shape
     if ch != 3 or W % 4:
@@ -168,8 +222,11 @@ def patch_embed(img, packed):
     return out, (th, tw)
 
 
-def patch_rows(img, pair=True):
-    """img ``[B, H, W, 3]`` channels-last -> 4 x 4 patch rows ``[B * ceil(H/4) * ceil(W/4), 48]`` (k = (ky*4 + kx)*3 + c)."""
+def patch_rows(img, pair=None):
+    """img ``[B, H, W, 3]`` channels-last -> 4 x 4 patch rows ``[B * ceil(H/4) * ceil(W/4), 48]`` (k = (ky*4 + kx)*3 + c);
+    ``pair=None``: pair rows under f16x3."""
+    pair = pair_rows() if pair is None else pair
+    _no_pair("patch_rows", pair)
     img = _dev(img, torch.float32, "img")
     B, H, W, ch = img.shape
     if ch != 3:
@@ -183,6 +240,7 @@ def patch_rows(img, pair=True):
 def layernorm(x, gamma, beta, eps, rowmap=None, G=1, zero_out=False, rows_out=None, pair=False):
     """LN over ``G * C`` channels of (gathered) rows of ``x [rows, C]`` -> ``[rows_out, G * C]``; see
     ``al3d_tok_layernorm_f32``."""
+    _no_pair("layernorm", pair)
     x = _dev(x, torch.float32, "x")
     C = x.shape[-1]
     if rowmap is None:
@@ -198,7 +256,9 @@ def layernorm(x, gamma, beta, eps, rowmap=None, G=1, zero_out=False, rows_out=No
 
 
 def linear(a, packed, a_pair=False, act=None, residual=None, rowmap=None, out=None, out_rows=None, out_pair=False):
-    """``out[rowmap[m]] = act(a[m] @ W^T + b) + residual[rowmap[m]]``; ``residual`` may be ``out`` itself."""
+    """``out[rowmap[m]] = act(a[m] @ W^T + b) + residual[rowmap[m]]``; ``residual`` may be ``out`` itself.  Arithmetic from
+    ``detector_ops.MATH`` now; pair rows in or out under f16x3 only."""
+    _no_pair("linear", a_pair, out_pair)
     a = _dev(a, torch.float32, "a")
     M, K = a.shape
     if K != packed.k:
@@ -217,42 +277,63 @@ def linear(a, packed, a_pair=False, act=None, residual=None, rowmap=None, out=No
             out = alloc((M if out_rows is None else out_rows, packed.n), dtype=torch.float32, device=a.device)
     if residual is not None:
         residual = _dev(residual, torch.float32, "residual")
-    lib.call("al3d_tok_linear_f16x3", _ptr(a), int(a_pair), _ptr(packed.image), _ptr(packed.scale), _ptr(packed.bias),
-             M, K, packed.n, {None: 0, "gelu": 1, "relu": 2}[act], _ptr(residual), 0 if residual is None else residual.shape[-1],
-             _ptr(rowmap), _ptr(out), out.shape[-1], int(out_pair), _stream())
+    arith = arithmetic()
+    image, scale = packed.packed(arith)
+    act_code = {None: 0, "gelu": 1, "relu": 2}[act]
+    ldr = 0 if residual is None else residual.shape[-1]
+    if arith == "f16x3":
+        lib.call("al3d_tok_linear_f16x3", _ptr(a), int(a_pair), _ptr(image), _ptr(scale), _ptr(packed.bias),
+                 M, K, packed.n, act_code, _ptr(residual), ldr, _ptr(rowmap), _ptr(out), out.shape[-1], int(out_pair), _stream())
+    else:
+        lib.call("al3d_tok_linear_bf16x6", _ptr(a), _ptr(image), _ptr(scale), _ptr(packed.bias), M, K, packed.n, act_code,
+                 _ptr(residual), ldr, _ptr(rowmap), _ptr(out), out.shape[-1], _stream())
     return out
 
 
-def window_attention(qkv, table, heads, win_rows, win_cols, shift, scale, pair=True):
-    """qkv ``[nwin * 49, 3 C]`` in window order -> attention output ``[nwin * 49, C]`` (pair rows by default)."""
+def window_attention(qkv, table, heads, win_rows, win_cols, shift, scale, pair=None):
+    """qkv ``[nwin * 49, 3 C]`` in window order -> attention output ``[nwin * 49, C]`` (``pair=None``: pair rows where the
+    arithmetic has them, i.e. under f16x3)."""
+    pair = pair_rows() if pair is None else pair
+    _no_pair("window_attention", pair)
     qkv = _dev(qkv, torch.float32, "qkv")
     rows, c3 = qkv.shape
     C = c3 // 3
     nwin = rows // 49
     out = torch.empty((rows, C), dtype=torch.float32, device=qkv.device)
-    lib.call("al3d_tok_window_attention_f32", _ptr(qkv), _ptr(_dev(table, torch.float32, "table")), nwin, C, heads,
-             win_rows, win_cols, int(shift), float(scale), int(pair), _ptr(out), _stream())
+    if arithmetic() == "f16x3":
+        lib.call("al3d_tok_window_attention_f32", _ptr(qkv), _ptr(_dev(table, torch.float32, "table")), nwin, C, heads,
+                 win_rows, win_cols, int(shift), float(scale), int(pair), _ptr(out), _stream())
+    else:
+        lib.call("al3d_tok_window_attention_bf16x6", _ptr(qkv), _ptr(_dev(table, torch.float32, "table")), nwin, C, heads,
+                 win_rows, win_cols, int(shift), float(scale), _ptr(out), _stream())
     return out
 
 
-def window_attention_tokens(qkv, bias_qkv, table, B, H, W, heads, shift, scale, pair=True):
-    """qkv ``[B * H * W, 3 C]`` in TOKEN order -> attention output ``[B * H * W, C]`` in token order (pair rows by default):
-    shift, padding and window partition from the window's position; a padded position's q / k / v is ``bias_qkv``."""
+def window_attention_tokens(qkv, bias_qkv, table, B, H, W, heads, shift, scale, pair=None):
+    """qkv ``[B * H * W, 3 C]`` in TOKEN order -> attention output ``[B * H * W, C]`` in token order (``pair=None``: pair rows
+    under f16x3): shift, padding and window partition from the window's position; a padded position's q / k / v is
+    ``bias_qkv``."""
+    pair = pair_rows() if pair is None else pair
+    _no_pair("window_attention_tokens", pair)
     qkv = _dev(qkv, torch.float32, "qkv")
     rows, c3 = qkv.shape
     C = c3 // 3
     if rows != B * H * W:
         raise lib.Al3dError(f"window_attention_tokens: qkv has {rows} rows, {B} maps of {H} x {W} need {B * H * W}")
     out = torch.empty((rows, C), dtype=torch.float32, device=qkv.device)
-    lib.call("al3d_tok_window_attention_tokens_f32", _ptr(qkv), _ptr(_dev(bias_qkv, torch.float32, "bias_qkv")),
-             _ptr(_dev(table, torch.float32, "table")), B, H, W, C, heads, int(shift), float(scale), int(pair), _ptr(out), _stream())
+    if arithmetic() == "f16x3":
+        lib.call("al3d_tok_window_attention_tokens_f32", _ptr(qkv), _ptr(_dev(bias_qkv, torch.float32, "bias_qkv")),
+                 _ptr(_dev(table, torch.float32, "table")), B, H, W, C, heads, int(shift), float(scale), int(pair), _ptr(out), _stream())
+    else:
+        lib.call("al3d_tok_window_attention_tokens_bf16x6", _ptr(qkv), _ptr(_dev(bias_qkv, torch.float32, "bias_qkv")),
+                 _ptr(_dev(table, torch.float32, "table")), B, H, W, C, heads, int(shift), float(scale), _ptr(out), _stream())
     return out
 
 
 def mha16(q, k, v, B, Pq, Pk, heads, scale):
     """Attention core of ``nn.MultiheadAttention`` for 16-channel heads: q ``[B * Pq, >= heads * 16]``, k / v
     ``[B * Pk, ...]`` (column slices of wider row matrices are fine: the row pitch is the tensor's stride) ->
-    ``[B * Pq, heads * 16]``."""
+    ``[B * Pq, heads * 16]``.  Arithmetic from ``detector_ops.MATH`` now."""
     for t, name in ((q, "q"), (k, "k"), (v, "v")):
         if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1):
             raise lib.Al3dError(f"mha16: {name} must be a device float32 row matrix (unit column stride)")
@@ -260,7 +341,7 @@ def mha16(q, k, v, B, Pq, Pk, heads, scale):
         raise lib.Al3dError("mha16: row counts do not match B, Pq, Pk")
     out = torch.empty((B * Pq, heads * 16), dtype=torch.float32, device=q.device)
     ws = torch.empty(lib.load().al3d_tok_mha16_workspace_bytes(B, heads, Pq, Pk), dtype=torch.uint8, device=q.device)
-    lib.call("al3d_tok_mha16_f32", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), B, heads,
+    lib.call("al3d_tok_mha16_f32" if arithmetic() == "f16x3" else "al3d_tok_mha16_bf16x6", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), B, heads,
              Pq, Pk, float(scale), _ptr(out), out.shape[1], _ptr(ws), _stream())
     return out
 

@@ -841,6 +841,29 @@ int al3d_tok_window_attention_tokens_f32(const float* qkv, const float* bias_qkv
 int64_t al3d_tok_mha16_workspace_bytes(int B, int heads, int Pq, int Pk);
 int al3d_tok_mha16_f32(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, int B, int heads, int Pq,
                        int Pk, float scale, float* out, int ldo, void* workspace, void* stream);
+/* The token GEMM and the two attentions in bf16x6 arithmetic (csrc/tokens_bf16x6.hip; AL3D_MATH=bf16x6 / f32 and the
+ * AL3D_MATH=auto re-run on the token path): every fp32 operand split exactly into three bf16 pieces, a product = the six
+ * partial products of total order <= 2 in one fp32 accumulator, as al3d_conv2d_nhwc_bf16x6.  fp32-class accuracy over the
+ * full fp32 range: no operand has to stay below 65504.  f32 rows in and out (pair rows are f16 planes: none here);
+ * non-finite input gives non-finite output.
+ * al3d_tok_linear_bf16x6: the contract of al3d_tok_linear_f16x3 -- out[rowmap[m]] = act((a[m] . W^T) * scale + bias) +
+ *   residual[rowmap[m]] -- with W as al3d_split_bf16x3 planes [3][N][K] and scale [N] or null (the bf16 split has no
+ *   exponent to hand back: scale only carries a folded BatchNorm).  act 0 none / 1 exact (erf) GELU / 2 ReLU; rowmap null =
+ *   identity, -1 = row dropped; residual (pitch ldr) may alias out.  K % 16 == 0, N % 4 == 0.
+ * al3d_tok_window_attention_bf16x6 / al3d_tok_window_attention_tokens_bf16x6: the contracts of the two _f32 entries above
+ *   (window order; token order with bias_qkv for padded positions), q scale, k, v and the probabilities split three ways,
+ *   the softmax in fp32.
+ * al3d_tok_mha16_bf16x6: the contract of al3d_tok_mha16_f32 (strided q / k / v, key chunks of <= 1,024, the same combine),
+ *   workspace >= al3d_tok_mha16_workspace_bytes(). */
+int al3d_tok_linear_bf16x6(const float* a, const void* wgt_bf16x3, const float* scale, const float* bias, int64_t M, int K,
+                           int N, int act, const float* residual, int ldr, const int* rowmap, float* out, int ldc,
+                           void* stream);
+int al3d_tok_window_attention_bf16x6(const float* qkv, const float* table, int nwin, int C, int heads, int win_rows,
+                                     int win_cols, int shift, float scale, float* out, void* stream);
+int al3d_tok_window_attention_tokens_bf16x6(const float* qkv, const float* bias_qkv, const float* table, int B, int H, int W,
+                                            int C, int heads, int shift, float scale, float* out, void* stream);
+int al3d_tok_mha16_bf16x6(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, int B, int heads,
+                          int Pq, int Pk, float scale, float* out, int ldo, void* workspace, void* stream);
 
 /* CenterPoint head post-processing (bevfusion/mmdet3d/models/heads/bbox/centerpoint.py:637-884 with
  * core/bbox/coders/centerpoint_bbox_coders.py:62-225, ops/iou3d/src/iou3d_kernel.cu:244-331 and
