@@ -1,7 +1,7 @@
-// Pieces shared by the token kernels of both arithmetics (tokens.hip: f16x3, tokens_bf16x6.hip: bf16x6): vector
-// typedefs, the erf / GELU of the GEMM epilogues, the geometry of the 7 x 7 window kernel (parameter block, staged-row
-// swizzle, relative-position code, shifted-window region) and the head-dim-16 attention's parameter block and chunk
-// combine kernel.  Moved here verbatim from tokens.hip; nothing in this header depends on the operand format.
+// Pieces shared by the token kernels of both arithmetics (tokens.hip: f16x3, tokens_bf16x6.hip: bf16x6) that do not
+// depend on the operand format: vector typedefs, the zero row, the erf / GELU of the GEMM epilogues, the parameter blocks
+// and staged-row layout of the 7 x 7 window kernel, the head-dim-16 attention's parameter block and chunk combine kernel.
+// The attention kernels themselves, with the window geometry and softmax, are in tok_attention.h.
 #pragma once
 #include "al3d_common.h"
 
@@ -9,6 +9,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float tk_f32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void tk_lds_void;
 typedef const __attribute__((address_space(1))) void tk_gbl_void;
+
+static __device__ __attribute__((aligned(256))) float g_tok_zero[64];     // stays zero: source of rows beyond a matrix / window
 
 template <int N> __device__ __forceinline__ void tk_wait_vm()
 {

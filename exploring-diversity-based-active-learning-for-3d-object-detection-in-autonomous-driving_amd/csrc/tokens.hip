@@ -15,23 +15,25 @@
 //                                3-stage ring exactly as conv2d_f16x3_dma2_kernel, rows addressed directly;
 //                                epilogue: bias, exact (erf) GELU, residual, row SCATTER (window order -> token
 //                                order, padding rows dropped), f32 or pair rows out
-//   tok_window_attention_kernel  two waves per (window, head), one per query tile: S^T = K (Q scale)^T on the matrix
-//                                cores with both operands split (main + 2^-11 correction accumulators), + relative
-//                                position bias + shifted-window region mask computed from the window's position (no
-//                                mask tensor), softmax down the accumulator registers, O^T = V^T P^T with P taken
-//                                straight from the accumulators as the B operand (no LDS round trip), pair rows out;
+//   tok_window_attention_kernel<TkF16x3>  (tok_attention.h, shared with tokens_bf16x6.hip; TkF16x3 below is this
+//                                file's arithmetic) two waves per (window, head), one per query tile: S^T = K (Q scale)^T
+//                                on the matrix cores with both operands split (main + 2^-11 correction accumulators),
+//                                + relative position bias + shifted-window region mask computed from the window's
+//                                position (no mask tensor), softmax down the accumulator registers, O^T = V^T P^T with P
+//                                taken straight from the accumulators as the B operand (no LDS round trip), pair rows out;
 //                                reads qkv in window order or (token-order mode, embed 384 / 768) in the map's own order
 //   tok_mlp_f16x3_kernel         embed 96: LN2 + fc1 + exact GELU + fc2 + residual in one kernel (hidden rows stay in
 //                                registers, weights through an LDS-DMA ring)
 //   tok_attn_block_f16x3_kernel  embed 96 / 192: LN1 + qkv + window attention + proj + residual in one kernel; 2 NH
-//                                waves per window, K^T / V fragments through LDS, everything else in accumulators
+//                                waves per window, K^T / V fragments through LDS, everything else in accumulators;
+//                                window geometry, region mask and softmax are tok_attention.h's
 //   tok_patch_embed_f16x3_kernel Conv2d(3, 96, 4, 4) + LayerNorm of the patch embedding in one kernel
-//   tok_mha16_kernel (+ combine) the TransFusion decoder's multi-head attention (head dim 16)
+//   tok_mha16_kernel<TkF16x3> (+ combine)  the TransFusion decoder's multi-head attention (head dim 16; tok_attention.h)
 //
 // Nothing here calls a BLAS / MIOpen routine.  gfx950 only.
 #include "al3d_common.h"
 #include "sp_rows.h"
-#include "tok_shared.h"
+#include "tok_attention.h"
 #include <type_traits>
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -40,8 +42,6 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 #define TK_STAGE 16384      // bytes per ring stage: A 8 KB (128 rows x 16 channels f32 / pair) + B 8 KB
 #define TK_BOFF 8192
 #define TK_NS 3
-
-__device__ __attribute__((aligned(256))) float g_tok_zero[64];     // stays zero: source of rows beyond M
 
 __device__ __forceinline__ int tk_swz(int r) { return (r & 1) | (((r >> 3) & 1) << 1); }
 
@@ -864,7 +864,7 @@ extern "C" int al3d_tok_mlp_f16x3(float* x, int64_t T, int C, int hidden, const 
     return AL3D_OK;
 }
 
-// ------------------------------------------------------------------ 7 x 7 window attention, head dim 32
+// ------------------------------------------------------------------ window attention and head-dim-16 attention (tok_attention.h)
 
 // the f16x3 split of 8 values with the packed conversions of sp_split8 (3 instructions per element instead of 5); the
 // inputs are pinned first (see tk_split: the high part and the residual must see the same rounded fp32 value)
@@ -878,423 +878,71 @@ __device__ __forceinline__ void tk_split8p(float (&v)[8], f16x8& ph, f16x8& pl)
     pl = __builtin_bit_cast(f16x8, lo);
 }
 
-// Two waves (= one 128-thread workgroup) per (window, head), one 32-query tile each.  The head's q, k, v rows (49 x 128 B each, 1152+ B apart in
-// the qkv matrix) come in by LDS-DMA, eight whole rows per instruction (every 128-byte line fetched once, by one
-// instruction); a row's eight 16-byte chunks are stored permuted (chunk q at position q ^ ((row >> 1) & 7), applied
-// on the SOURCE side: the LDS side of a DMA is lane-linear) so that the fragment reads are conflict-free.
-// C-layout of v_mfma_f32_32x32x16: column = lane & 31, rows in the 16 registers
-// (row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)); S^T puts the KEYS on the rows, so a query's softmax runs down a
-// lane's registers (+ one exchange with lane ^ 32), and P^T is already the B operand of O^T = V^T P^T: registers
-// 8 s .. 8 s + 7 of a tile are k-step s, in the order key = 16 s + 8 (j >> 2) + 4 h + (j & 3) -- the V^T fragment
-// is read in that same order.  Both operands of both products are activations: each is split (xh, xl' = residual
-// x 2^11) and the product is  xh yh  +  2^-11 (xh yl' + xl' yh)  with the two brackets in separate accumulators.
-
-__global__ __launch_bounds__(128, 3) void tok_window_attention_kernel(TokAttnParams p)
-{
-    __shared__ __attribute__((aligned(1024))) unsigned char stg[3 * TK_ABYTES];    // k | q | v
-    __shared__ float tbl[1][176];
-    // two waves per (window, head): they share the staged q / k / v rows and take one 32-query tile each; K fragments are
-    // read (and split) where they are used instead of being held: <= 168 registers, three waves per SIMD, six workgroups
-    // per CU by LDS -- twelve resident waves with half the dependent chain each (one wave per item held 7 per CU)
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    const int item = blockIdx.x;
-    const int win = item / p.heads, head = item - win * p.heads;
-    const int c = lane & 31, h = lane >> 5;
-    const int ld = 3 * p.C;
-    const float* base = p.qkv + (int64_t)win * TK_NT * ld + head * 32;
-    const unsigned stg_base = (unsigned)(size_t)(tk_lds_void*)stg;
-    const int wi = win % (p.nwy * p.nwx), wb = win / (p.nwy * p.nwx), wy = wi / p.nwx, wx = wi - wy * p.nwx;
-    // token-order mode: token row of window position `row`, -1 for padding (shifted[hp] = padded[(hp + shift) % Hp])
-    auto token_of = [&](int row) __attribute__((always_inline)) -> int {
-        const int ty = (row * 37) >> 8, tx = row - ty * TK_WS;
-        int hs = wy * TK_WS + ty + p.shift, ws = wx * TK_WS + tx + p.shift;
-        hs -= hs >= p.nwy * TK_WS ? p.nwy * TK_WS : 0;
-        ws -= ws >= p.nwx * TK_WS ? p.nwx * TK_WS : 0;
-        return hs < p.H && ws < p.W ? (wb * p.H + hs) * p.W + ws : -1;
-    };
-    // the rows first (their latency is the longest: per row group ONE source row address serves the k, q and v pieces), then
-    // the position-bias table and the region codes in its shadow -- with the table load in front every item began by
-    // waiting for it before a single row was requested (35 % of an item's life by per-phase time stamps)
+// The arithmetic of the attention kernels (tok_attention.h): every operand is an activation, split (xh, xl' = residual
+// x 2^11); a product is  xh yh  +  2^-11 (xh yl' + xl' yh)  with the two brackets in separate accumulators.
+struct TkF16x3 {
+    struct Frag { f16x8 h, l; };
+    struct Acc { f32x16 m, c; };                         // main, 2^-11 correction
+    static constexpr int kWavesPerSimd = 3;              // <= 168 registers
+    static constexpr bool kPairRows = true;
+    static __device__ __forceinline__ void split8(float (&v)[8], Frag& o) { tk_split8p(v, o.h, o.l); }
+    static __device__ __forceinline__ void mac(const Frag& a, const Frag& b, Acc& acc)
     {
-        const int rl = lane >> 3, pos = lane & 7;
-#pragma unroll
-        for (int it0 = 0; it0 < 4; ++it0) {
-            const int it = 2 * it0 + wave;                      // the row groups of an array alternate between the waves
-            if (it >= 7) continue;
-            const int row = it * 8 + rl;
-            const int chunk = pos ^ ((row >> 1) & 7);
-            const bool live = row < TK_NT;
-            const float* rp = g_tok_zero;
-            if (live) {
-                rp = base + (int64_t)row * ld;
-                if (p.bias) {
-                    const int tok = token_of(row);
-                    rp = (tok >= 0 ? p.qkv + (int64_t)tok * ld : p.bias) + head * 32;
-                }
-            }
-            rp += chunk * 4;
-#pragma unroll
-            for (int arr = 0; arr < 3; ++arr) {
-                const int aoff = live ? (arr == 0 ? p.C : arr == 1 ? 0 : 2 * p.C) : 0;
-                const unsigned dst = __builtin_amdgcn_readfirstlane(stg_base + arr * TK_ABYTES + it * 1024);
-                __builtin_amdgcn_global_load_lds((tk_gbl_void*)(rp + aoff), (tk_lds_void*)(size_t)dst, 16, 0, 0);
-            }
-        }
+        acc.c = TK_MFMA(a.l, b.h, acc.c);
+        acc.c = TK_MFMA(a.h, b.l, acc.c);
+        acc.m = TK_MFMA(a.h, b.h, acc.m);
     }
-    float tv[2];
+    static __device__ __forceinline__ float value(const Acc& a, int r) { return a.m[r] + a.c[r] * 0.00048828125f; }
+    static __device__ __forceinline__ void rescale(Acc& a, float f)
+    {
 #pragma unroll
-    for (int k = 0; k < 2; ++k) { const int t = threadIdx.x + 128 * k; tv[k] = t < 169 ? p.table[t * p.heads + head] : 0.f; }
-    // shifted-window regions of the window's 7 rows / 7 columns, two bits each (uniform): tokens attend inside a region
-    int rycode = 0, rxcode = 0;
-    if (p.shift > 0) {
-        for (int t = 0; t < TK_WS; ++t) {
-            rycode |= tk_region1(wy * TK_WS + t, p.nwy * TK_WS, p.shift) << (2 * t);
-            rxcode |= tk_region1(wx * TK_WS + t, p.nwx * TK_WS, p.shift) << (2 * t);
-        }
+        for (int r = 0; r < 16; ++r) { a.m[r] *= f; a.c[r] *= f; }
     }
+    // group of 8 channels at dst as a pair row: xh[8] | xl'[8]; this lane owns elements 4 h .. 4 h + 3
+    static __device__ __forceinline__ void store_pair4(float* dst, int h, const float (&y)[4])
+    {
+        _Float16 hh[4], ll[4];
 #pragma unroll
-    for (int k = 0; k < 2; ++k) { const int t = threadIdx.x + 128 * k; if (t < 176) tbl[0][t] = tv[k]; }
-    tk_wait_vm<0>();
-    __syncthreads();                                   // both waves' shares of k, q and v have landed
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
-
-    const bool masked = p.shift > 0;
-    // one 32-query tile at a time (a real loop: the state of a tile -- 64 logit + 32 output accumulators -- is live only
-    // inside its iteration, which is what lets several waves share a SIMD)
-    for (int j = wave; j <= wave; ++j) {                // this wave's query tile
-        const int query = 32 * j + c;
-        f16x8 qh[2], ql[2];
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            tk_f32x4 lo, hi;
-            asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %3\n\ts_waitcnt lgkmcnt(0)"
-                         : "=&v"(lo), "=&v"(hi)
-                         : "v"(stg_base + TK_ABYTES + tk_arow_off(query, 4 * s + 2 * h)),
-                           "v"(stg_base + TK_ABYTES + tk_arow_off(query, 4 * s + 2 * h + 1))
-                         : "memory");
-            float qv[8] = {lo[0] * p.scale, lo[1] * p.scale, lo[2] * p.scale, lo[3] * p.scale,
-                                 hi[0] * p.scale, hi[1] * p.scale, hi[2] * p.scale, hi[3] * p.scale};
-            tk_split8p(qv, qh[s], ql[s]);
-        }
-        f32x16 sm[2], sc[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { sm[i][r] = 0.f; sc[i][r] = 0.f; }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                tk_f32x4 lo, hi;                                 // K fragment (A operand: rows = keys), split here
-                asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %3\n\ts_waitcnt lgkmcnt(0)"
-                             : "=&v"(lo), "=&v"(hi)
-                             : "v"(stg_base + tk_arow_off(32 * i + c, 4 * s + 2 * h)), "v"(stg_base + tk_arow_off(32 * i + c, 4 * s + 2 * h + 1))
-                             : "memory");
-                f16x8 kh, kl;
-                { float kv[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]}; tk_split8p(kv, kh, kl); }
-                sc[i] = TK_MFMA(kl, qh[s], sc[i]);
-                sc[i] = TK_MFMA(kh, ql[s], sc[i]);
-                sm[i] = TK_MFMA(kh, qh[s], sm[i]);
-            }
-        // logits -> probabilities, in place in sm[i] (rows = keys, column = this lane's query)
-        const int qq = query < TK_NT ? query : TK_NT - 1;
-        const int qy = (qq * 37) >> 8, qx = qq - TK_WS * qy;
-        const int qcode = qq + 6 * qy + 84;                          // 13 y + x + 84
-        // bit k of `diff`: key k lies in ANOTHER shifted-window region than this query (-100 on its logit).  A bit mask per
-        // query instead of a region lookup per element: that form (an LDS read behind `if (masked)`) made hipcc serialise
-        // 64 LDS round trips per tile
-        unsigned dlo = 0u, dhi = 0u;
-        if (masked) {
-            const int myry = (rycode >> (2 * qy)) & 3, myrx = (rxcode >> (2 * qx)) & 3;
-            unsigned colmask = 0u;
-            unsigned long long same = 0ull;
-#pragma unroll
-            for (int t = 0; t < TK_WS; ++t) colmask |= (unsigned)(((rxcode >> (2 * t)) & 3) == myrx) << t;
-#pragma unroll
-            for (int t = 0; t < TK_WS; ++t)
-                if (((rycode >> (2 * t)) & 3) == myry) same |= (unsigned long long)colmask << (TK_WS * t);
-            const unsigned long long diff = ~same >> (4 * h);        // the lane's keys are c + 4 h with compile-time c
-            dlo = (unsigned)diff;
-            dhi = (unsigned)(diff >> 32);
-        }
-        const float* tq = tbl[0] + qcode;
-        float mx = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            float tb[16];                                            // the tile's 16 bias lookups first, then their uses
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int cc = 32 * i + (r & 3) + 8 * (r >> 2);      // key = cc + 4 h
-                tb[r] = tq[-(h ? tk_kcode(cc + 4) : tk_kcode(cc))];
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int cc = 32 * i + (r & 3) + 8 * (r >> 2);
-                float v = sm[i][r] + sc[i][r] * 0.00048828125f;
-                v += tb[r];
-                if (masked) v += (float)(((cc < 32 ? dlo : dhi) >> (cc & 31)) & 1u) * -100.0f;
-                if (cc + 4 >= TK_NT) v = (cc >= TK_NT || h) ? -INFINITY : v;
-                sm[i][r] = v;
-                mx = fmaxf(mx, v);
-            }
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        float sum = 0.f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                // e^(v - mx) = 2^((v - mx) log2 e): the product in two pieces so that the argument of v_exp_f32 carries no
-                // rounding of its own beyond 2^-24 relative (|v - mx| <= ~100 here)
-                const float d = sm[i][r] - mx;
-                const float t = __builtin_fmaf(d, 1.44269502162933349609f, d * 1.92596299112661746e-8f);
-                const float e = __builtin_amdgcn_exp2f(t);
-                sm[i][r] = e;
-                sum += e;
-            }
-        sum += __shfl_xor(sum, 32);
-        const float inv = 1.0f / sum;
-        // O^T[d][query] = sum_key V[key][d] P[query][key]; P is normalised AFTER the product (one multiply per output)
-        f32x16 om, oc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { om[r] = 0.f; oc[r] = 0.f; }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                float vv[8];
-                unsigned va[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const int key = 32 * i + 16 * s + 8 * (e >> 2) + 4 * h + (e & 3);
-                    va[e] = stg_base + 2 * TK_ABYTES + tk_arow_off(key, c >> 2) + ((c & 3) << 2);
-                }
-                // one block: the wait belongs to the reads (separate asm statements could be scheduled apart from their uses)
-                asm volatile("ds_read_b32 %0, %8\n\tds_read_b32 %1, %9\n\tds_read_b32 %2, %10\n\tds_read_b32 %3, %11\n\t"
-                             "ds_read_b32 %4, %12\n\tds_read_b32 %5, %13\n\tds_read_b32 %6, %14\n\tds_read_b32 %7, %15\n\t"
-                             "s_waitcnt lgkmcnt(0)"
-                             : "=&v"(vv[0]), "=&v"(vv[1]), "=&v"(vv[2]), "=&v"(vv[3]), "=&v"(vv[4]), "=&v"(vv[5]), "=&v"(vv[6]), "=&v"(vv[7])
-                             : "v"(va[0]), "v"(va[1]), "v"(va[2]), "v"(va[3]), "v"(va[4]), "v"(va[5]), "v"(va[6]), "v"(va[7])
-                             : "memory");
-                f16x8 vh, vl, ph, pl;
-                tk_split8p(vv, vh, vl);
-                float pv[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) pv[e] = sm[i][8 * s + e];
-                tk_split8p(pv, ph, pl);
-                oc = TK_MFMA(vl, ph, oc);
-                oc = TK_MFMA(vh, pl, oc);
-                om = TK_MFMA(vh, ph, om);
-            }
-        if (query >= TK_NT) continue;
-        // rows of O^T are d = (r & 3) + 8 (r >> 2) + 4 h: four consecutive channels per register quad
-        int64_t out_row = (int64_t)win * TK_NT + query;
-        if (p.bias) {
-            out_row = token_of(query);
-            if (out_row < 0) continue;                       // a padded position's output is cropped
-        }
-        float* orow = p.out + out_row * p.C + head * 32;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            float y[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) y[e] = (om[4 * g + e] + oc[4 * g + e] * 0.00048828125f) * inv;
-            if (p.pair) {                                // group g of the head: xh[8] | xl'[8]; this lane owns elements 4 h .. 4 h + 3
-                _Float16 hh[4], ll[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) tk_split(y[e], hh[e], ll[e]);
-                typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-                const h4 vh4 = {hh[0], hh[1], hh[2], hh[3]}, vl4 = {ll[0], ll[1], ll[2], ll[3]};
-                char* o = reinterpret_cast<char*>(orow + 8 * g);
-                *reinterpret_cast<uint2*>(o + 8 * h) = __builtin_bit_cast(uint2, vh4);
-                *reinterpret_cast<uint2*>(o + 16 + 8 * h) = __builtin_bit_cast(uint2, vl4);
-            } else {
-                *reinterpret_cast<float4*>(orow + 8 * g + 4 * h) = make_float4(y[0], y[1], y[2], y[3]);
-            }
-        }
+        for (int e = 0; e < 4; ++e) tk_split(y[e], hh[e], ll[e]);
+        typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+        const h4 vh4 = {hh[0], hh[1], hh[2], hh[3]}, vl4 = {ll[0], ll[1], ll[2], ll[3]};
+        char* o = reinterpret_cast<char*>(dst);
+        *reinterpret_cast<uint2*>(o + 8 * h) = __builtin_bit_cast(uint2, vh4);
+        *reinterpret_cast<uint2*>(o + 16 + 8 * h) = __builtin_bit_cast(uint2, vl4);
     }
-}
+};
+template __global__ void tok_window_attention_kernel<TkF16x3>(TokAttnParams);
+template __global__ void tok_mha16_kernel<TkF16x3>(TokMhaParams);
 
 extern "C" int al3d_tok_window_attention_f32(const float* qkv, const float* table, int nwin, int C, int heads,
                                              int win_rows, int win_cols, int shift, float scale, int out_pair,
                                              float* out, void* stream)
 {
-    AL3D_REQUIRE(qkv && table && out, "al3d_tok_window_attention_f32: null pointer");
-    AL3D_REQUIRE(nwin >= 0 && heads >= 1 && C == heads * 32, "al3d_tok_window_attention_f32: C=%d must be heads (%d) x 32", C, heads);
-    AL3D_REQUIRE(win_rows >= 1 && win_cols >= 1 && nwin % (win_rows * win_cols) == 0,
-                 "al3d_tok_window_attention_f32: nwin=%d is not a whole number of %d x %d window grids", nwin, win_rows, win_cols);
-    AL3D_REQUIRE(shift >= 0 && shift < TK_WS, "al3d_tok_window_attention_f32: shift=%d outside [0, 7)", shift);
-    AL3D_REQUIRE((((uintptr_t)qkv | (uintptr_t)out) & 15) == 0, "al3d_tok_window_attention_f32: qkv / out must be 16-byte aligned");
-    if (nwin == 0) return AL3D_OK;
-    TokAttnParams p{qkv, table, out, nwin, C, heads, win_rows, win_cols, shift, scale, out_pair, nullptr, 0, 0};
-    const int64_t items = (int64_t)nwin * heads;
-    hipLaunchKernelGGL(tok_window_attention_kernel, dim3((unsigned)items), dim3(128), 0, (hipStream_t)stream, p);
-    AL3D_CHECK_LAUNCH("tok_window_attention_kernel");
-    return AL3D_OK;
+    const TokAttnParams p{qkv, table, out, nwin, C, heads, win_rows, win_cols, shift, scale, out_pair, nullptr, 0, 0};
+    return tok_window_attention_launch<TkF16x3>("al3d_tok_window_attention_f32", false, 0, p, stream);
 }
 
 extern "C" int al3d_tok_window_attention_tokens_f32(const float* qkv, const float* bias_qkv, const float* table, int B, int H,
                                                     int W, int C, int heads, int shift, float scale, int out_pair,
                                                     float* out, void* stream)
 {
-    AL3D_REQUIRE(B >= 0 && H >= 1 && W >= 1 && (int64_t)B * H * W < ((int64_t)1 << 31), "al3d_tok_window_attention_tokens_f32: bad map size");
-    if (B == 0) return AL3D_OK;
-    AL3D_REQUIRE(qkv && bias_qkv && table && out, "al3d_tok_window_attention_tokens_f32: null pointer (a model without qkv bias passes zeros)");
-    AL3D_REQUIRE(heads >= 1 && C == heads * 32, "al3d_tok_window_attention_tokens_f32: C=%d must be heads (%d) x 32", C, heads);
-    AL3D_REQUIRE(shift >= 0 && shift < TK_WS, "al3d_tok_window_attention_tokens_f32: shift=%d outside [0, 7)", shift);
-    AL3D_REQUIRE((((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)bias_qkv) & 15) == 0, "al3d_tok_window_attention_tokens_f32: qkv / bias / out must be 16-byte aligned");
-    const int nwy = (H + TK_WS - 1) / TK_WS, nwx = (W + TK_WS - 1) / TK_WS;
-    const int64_t items = (int64_t)B * nwy * nwx * heads;
-    AL3D_REQUIRE(items < ((int64_t)1 << 31), "al3d_tok_window_attention_tokens_f32: too many (window, head) items");
-    TokAttnParams p{qkv, table, out, B * nwy * nwx, C, heads, nwy, nwx, shift, scale, out_pair, bias_qkv, H, W};
-    hipLaunchKernelGGL(tok_window_attention_kernel, dim3((unsigned)items), dim3(128), 0, (hipStream_t)stream, p);
-    AL3D_CHECK_LAUNCH("tok_window_attention_kernel");
-    return AL3D_OK;
-}
-
-// ------------------------------------------------------------------ multi-head attention, head dim 16, any key count
-// The TransFusion query decoder (bevfusion/mmdet3d/models/utils/transformer.py:71-112: nn.MultiheadAttention with 8
-// heads of 16 channels; 200 queries against themselves, then against the 180 x 180 = 32,400 BEV cells).
-// One wave per (sample, head, 32-query tile, key chunk): S^T = K (Q scale)^T per 32-key tile -- head dim 16 is exactly
-// one k-step of v_mfma_f32_32x32x16 -- an online softmax down the accumulator registers (running max / sum per query
-// = per lane), and O^T += V^T P^T with P taken from the accumulators as the B operand (rows of O^T = the 16 channels;
-// the upper half of the 32-row tile is idle).  Both operands split as in the window kernel (main + 2^-11 correction
-// accumulators).  Each wave writes (max, sum, O[16]) of its chunk; tok_mha16_combine_kernel merges the chunks.
-
-__global__ __launch_bounds__(64) void tok_mha16_kernel(TokMhaParams p)
-{
-    const int lane = threadIdx.x, c = lane & 31, h = lane >> 5;
-    int id = blockIdx.x;
-    const int chunk = id % p.chunks; id /= p.chunks;
-    const int qt = id % p.qtiles; id /= p.qtiles;
-    const int head = id % p.heads;
-    const int b = id / p.heads;
-    const int query = qt * 32 + c;
-    f16x8 qh, ql;
-    {
-        float qv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (query < p.Pq) {
-            const float* qp = p.q + ((int64_t)b * p.Pq + query) * p.ldq + head * 16 + 8 * h;
-            const float4 a = *reinterpret_cast<const float4*>(qp), b4 = *reinterpret_cast<const float4*>(qp + 4);
-            qv[0] = a.x * p.scale; qv[1] = a.y * p.scale; qv[2] = a.z * p.scale; qv[3] = a.w * p.scale;
-            qv[4] = b4.x * p.scale; qv[5] = b4.y * p.scale; qv[6] = b4.z * p.scale; qv[7] = b4.w * p.scale;
-        }
-        tk_split8(qv, qh, ql);
-    }
-    const int key0 = chunk * p.keys_per_chunk;
-    const int key1 = key0 + p.keys_per_chunk < p.Pk ? key0 + p.keys_per_chunk : p.Pk;
-    const float* kb = p.k + (int64_t)b * p.Pk * p.ldk + head * 16;
-    const float* vb = p.v + (int64_t)b * p.Pk * p.ldv + head * 16;
-    float run_max = -INFINITY, run_sum = 0.f;
-    f32x16 om, oc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { om[r] = 0.f; oc[r] = 0.f; }
-    for (int kt = key0; kt < key1; kt += 32) {
-        // K tile: A operand, lane (key c, half h) holds K[key][8 h .. 8 h + 7]
-        f16x8 kh, kl;
-        {
-            float kv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            if (kt + c < key1) {
-                const float* kp = kb + (int64_t)(kt + c) * p.ldk + 8 * h;
-                const float4 a = *reinterpret_cast<const float4*>(kp), b4 = *reinterpret_cast<const float4*>(kp + 4);
-                kv[0] = a.x; kv[1] = a.y; kv[2] = a.z; kv[3] = a.w; kv[4] = b4.x; kv[5] = b4.y; kv[6] = b4.z; kv[7] = b4.w;
-            }
-            tk_split8(kv, kh, kl);
-        }
-        // V^T fragments of the tile's two k-steps (issued early: their latency hides behind the logits)
-        float vv[2][8];
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int key = kt + 16 * s + 8 * (e >> 2) + 4 * h + (e & 3);
-                vv[s][e] = (c < 16 && key < key1) ? vb[(int64_t)key * p.ldv + c] : 0.f;
-            }
-        f32x16 sm, sc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { sm[r] = 0.f; sc[r] = 0.f; }
-        sc = TK_MFMA(kl, qh, sc);
-        sc = TK_MFMA(kh, ql, sc);
-        sm = TK_MFMA(kh, qh, sm);
-        float mx = run_max;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int key = kt + (r & 3) + 8 * (r >> 2) + 4 * h;
-            const float v = key < key1 ? sm[r] + sc[r] * 0.00048828125f : -INFINITY;
-            sm[r] = v;
-            mx = fmaxf(mx, v);
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32));              // every tile holds at least one real key: mx is finite
-        const float resc = __builtin_amdgcn_exp2f((run_max - mx) * 1.44269504088896340736f);     // 0 on the first tile
-        float sum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float d = sm[r] - mx;
-            const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(d, 1.44269502162933349609f, d * 1.92596299112661746e-8f));
-            sm[r] = e;
-            sum += e;
-        }
-        sum += __shfl_xor(sum, 32);
-        run_sum = run_sum * resc + sum;
-        run_max = mx;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { om[r] *= resc; oc[r] *= resc; }
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            f16x8 vh, vl, ph, pl;
-            tk_split8(vv[s], vh, vl);
-            float pv[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) pv[e] = sm[8 * s + e];
-            tk_split8(pv, ph, pl);
-            oc = TK_MFMA(vl, ph, oc);
-            oc = TK_MFMA(vh, pl, oc);
-            om = TK_MFMA(vh, ph, om);
-        }
-    }
-    // rows of O^T: d = (r & 3) + 8 (r >> 2) + 4 h; d < 16 <=> r < 8
-    float* o = p.part + ((((int64_t)b * p.heads + head) * p.chunks + chunk) * (p.qtiles * 32) + query) * 18;
-    if (h == 0) { o[0] = run_max; o[1] = run_sum; }
-#pragma unroll
-    for (int r = 0; r < 8; ++r) o[2 + (r & 3) + 8 * (r >> 2) + 4 * h] = om[r] + oc[r] * 0.00048828125f;
+    const TokAttnParams p{qkv, table, out, 0, C, heads, 0, 0, shift, scale, out_pair, bias_qkv, H, W};
+    return tok_window_attention_launch<TkF16x3>("al3d_tok_window_attention_tokens_f32", true, B, p, stream);
 }
 
 extern "C" int64_t al3d_tok_mha16_workspace_bytes(int B, int heads, int Pq, int Pk)
 {
     if (B < 1 || heads < 1 || Pq < 1 || Pk < 1) return 0;
-    const int qtiles = (Pq + 31) / 32;
-    int chunks = (Pk + 1023) / 1024;
+    int qtiles, chunks, keys_per_chunk;
+    tok_mha16_plan(Pq, Pk, qtiles, chunks, keys_per_chunk);
     return al3d_align((int64_t)B * heads * chunks * qtiles * 32 * 18 * 4, 256);
 }
 
 extern "C" int al3d_tok_mha16_f32(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, int B, int heads,
                                   int Pq, int Pk, float scale, float* out, int ldo, void* workspace, void* stream)
 {
-    AL3D_REQUIRE(q && k && v && out && workspace, "al3d_tok_mha16_f32: null pointer");
-    AL3D_REQUIRE(B >= 1 && heads >= 1 && Pq >= 1 && Pk >= 1, "al3d_tok_mha16_f32: bad shape");
-    AL3D_REQUIRE(ldq >= heads * 16 && ldk >= heads * 16 && ldv >= heads * 16 && ldo >= heads * 16 && ldq % 4 == 0 && ldk % 4 == 0,
-                 "al3d_tok_mha16_f32: row pitches must cover heads x 16 channels (q, k pitches multiples of 4)");
-    AL3D_REQUIRE((((uintptr_t)q | (uintptr_t)k) & 15) == 0, "al3d_tok_mha16_f32: q / k must be 16-byte aligned");
-    TokMhaParams p;
-    p.q = q; p.k = k; p.v = v; p.part = (float*)workspace;
-    p.B = B; p.heads = heads; p.Pq = Pq; p.Pk = Pk; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv;
-    p.qtiles = (Pq + 31) / 32;
-    p.chunks = (Pk + 1023) / 1024;
-    p.keys_per_chunk = (int)al3d_align(al3d_cdiv(Pk, p.chunks), 32);
-    p.chunks = (int)al3d_cdiv(Pk, p.keys_per_chunk);       // no empty chunk: every partial holds at least one key
-    p.scale = scale;
-    const int64_t waves = (int64_t)B * heads * p.qtiles * p.chunks;
-    AL3D_REQUIRE(waves < ((int64_t)1 << 31), "al3d_tok_mha16_f32: too many work items");
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(tok_mha16_kernel, dim3((unsigned)waves), dim3(64), 0, s, p);
-    AL3D_CHECK_LAUNCH("tok_mha16_kernel");
-    const int64_t n = (int64_t)B * heads * Pq * 16;
-    hipLaunchKernelGGL(tok_mha16_combine_kernel, dim3((unsigned)al3d_cdiv(n, 256)), dim3(256), 0, s, (const float*)workspace, B,
-                       heads, p.chunks, p.qtiles * 32, Pq, out, ldo);
-    AL3D_CHECK_LAUNCH("tok_mha16_combine_kernel");
-    return AL3D_OK;
+    return tok_mha16_launch<TkF16x3>("al3d_tok_mha16_f32", q, ldq, k, ldk, v, ldv, B, heads, Pq, Pk, scale, out, ldo, workspace,
+                                     stream);
 }
 
 // ------------------------------------------------------------------ fused attention half of a Swin block
@@ -1356,13 +1004,9 @@ __global__ __launch_bounds__(C * 4 * WPB, 3) void tok_attn_block_f16x3_kernel(To
     const int nwin = p.B * p.nwy * p.nwx;
     const bool live = (int)blockIdx.x * WPB + lw < nwin;   // the last workgroup of an odd window count runs one window dry
     const int win = live ? blockIdx.x * WPB + lw : nwin - 1;
-    const int wi = win % (p.nwy * p.nwx), b = win / (p.nwy * p.nwx), wy = wi / p.nwx, wx = wi - wy * p.nwx;
+    const TkWinPos w = tk_win_pos(win, p.nwy, p.nwx);
     auto token_of = [&](int row) __attribute__((always_inline)) -> int {
-        const int ty = row / TK_WS, tx = row - ty * TK_WS;
-        int hs = wy * TK_WS + ty + p.shift, ws = wx * TK_WS + tx + p.shift;
-        hs -= hs >= p.nwy * TK_WS ? p.nwy * TK_WS : 0;
-        ws -= ws >= p.nwx * TK_WS ? p.nwx * TK_WS : 0;
-        return live && row < TK_NT && hs < p.H && ws < p.W ? (b * p.H + hs) * p.W + ws : -1;
+        return live && row < TK_NT ? tk_token_of(row, w, p.nwy, p.nwx, p.shift, p.H, p.W) : -1;
     };
 
     // ---- the weight stream of this wave: steps [0, KC) = k or v part, [KC, 2 KC) = q, [2 KC, 3 KC) = proj
@@ -1388,12 +1032,8 @@ __global__ __launch_bounds__(C * 4 * WPB, 3) void tok_attn_block_f16x3_kernel(To
         bv[0] = p.bias_qkv[(part == 0 ? C : 0) + 32 * hd + fr];
         bv[1] = part == 0 ? p.bias_proj[32 * hd + fr] : p.bias_qkv[2 * C + 32 * hd + fr];
     }
-    int rycode = 0, rxcode = 0;
-    if (p.shift > 0)
-        for (int t = 0; t < TK_WS; ++t) {
-            rycode |= tk_region1(wy * TK_WS + t, p.nwy * TK_WS, p.shift) << (2 * t);
-            rxcode |= tk_region1(wx * TK_WS + t, p.nwx * TK_WS, p.shift) << (2 * t);
-        }
+    int rycode, rxcode;
+    tk_region_codes(w, p.nwy, p.nwx, p.shift, rycode, rxcode);
     // ---- 1. LayerNorm: C / 24 lanes per row (4 or 8), three groups of 8 channels per lane, every row of the window in one
     // pass (the per-row work -- token index, divisions, root -- is then done by 4 or 8 lanes, not by 16 for three passes);
     // rows 49 .. 63 and padding positions come out as zero rows: keys with zero weight, finite values
@@ -1580,59 +1220,13 @@ __global__ __launch_bounds__(C * 4 * WPB, 3) void tok_attn_block_f16x3_kernel(To
                 sc[i] = TK_MFMA(kh, ql[s], sc[i]);
                 sm[i] = TK_MFMA(kh, qh[s], sm[i]);
             }
-        const int qq = query < TK_NT ? query : TK_NT - 1;
-        const int qy = (qq * 37) >> 8, qx = qq - TK_WS * qy;
-        const int qcode = qq + 6 * qy + 84;                          // 13 y + x + 84
-        // bit k of `diff`: key k lies in ANOTHER shifted-window region than this query (-100 on its logit)
-        unsigned dlo = 0u, dhi = 0u;
-        if (masked) {
-            const int myry = (rycode >> (2 * qy)) & 3, myrx = (rxcode >> (2 * qx)) & 3;
-            unsigned colmask = 0u;
-            unsigned long long same = 0ull;
-#pragma unroll
-            for (int t = 0; t < TK_WS; ++t) colmask |= (unsigned)(((rxcode >> (2 * t)) & 3) == myrx) << t;
-#pragma unroll
-            for (int t = 0; t < TK_WS; ++t)
-                if (((rycode >> (2 * t)) & 3) == myry) same |= (unsigned long long)colmask << (TK_WS * t);
-            const unsigned long long diff = ~same >> (4 * fh);       // the lane's keys are c + 4 fh with compile-time c
-            dlo = (unsigned)diff;
-            dhi = (unsigned)(diff >> 32);
-        }
-        const float* tq = tbl + qcode;
-        float mx = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            float tb[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int c = 32 * i + (r & 3) + 8 * (r >> 2);       // key = c + 4 fh
-                tb[r] = tq[-(fh ? tk_kcode(c + 4) : tk_kcode(c))];
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int c = 32 * i + (r & 3) + 8 * (r >> 2);
-                float v = sm[i][r] + sc[i][r] * 0.00048828125f;
-                v += tb[r];
-                if (masked) v += (float)(((c < 32 ? dlo : dhi) >> (c & 31)) & 1u) * -100.0f;
-                if (c + 4 >= TK_NT) v = (c >= TK_NT || fh) ? -INFINITY : v;
-                sm[i][r] = v;
-                mx = fmaxf(mx, v);
-            }
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        float sum = 0.f;
+        // logits -> probabilities in sm[i]: relative position bias from the table, shifted-window regions as a bit mask per
+        // query (tok_attention.h)
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float d = sm[i][r] - mx;
-                const float t = __builtin_fmaf(d, 1.44269502162933349609f, d * 1.92596299112661746e-8f);
-                const float e = __builtin_amdgcn_exp2f(t);
-                sm[i][r] = e;
-                sum += e;
-            }
-        sum += __shfl_xor(sum, 32);
-        const float inv = 1.0f / sum;
+            for (int r = 0; r < 16; ++r) sm[i][r] += sc[i][r] * 0.00048828125f;
+        const float inv = tk_window_softmax(sm, query, fh, tbl, masked, rycode, rxcode);
         f32x16 om, oc;
         zero16(om); zero16(oc);
         const unsigned char* vf = vb + hd * 8192 + lane * 16;

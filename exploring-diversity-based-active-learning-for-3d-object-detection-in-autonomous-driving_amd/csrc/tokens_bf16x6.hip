@@ -4,25 +4,24 @@
 // as the six partial products of total order <= 2 (x1w1, x1w2, x2w1, x1w3, x2w2, x3w1), accumulated in fp32 by
 // v_mfma_f32_32x32x16_bf16, smallest first.  bf16 has fp32's exponent: no operand needs |x| < 65504, no piece needs a
 // power-of-two lift, and all six products go into ONE accumulator.  The bf16 product has the fragment shapes of the f16
-// one, so row / lane orders, the staged-row swizzle, the softmax down the accumulator registers and the chunk combine
-// are those of tokens.hip (tok_shared.h).  f32 rows in and out: pair rows are f16 planes and do not exist here.
+// one, so the two attention kernels are tok_attention.h's templates -- the code tokens.hip runs -- instantiated for this
+// file's arithmetic TkBf16x6 (split three ways, six products).  f32 rows in and out: pair rows are f16 planes and do not
+// exist here.
 //
-//   tok_linear_bf16x6_kernel            128 x 128 x 16 tile staged through LDS like conv2d_bf16x6_kernel; activations
-//                                       split while they are staged, weights pre-split [3][N][K]; epilogue: scale,
-//                                       bias, exact GELU / ReLU, residual, row scatter
-//   tok_window_attention_bf16x6_kernel  q (scaled), k, v and the probabilities split three ways; softmax in fp32 VALU
-//   tok_mha16_bf16x6_kernel             the same for 16-channel heads, chunked online softmax, + the shared combine
+//   tok_linear_bf16x6_kernel               128 x 128 x 16 tile staged through LDS like conv2d_bf16x6_kernel; activations
+//                                          split while they are staged, weights pre-split [3][N][K]; epilogue: scale,
+//                                          bias, exact GELU / ReLU, residual, row scatter
+//   tok_window_attention_kernel<TkBf16x6>  q (scaled), k, v and the probabilities split three ways; softmax in fp32 VALU
+//   tok_mha16_kernel<TkBf16x6>             the same for 16-channel heads, chunked online softmax, + the shared combine
 //
 // Written for correctness over the full fp32 range, not for speed.  gfx950 only.
 #include "al3d_common.h"
-#include "tok_shared.h"
+#include "tok_attention.h"
 
 typedef __bf16 tb_bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 tb_bf16x4 __attribute__((ext_vector_type(4)));
 
 #define TB_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
-
-static __device__ __attribute__((aligned(256))) float g_tokb_zero[64];     // stays zero: source of staged rows beyond the window
 
 // x = a + b + c exactly (8 + 8 + 8 significand bits).  x is pinned to ONE rounded fp32 value first (tokens.hip's
 // tk_split: with the producer's arithmetic visible the high piece and the residual must see the same value).
@@ -202,347 +201,42 @@ extern "C" int al3d_tok_linear_bf16x6(const float* a, const void* wgt_bf16x3, co
     return AL3D_OK;
 }
 
-// ------------------------------------------------------------------ 7 x 7 window attention, head dim 32, bf16x6
-// tok_window_attention_kernel with the bf16 split: two waves per (window, head), one 32-query tile each; the head's q, k,
-// v rows staged as f32 by LDS-DMA with the same source-side chunk permutation; S^T = K (Q scale)^T with the keys on the
-// accumulator rows, relative position bias + region mask + softmax down the registers in fp32, O^T = V^T P^T with P taken
-// from the accumulators as the B operand.  Each product is six bf16 MFMAs into one accumulator.
-__global__ __launch_bounds__(128, 2) void tok_window_attention_bf16x6_kernel(TokAttnParams p)
-{
-    __shared__ __attribute__((aligned(1024))) unsigned char stg[3 * TK_ABYTES];    // k | q | v
-    __shared__ float tbl[176];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    const int item = blockIdx.x;
-    const int win = item / p.heads, head = item - win * p.heads;
-    const int c = lane & 31, h = lane >> 5;
-    const int ld = 3 * p.C;
-    const float* base = p.qkv + (int64_t)win * TK_NT * ld + head * 32;
-    const unsigned stg_base = (unsigned)(size_t)(tk_lds_void*)stg;
-    const int wi = win % (p.nwy * p.nwx), wb = win / (p.nwy * p.nwx), wy = wi / p.nwx, wx = wi - wy * p.nwx;
-    // token-order mode: token row of window position `row`, -1 for padding (shifted[hp] = padded[(hp + shift) % Hp])
-    auto token_of = [&](int row) __attribute__((always_inline)) -> int {
-        const int ty = (row * 37) >> 8, tx = row - ty * TK_WS;
-        int hs = wy * TK_WS + ty + p.shift, ws = wx * TK_WS + tx + p.shift;
-        hs -= hs >= p.nwy * TK_WS ? p.nwy * TK_WS : 0;
-        ws -= ws >= p.nwx * TK_WS ? p.nwx * TK_WS : 0;
-        return hs < p.H && ws < p.W ? (wb * p.H + hs) * p.W + ws : -1;
-    };
-    {
-        const int rl = lane >> 3, pos = lane & 7;
-#pragma unroll
-        for (int it0 = 0; it0 < 4; ++it0) {
-            const int it = 2 * it0 + wave;                      // the row groups of an array alternate between the waves
-            if (it >= 7) continue;
-            const int row = it * 8 + rl;
-            const int chunk = pos ^ ((row >> 1) & 7);
-            const bool live = row < TK_NT;
-            const float* rp = g_tokb_zero;
-            if (live) {
-                rp = base + (int64_t)row * ld;
-                if (p.bias) {
-                    const int tok = token_of(row);
-                    rp = (tok >= 0 ? p.qkv + (int64_t)tok * ld : p.bias) + head * 32;
-                }
-            }
-            rp += chunk * 4;
-#pragma unroll
-            for (int arr = 0; arr < 3; ++arr) {
-                const int aoff = live ? (arr == 0 ? p.C : arr == 1 ? 0 : 2 * p.C) : 0;
-                const unsigned dst = __builtin_amdgcn_readfirstlane(stg_base + arr * TK_ABYTES + it * 1024);
-                __builtin_amdgcn_global_load_lds((tk_gbl_void*)(rp + aoff), (tk_lds_void*)(size_t)dst, 16, 0, 0);
-            }
-        }
-    }
-    float tv[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) { const int t = threadIdx.x + 128 * k; tv[k] = t < 169 ? p.table[t * p.heads + head] : 0.f; }
-    // shifted-window regions of the window's 7 rows / 7 columns, two bits each (uniform): tokens attend inside a region
-    int rycode = 0, rxcode = 0;
-    if (p.shift > 0) {
-        for (int t = 0; t < TK_WS; ++t) {
-            rycode |= tk_region1(wy * TK_WS + t, p.nwy * TK_WS, p.shift) << (2 * t);
-            rxcode |= tk_region1(wx * TK_WS + t, p.nwx * TK_WS, p.shift) << (2 * t);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 2; ++k) { const int t = threadIdx.x + 128 * k; if (t < 176) tbl[t] = tv[k]; }
-    tk_wait_vm<0>();
-    __syncthreads();                                   // both waves' shares of k, q and v have landed
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");                     // the staged rows were written by the DMA, not by a store the compiler saw
-
-    const bool masked = p.shift > 0;
-    const float* stgf = reinterpret_cast<const float*>(stg);
-    auto frag = [&](int arr, int row, int s, TbOp& o, float mul) __attribute__((always_inline)) {
-        // channels 16 s + 8 h .. + 7 of staged row `row` of array arr (0 k, 1 q, 2 v)
-        const float4 lo = *reinterpret_cast<const float4*>(stgf + ((arr * TK_ABYTES + tk_arow_off(row, 4 * s + 2 * h)) >> 2));
-        const float4 hi = *reinterpret_cast<const float4*>(stgf + ((arr * TK_ABYTES + tk_arow_off(row, 4 * s + 2 * h + 1)) >> 2));
-        const float v[8] = {lo.x * mul, lo.y * mul, lo.z * mul, lo.w * mul, hi.x * mul, hi.y * mul, hi.z * mul, hi.w * mul};
-        tb_split8(v, o);
-    };
-    {
-        const int query = 32 * wave + c;                   // this wave's query tile
-        TbOp q[2];
-#pragma unroll
-        for (int s = 0; s < 2; ++s) frag(1, query, s, q[s], p.scale);
-        f32x16 sm[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sm[i][r] = 0.f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                TbOp k;                                     // K fragment (A operand: rows = keys), split here
-                frag(0, 32 * i + c, s, k, 1.0f);
-                tb_mac6(k, q[s], sm[i]);
-            }
-        // logits -> probabilities, in place in sm[i] (rows = keys, column = this lane's query)
-        const int qq = query < TK_NT ? query : TK_NT - 1;
-        const int qy = (qq * 37) >> 8, qx = qq - TK_WS * qy;
-        const int qcode = qq + 6 * qy + 84;                          // 13 y + x + 84
-        // bit k of `diff`: key k lies in ANOTHER shifted-window region than this query (-100 on its logit)
-        unsigned dlo = 0u, dhi = 0u;
-        if (masked) {
-            const int myry = (rycode >> (2 * qy)) & 3, myrx = (rxcode >> (2 * qx)) & 3;
-            unsigned colmask = 0u;
-            unsigned long long same = 0ull;
-#pragma unroll
-            for (int t = 0; t < TK_WS; ++t) colmask |= (unsigned)(((rxcode >> (2 * t)) & 3) == myrx) << t;
-#pragma unroll
-            for (int t = 0; t < TK_WS; ++t)
-                if (((rycode >> (2 * t)) & 3) == myry) same |= (unsigned long long)colmask << (TK_WS * t);
-            const unsigned long long diff = ~same >> (4 * h);        // the lane's keys are c + 4 h with compile-time c
-            dlo = (unsigned)diff;
-            dhi = (unsigned)(diff >> 32);
-        }
-        const float* tq = tbl + qcode;
-        float mx = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int cc = 32 * i + (r & 3) + 8 * (r >> 2);      // key = cc + 4 h
-                float v = sm[i][r] + tq[-(h ? tk_kcode(cc + 4) : tk_kcode(cc))];
-                if (masked) v += (float)(((cc < 32 ? dlo : dhi) >> (cc & 31)) & 1u) * -100.0f;
-                if (cc + 4 >= TK_NT) v = (cc >= TK_NT || h) ? -INFINITY : v;
-                sm[i][r] = v;
-                mx = fmaxf(mx, v);
-            }
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        float sum = 0.f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                // e^(v - mx) = 2^((v - mx) log2 e): the product in two pieces, as in tok_window_attention_kernel
-                const float d = sm[i][r] - mx;
-                const float t = __builtin_fmaf(d, 1.44269502162933349609f, d * 1.92596299112661746e-8f);
-                const float e = __builtin_amdgcn_exp2f(t);
-                sm[i][r] = e;
-                sum += e;
-            }
-        sum += __shfl_xor(sum, 32);
-        const float inv = 1.0f / sum;
-        // O^T[d][query] = sum_key V[key][d] P[query][key]; P is normalised AFTER the product (one multiply per output)
-        f32x16 om;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) om[r] = 0.f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                float vv[8], pv[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const int key = 32 * i + 16 * s + 8 * (e >> 2) + 4 * h + (e & 3);
-                    vv[e] = stgf[((2 * TK_ABYTES + tk_arow_off(key, c >> 2)) >> 2) + (c & 3)];
-                    pv[e] = sm[i][8 * s + e];
-                }
-                TbOp v, pr;
-                tb_split8(vv, v);
-                tb_split8(pv, pr);
-                tb_mac6(v, pr, om);
-            }
-        if (query >= TK_NT) return;
-        // rows of O^T are d = (r & 3) + 8 (r >> 2) + 4 h: four consecutive channels per register quad
-        int64_t out_row = (int64_t)win * TK_NT + query;
-        if (p.bias) {
-            out_row = token_of(query);
-            if (out_row < 0) return;                         // a padded position's output is cropped
-        }
-        float* orow = p.out + out_row * p.C + head * 32;
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-            *reinterpret_cast<float4*>(orow + 8 * g + 4 * h) =
-                make_float4(om[4 * g] * inv, om[4 * g + 1] * inv, om[4 * g + 2] * inv, om[4 * g + 3] * inv);
-    }
-}
+// ------------------------------------------------------------------ window attention and head-dim-16 attention (tok_attention.h)
+// q (scaled), k, v and the probabilities split three ways; each product is six bf16 MFMAs into one accumulator.  f32 rows
+// out: pair rows are f16 planes and do not exist here.
+struct TkBf16x6 {
+    using Frag = TbOp;
+    using Acc = f32x16;
+    static constexpr int kWavesPerSimd = 2;
+    static constexpr bool kPairRows = false;
+    static __device__ __forceinline__ void split8(float (&v)[8], Frag& o) { tb_split8(v, o); }
+    static __device__ __forceinline__ void mac(const Frag& a, const Frag& b, Acc& acc) { tb_mac6(a, b, acc); }
+    static __device__ __forceinline__ float value(const Acc& a, int r) { return a[r]; }
+    static __device__ __forceinline__ void rescale(Acc& a, float f) { a *= f; }
+};
+template __global__ void tok_window_attention_kernel<TkBf16x6>(TokAttnParams);
+template __global__ void tok_mha16_kernel<TkBf16x6>(TokMhaParams);
 
 extern "C" int al3d_tok_window_attention_bf16x6(const float* qkv, const float* table, int nwin, int C, int heads,
                                                 int win_rows, int win_cols, int shift, float scale, float* out,
                                                 void* stream)
 {
-    AL3D_REQUIRE(qkv && table && out, "al3d_tok_window_attention_bf16x6: null pointer");
-    AL3D_REQUIRE(nwin >= 0 && heads >= 1 && C == heads * 32, "al3d_tok_window_attention_bf16x6: C=%d must be heads (%d) x 32", C, heads);
-    AL3D_REQUIRE(win_rows >= 1 && win_cols >= 1 && nwin % (win_rows * win_cols) == 0,
-                 "al3d_tok_window_attention_bf16x6: nwin=%d is not a whole number of %d x %d window grids", nwin, win_rows, win_cols);
-    AL3D_REQUIRE(shift >= 0 && shift < TK_WS, "al3d_tok_window_attention_bf16x6: shift=%d outside [0, 7)", shift);
-    AL3D_REQUIRE((((uintptr_t)qkv | (uintptr_t)out) & 15) == 0, "al3d_tok_window_attention_bf16x6: qkv / out must be 16-byte aligned");
-    if (nwin == 0) return AL3D_OK;
-    const int64_t items = (int64_t)nwin * heads;
-    AL3D_REQUIRE(items < ((int64_t)1 << 31), "al3d_tok_window_attention_bf16x6: too many (window, head) items");
-    TokAttnParams p{qkv, table, out, nwin, C, heads, win_rows, win_cols, shift, scale, 0, nullptr, 0, 0};
-    hipLaunchKernelGGL(tok_window_attention_bf16x6_kernel, dim3((unsigned)items), dim3(128), 0, (hipStream_t)stream, p);
-    AL3D_CHECK_LAUNCH("tok_window_attention_bf16x6_kernel");
-    return AL3D_OK;
+    const TokAttnParams p{qkv, table, out, nwin, C, heads, win_rows, win_cols, shift, scale, 0, nullptr, 0, 0};
+    return tok_window_attention_launch<TkBf16x6>("al3d_tok_window_attention_bf16x6", false, 0, p, stream);
 }
 
 extern "C" int al3d_tok_window_attention_tokens_bf16x6(const float* qkv, const float* bias_qkv, const float* table, int B,
                                                        int H, int W, int C, int heads, int shift, float scale,
                                                        float* out, void* stream)
 {
-    AL3D_REQUIRE(B >= 0 && H >= 1 && W >= 1 && (int64_t)B * H * W < ((int64_t)1 << 31), "al3d_tok_window_attention_tokens_bf16x6: bad map size");
-    if (B == 0) return AL3D_OK;
-    AL3D_REQUIRE(qkv && bias_qkv && table && out, "al3d_tok_window_attention_tokens_bf16x6: null pointer (a model without qkv bias passes zeros)");
-    AL3D_REQUIRE(heads >= 1 && C == heads * 32, "al3d_tok_window_attention_tokens_bf16x6: C=%d must be heads (%d) x 32", C, heads);
-    AL3D_REQUIRE(shift >= 0 && shift < TK_WS, "al3d_tok_window_attention_tokens_bf16x6: shift=%d outside [0, 7)", shift);
-    AL3D_REQUIRE((((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)bias_qkv) & 15) == 0, "al3d_tok_window_attention_tokens_bf16x6: qkv / bias / out must be 16-byte aligned");
-    const int nwy = (H + TK_WS - 1) / TK_WS, nwx = (W + TK_WS - 1) / TK_WS;
-    const int64_t items = (int64_t)B * nwy * nwx * heads;
-    AL3D_REQUIRE(items < ((int64_t)1 << 31), "al3d_tok_window_attention_tokens_bf16x6: too many (window, head) items");
-    TokAttnParams p{qkv, table, out, B * nwy * nwx, C, heads, nwy, nwx, shift, scale, 0, bias_qkv, H, W};
-    hipLaunchKernelGGL(tok_window_attention_bf16x6_kernel, dim3((unsigned)items), dim3(128), 0, (hipStream_t)stream, p);
-    AL3D_CHECK_LAUNCH("tok_window_attention_bf16x6_kernel");
-    return AL3D_OK;
-}
-
-// ------------------------------------------------------------------ multi-head attention, head dim 16, bf16x6
-// tok_mha16_kernel with the bf16 split: one wave per (sample, head, 32-query tile, key chunk), online softmax down the
-// accumulator registers, (max, sum, O[16]) per chunk, merged by tok_mha16_combine_kernel (tok_shared.h).
-__global__ __launch_bounds__(64) void tok_mha16_bf16x6_kernel(TokMhaParams p)
-{
-    const int lane = threadIdx.x, c = lane & 31, h = lane >> 5;
-    int id = blockIdx.x;
-    const int chunk = id % p.chunks; id /= p.chunks;
-    const int qt = id % p.qtiles; id /= p.qtiles;
-    const int head = id % p.heads;
-    const int b = id / p.heads;
-    const int query = qt * 32 + c;
-    TbOp q;
-    {
-        float qv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (query < p.Pq) {
-            const float* qp = p.q + ((int64_t)b * p.Pq + query) * p.ldq + head * 16 + 8 * h;
-            const float4 a = *reinterpret_cast<const float4*>(qp), b4 = *reinterpret_cast<const float4*>(qp + 4);
-            qv[0] = a.x * p.scale; qv[1] = a.y * p.scale; qv[2] = a.z * p.scale; qv[3] = a.w * p.scale;
-            qv[4] = b4.x * p.scale; qv[5] = b4.y * p.scale; qv[6] = b4.z * p.scale; qv[7] = b4.w * p.scale;
-        }
-        tb_split8(qv, q);
-    }
-    const int key0 = chunk * p.keys_per_chunk;
-    const int key1 = key0 + p.keys_per_chunk < p.Pk ? key0 + p.keys_per_chunk : p.Pk;
-    const float* kb = p.k + (int64_t)b * p.Pk * p.ldk + head * 16;
-    const float* vb = p.v + (int64_t)b * p.Pk * p.ldv + head * 16;
-    float run_max = -INFINITY, run_sum = 0.f;
-    f32x16 om;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) om[r] = 0.f;
-    for (int kt = key0; kt < key1; kt += 32) {
-        // K tile: A operand, lane (key c, half h) holds K[key][8 h .. 8 h + 7]
-        TbOp k;
-        {
-            float kv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            if (kt + c < key1) {
-                const float* kp = kb + (int64_t)(kt + c) * p.ldk + 8 * h;
-                const float4 a = *reinterpret_cast<const float4*>(kp), b4 = *reinterpret_cast<const float4*>(kp + 4);
-                kv[0] = a.x; kv[1] = a.y; kv[2] = a.z; kv[3] = a.w; kv[4] = b4.x; kv[5] = b4.y; kv[6] = b4.z; kv[7] = b4.w;
-            }
-            tb_split8(kv, k);
-        }
-        // V^T fragments of the tile's two k-steps (issued early: their latency hides behind the logits)
-        float vv[2][8];
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int key = kt + 16 * s + 8 * (e >> 2) + 4 * h + (e & 3);
-                vv[s][e] = (c < 16 && key < key1) ? vb[(int64_t)key * p.ldv + c] : 0.f;
-            }
-        f32x16 sm;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sm[r] = 0.f;
-        tb_mac6(k, q, sm);
-        float mx = run_max;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int key = kt + (r & 3) + 8 * (r >> 2) + 4 * h;
-            const float v = key < key1 ? sm[r] : -INFINITY;
-            sm[r] = v;
-            mx = fmaxf(mx, v);
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32));              // every tile holds at least one real key: mx is finite
-        const float resc = __builtin_amdgcn_exp2f((run_max - mx) * 1.44269504088896340736f);     // 0 on the first tile
-        float sum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float d = sm[r] - mx;
-            const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(d, 1.44269502162933349609f, d * 1.92596299112661746e-8f));
-            sm[r] = e;
-            sum += e;
-        }
-        sum += __shfl_xor(sum, 32);
-        run_sum = run_sum * resc + sum;
-        run_max = mx;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) om[r] *= resc;
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            float pv[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) pv[e] = sm[8 * s + e];
-            TbOp v, pr;
-            tb_split8(vv[s], v);
-            tb_split8(pv, pr);
-            tb_mac6(v, pr, om);
-        }
-    }
-    // rows of O^T: d = (r & 3) + 8 (r >> 2) + 4 h; d < 16 <=> r < 8
-    float* o = p.part + ((((int64_t)b * p.heads + head) * p.chunks + chunk) * (p.qtiles * 32) + query) * 18;
-    if (h == 0) { o[0] = run_max; o[1] = run_sum; }
-#pragma unroll
-    for (int r = 0; r < 8; ++r) o[2 + (r & 3) + 8 * (r >> 2) + 4 * h] = om[r];
+    const TokAttnParams p{qkv, table, out, 0, C, heads, 0, 0, shift, scale, 0, bias_qkv, H, W};
+    return tok_window_attention_launch<TkBf16x6>("al3d_tok_window_attention_tokens_bf16x6", true, B, p, stream);
 }
 
 extern "C" int al3d_tok_mha16_bf16x6(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, int B,
                                      int heads, int Pq, int Pk, float scale, float* out, int ldo, void* workspace,
                                      void* stream)
 {
-    AL3D_REQUIRE(q && k && v && out && workspace, "al3d_tok_mha16_bf16x6: null pointer");
-    AL3D_REQUIRE(B >= 1 && heads >= 1 && Pq >= 1 && Pk >= 1, "al3d_tok_mha16_bf16x6: bad shape");
-    AL3D_REQUIRE(ldq >= heads * 16 && ldk >= heads * 16 && ldv >= heads * 16 && ldo >= heads * 16 && ldq % 4 == 0 && ldk % 4 == 0,
-                 "al3d_tok_mha16_bf16x6: row pitches must cover heads x 16 channels (q, k pitches multiples of 4)");
-    AL3D_REQUIRE((((uintptr_t)q | (uintptr_t)k) & 15) == 0, "al3d_tok_mha16_bf16x6: q / k must be 16-byte aligned");
-    TokMhaParams p;
-    p.q = q; p.k = k; p.v = v; p.part = (float*)workspace;
-    p.B = B; p.heads = heads; p.Pq = Pq; p.Pk = Pk; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv;
-    p.qtiles = (Pq + 31) / 32;
-    p.chunks = (Pk + 1023) / 1024;
-    p.keys_per_chunk = (int)al3d_align(al3d_cdiv(Pk, p.chunks), 32);
-    p.chunks = (int)al3d_cdiv(Pk, p.keys_per_chunk);       // no empty chunk: every partial holds at least one key
-    p.scale = scale;
-    const int64_t waves = (int64_t)B * heads * p.qtiles * p.chunks;
-    AL3D_REQUIRE(waves < ((int64_t)1 << 31), "al3d_tok_mha16_bf16x6: too many work items");
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(tok_mha16_bf16x6_kernel, dim3((unsigned)waves), dim3(64), 0, s, p);
-    AL3D_CHECK_LAUNCH("tok_mha16_bf16x6_kernel");
-    const int64_t n = (int64_t)B * heads * Pq * 16;
-    hipLaunchKernelGGL(tok_mha16_combine_kernel, dim3((unsigned)al3d_cdiv(n, 256)), dim3(256), 0, s, (const float*)workspace, B,
-                       heads, p.chunks, p.qtiles * 32, Pq, out, ldo);
-    AL3D_CHECK_LAUNCH("tok_mha16_combine_kernel");
-    return AL3D_OK;
+    return tok_mha16_launch<TkBf16x6>("al3d_tok_mha16_bf16x6", q, ldq, k, ldk, v, ldv, B, heads, Pq, Pk, scale, out, ldo,
+                                      workspace, stream);
 }

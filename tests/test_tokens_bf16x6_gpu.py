@@ -143,6 +143,22 @@ def test_gemm_refuses_bad_arguments(epi):
         T.linear(epi["a"], pk, out=torch.empty(epi["M"], epi["N"] + 2, device=DEV))       # ldc no multiple of 4
 
 
+def test_window_attention_refuses_2_31_items():
+    """nwin * heads = 2^31 (window, head) items do not fit a grid: both window-order entries refuse them by name.  (Without
+    the check the launch itself fails as an invalid configuration: no kernel ever runs over these small tensors.)"""
+    from al3d import lib
+    qkv, out = torch.zeros(49, 3 * 1024, device=DEV), torch.zeros(49, 1024, device=DEV)
+    table = torch.zeros(169, 32, device=DEV)
+    stream = torch.cuda.current_stream().cuda_stream
+    nwin, C, heads = 2 ** 26, 1024, 32
+    with pytest.raises(lib.Al3dError, match="too many"):
+        lib.call("al3d_tok_window_attention_f32", qkv.data_ptr(), table.data_ptr(), nwin, C, heads, 1, 1, 0, 32 ** -0.5, 0,
+                 out.data_ptr(), stream)
+    with pytest.raises(lib.Al3dError, match="too many"):
+        lib.call("al3d_tok_window_attention_bf16x6", qkv.data_ptr(), table.data_ptr(), nwin, C, heads, 1, 1, 0, 32 ** -0.5,
+                 out.data_ptr(), stream)
+
+
 def test_nonfinite_input_propagates():
     from al3d import token_ops as T
     g = torch.Generator().manual_seed(2)
