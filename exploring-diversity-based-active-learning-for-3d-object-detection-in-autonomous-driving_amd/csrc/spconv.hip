@@ -16,6 +16,7 @@
 // round trip and results are deterministic.
 #include "al3d_common.h"
 #include "al3d_scan.h"
+#include "sp_sites.h"
 
 struct SpDims { int B, D, H, W; };
 
@@ -640,6 +641,36 @@ extern "C" int64_t al3d_sp_down_sites_blocked_workspace_bytes(int B, int OD, int
     return sp_down_sites_ws(B, OD, OH, OW, true);
 }
 
+// The passes after the marking one: workspace (laid out as sp_down_sites_ws says) holds one flag byte per cell of `words` 32-cell
+// words; packs them, scans the popcounts and numbers the marked cells of grid `go` in ascending cell order.
+template <bool BLOCKED>
+static int sp_number_marked(void* workspace, int64_t words, SpDims go, int* grid_out, int* coords_out, int* counter, int cap,
+                            hipStream_t s)
+{
+    const int64_t fb = al3d_align(words * 32, 256), wb = al3d_align(words * 4, 256);
+    unsigned char* flags = (unsigned char*)workspace;
+    unsigned* bits = (unsigned*)(flags + fb);
+    int* cnt = (int*)(flags + fb + wb);
+    int* wscan = (int*)(flags + fb + 2 * wb);
+    void* scan_ws = flags + fb + 3 * wb;
+    hipLaunchKernelGGL(sp_down_pack_kernel, dim3(blocks_for(words, 256)), dim3(256), 0, s, flags, words, bits, cnt);
+    int rc = al3d_exclusive_scan_i32(cnt, wscan, words, scan_ws, s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(sp_down_assign_kernel<BLOCKED>, dim3(blocks_for(words, 256)), dim3(256), 0, s, bits, wscan,
+                       words, go, grid_out, coords_out, cap);
+    hipLaunchKernelGGL(sp_count_tail_kernel, dim3(1), dim3(64), 0, s, bits, wscan, words, counter);
+    return AL3D_OK;
+}
+
+// for csrc/spconv_mod.hip (sp_sites.h): raster numbering of the cells its own marking pass flagged
+int al3d_sp_number_marked_raster(void* workspace, int B, int OD, int OH, int OW, int* grid_out, int* coords_out, int* counter,
+                                 int cap, hipStream_t stream)
+{
+    SpDims go = {B, OD, OH, OW};
+    return sp_number_marked<false>(workspace, (sp_down_cells(B, OD, OH, OW, false) + 31) / 32, go, grid_out, coords_out, counter,
+                                   cap, stream);
+}
+
 template <bool BLOCKED>
 static int sp_down_sites_impl(const int* coords_in, int n_in, const int* ksize, const int* stride,
                               const int* pad, int B, int OD, int OH, int OW, int* grid_out,
@@ -653,12 +684,7 @@ static int sp_down_sites_impl(const int* coords_in, int n_in, const int* ksize, 
     AL3D_REQUIRE(((uintptr_t)coords_out & 15) == 0 && ((uintptr_t)workspace & 15) == 0,
                  "al3d_sp_down_sites: coords_out / workspace must be 16-byte aligned");
     const int64_t words = (cells + 31) / 32;
-    const int64_t fb = al3d_align(words * 32, 256), wb = al3d_align(words * 4, 256);
     unsigned char* flags = (unsigned char*)workspace;
-    unsigned* bits = (unsigned*)(flags + fb);
-    int* cnt = (int*)(flags + fb + wb);
-    int* wscan = (int*)(flags + fb + 2 * wb);
-    void* scan_ws = flags + fb + 3 * wb;
     if (n_in > 0) {
         AL3D_REQUIRE(coords_in, "al3d_sp_down_sites: null coords");
         if (hipMemsetAsync(flags, 0, (size_t)words * 32, s) != hipSuccess)
@@ -667,12 +693,8 @@ static int sp_down_sites_impl(const int* coords_in, int n_in, const int* ksize, 
         SpDims go = {B, OD, OH, OW};
         hipLaunchKernelGGL(sp_down_mark_kernel<BLOCKED>, dim3(blocks_for(n_in, 256)), dim3(256), 0, s, coords_in, n_in,
                            q, go, flags);
-        hipLaunchKernelGGL(sp_down_pack_kernel, dim3(blocks_for(words, 256)), dim3(256), 0, s, flags, words, bits, cnt);
-        int rc = al3d_exclusive_scan_i32(cnt, wscan, words, scan_ws, s);
+        int rc = sp_number_marked<BLOCKED>(workspace, words, go, grid_out, coords_out, counter, cap, s);
         if (rc) return rc;
-        hipLaunchKernelGGL(sp_down_assign_kernel<BLOCKED>, dim3(blocks_for(words, 256)), dim3(256), 0, s, bits, wscan,
-                           words, go, grid_out, coords_out, cap);
-        hipLaunchKernelGGL(sp_count_tail_kernel, dim3(1), dim3(64), 0, s, bits, wscan, words, counter);
     } else if (hipMemsetAsync(counter, 0, 4, s) != hipSuccess) {
         return al3d_fail(AL3D_ELAUNCH, "al3d_sp_down_sites: memset failed");
     }

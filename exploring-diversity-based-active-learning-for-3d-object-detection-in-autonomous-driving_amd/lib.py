@@ -232,6 +232,18 @@ SIGNATURES = {
                                                         c_p]),
     "al3d_tok_mha16_bf16x6": (c_int, [c_p, c_int, c_p, c_int, c_p, c_int, c_int, c_int, c_int, c_int, c_flt, c_p, c_int, c_p,
                                       c_p]),
+    "al3d_sp_coords_check": (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p]),
+    "al3d_sp_maxpool_f32": (c_int, [c_p, c_p, c_i64, c_int, c_int, c_int, c_int, c_p, c_p]),
+    "al3d_sp_inverse_table": (c_int, [c_p, c_i64, c_int, c_int, c_int, c_p, c_p]),
+    "al3d_sp_inverse_table_tiles": (c_int, [c_p, c_i64, c_int, c_int, c_int, c_p, c_int, c_p, c_p]),
+    "al3d_sp_up_sites_workspace_bytes": (c_i64, [c_int, c_int, c_int, c_int]),
+    "al3d_sp_up_sites": (c_int, [c_p, c_int, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_p,
+                                 c_p, c_int, c_p, c_p]),
+    "al3d_sp_up_table": (c_int, [c_p, c_int, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_p, c_p]),
+    "al3d_sp_up_table_tiles": (c_int, [c_p, c_int, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_p,
+                                       c_int, c_p, c_p]),
+    "al3d_sp_conv_any_f32": (c_int, [c_p, c_p, c_int, c_p, c_int, c_int, c_p, c_p, c_p, c_int, c_p, c_int,
+                                     c_p]),
 }
 
 _lib = None

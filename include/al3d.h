@@ -938,6 +938,47 @@ int64_t al3d_seg_classify_workspace_bytes(int N, int H, int W);
 int al3d_seg_classify_f32(const float* in, const float* w, const float* b, int N, int H, int W, int C, int K,
                           float* prob, float* entropy_sum, int* area, void* workspace, void* stream);
 
+/* ---------------------------------------------------------------- spconv-1.x module surface (csrc/spconv_mod.hip)
+ * What al3d.spconv needs beside the encoder's entry points above.  All of it deterministic: integer work, f32 comparisons
+ * and fixed-order f32 FMA chains, no float atomic.
+ *
+ * Bounds check of a caller's coordinate rows [n][4] (b, z, y, x), 16-byte aligned: *status (device int, zeroed here) gets
+ * bit 0 / 1 / 2 / 3 set when some row's b / z / y / x lies outside [0,B) / [0,D) / [0,H) / [0,W).  Reads nothing but
+ * `coords`; B*D*H*W < 2^31.  Duplicate rows are not detected.  The reference has no such check: spconv indexes its grid by
+ * whatever it is handed (spconv_ops.h:51-120, getIndicePair). */
+int al3d_sp_coords_check(const int* coords, int n, int B, int D, int H, int W, int* status, void* stream);
+/* SparseMaxPool3d over a tap-major table nbr [K][ld] (al3d_sp_down_table, ld >= n_out): out[o][c] = max over the taps with
+ * nbr[k][o] >= 0 of feats[nbr[k][o]][c], any C >= 1.  zero_floor != 0: the running maximum starts at 0, the reference's
+ * zero-initialised output (pool_ops.h:34, maxpool.cc:36); 0: at -inf, the true maximum.  A NaN input never wins the `<`
+ * comparison (pool_ops.h:34). */
+int al3d_sp_maxpool_f32(const float* feats, const int* nbr, int64_t ld, int K, int C, int n_out, int zero_floor, float* out,
+                        void* stream);
+/* SparseInverseConv3d's rulebook from the paired forward layer's table nbr_fwd [K][ld_fwd] over n_out outputs and n_in
+ * inputs: nbr_inv[k][i] = o where nbr_fwd[k][o] == i, else -1 (one writer per entry); nbr_inv is [K][max(n_in, 1)], or
+ * [K][pitch] + per-tile tap masks (pitch = al3d_sp_table_pitch(n_in)) for the tiled kernels.  K <= 27.  Replaces
+ * spconv_ops.h:260-361 run with `inverse` set (the pairs' two columns swapped). */
+int al3d_sp_inverse_table(const int* nbr_fwd, int64_t ld_fwd, int K, int n_out, int n_in, int* nbr_inv, void* stream);
+int al3d_sp_inverse_table_tiles(const int* nbr_fwd, int64_t ld_fwd, int K, int n_out, int n_in, int* nbr_inv, int pitch,
+                                unsigned* tile_mask, void* stream);
+/* SparseConvTranspose3d's rulebook (geometry.h:88-141, 197-245: getValidOutPosTranspose / getIndicePairsDeConv): input i
+ * feeds the output cell i*s - p + d_k at tap k.  al3d_sp_up_sites numbers the fed cells of the [B][OD][OH][OW] grid in
+ * raster (b, z, y, x) order the way al3d_sp_down_sites does (same arguments, same workspace layout; grid_out pre-filled
+ * with -1 gets the rows, *counter the count); al3d_sp_up_table(_tiles) then writes nbr[k][o] = the input row at
+ * (o + p - d_k) / s where that is a cell of the input grid [B][ID][IH][IW] (grid_in), else -1.  At most 27 taps. */
+int64_t al3d_sp_up_sites_workspace_bytes(int B, int OD, int OH, int OW);
+int al3d_sp_up_sites(const int* coords_in, int n_in, const int* ksize, const int* stride, const int* pad, int B, int OD,
+                     int OH, int OW, int* grid_out, int* coords_out, int* counter, int cap, void* workspace, void* stream);
+int al3d_sp_up_table(const int* coords_out, int n_out, const int* ksize, const int* stride, const int* pad, int B, int ID,
+                     int IH, int IW, const int* grid_in, int* nbr, void* stream);
+int al3d_sp_up_table_tiles(const int* coords_out, int n_out, const int* ksize, const int* stride, const int* pad, int B,
+                           int ID, int IH, int IW, const int* grid_in, int* nbr, int pitch, unsigned* tile_mask,
+                           void* stream);
+/* al3d_sp_conv_f32's arguments and result for ANY channel pair (weights [K][Cin][Cout]): one f32 FMA chain per output
+ * element over (k, ci) ascending.  For the pairs no templated kernel is built for (spconv_ops.h:260-361 serves any pair
+ * through its GEMM). */
+int al3d_sp_conv_any_f32(const float* fin, const int* nbr, int K, const float* wgt, int cin, int cout, const float* scale,
+                         const float* shift, const float* residual, int relu, float* fout, int n_out, void* stream);
+
 /* ---------------------------------------------------------------- runtime
  * A HIP stream restricted to n_cus compute units starting at first_cu (hipExtStreamCreateWithCUMask); the
  * reference has no analogue (its loader workers are host processes, det3d/datasets/loader/build_loader.py:23-59):
