@@ -3,25 +3,9 @@ torch statement of bevfusion/mmdet3d/models/vtransforms/base.py:127-163 + ops/be
 point order, then the reference's permute / unbind / cat).  The reference's own op needs its CUDA extension
 (bev_pool_ext) and mmcv, both absent: parity unpinned, like spconv and the rotated NMS."""
 import numpy as np
-import torch
 
-
-def _torch_bev_pool(x, geom, B, dx, bx, nx):
-    """The reference expressions, with index_add_ standing in for sort + segmented sum."""
-    Np = x.shape[0]
-    x, geom = torch.from_numpy(x), torch.from_numpy(geom)
-    dx, bx = torch.tensor(dx, dtype=torch.float32), torch.tensor(bx, dtype=torch.float32)
-    g = ((geom - (bx - dx / 2.0)) / dx).long()
-    batch_ix = torch.cat([torch.full([Np // B, 1], ix, dtype=torch.long) for ix in range(B)])
-    g = torch.cat((g, batch_ix), 1)
-    kept = (g[:, 0] >= 0) & (g[:, 0] < nx[0]) & (g[:, 1] >= 0) & (g[:, 1] < nx[1]) & (g[:, 2] >= 0) & (g[:, 2] < nx[2])
-    x, g = x[kept], g[kept]
-    H, W, Dz, C = nx[0], nx[1], nx[2], x.shape[1]
-    out = torch.zeros(B * Dz * H * W, C)
-    lin = ((g[:, 3] * Dz + g[:, 2]) * H + g[:, 0]) * W + g[:, 1]           # out[b, z, x, y, c] (bev_pool_cuda.cu:33-36)
-    out.index_add_(0, lin, x)
-    out = out.view(B, Dz, H, W, C).permute(0, 4, 1, 2, 3).contiguous()     # bev_pool.py:96
-    return torch.cat(out.unbind(dim=2), 1)                                  # base.py:161 -> [B, Dz*C, H, W]
+import bevpool_cases as cases
+from bevpool_cases import torch_bev_pool as _torch_bev_pool          # the torch statement, shared with the GPU regime tests
 
 
 def test_oracle_bev_pool_equals_torch_statement(oracle):
@@ -51,3 +35,43 @@ def test_oracle_bev_pool_fused_outer_product_equals_materialised(oracle):
     a = oracle.bev_pool(x.reshape(-1, C), geom, B, lo, dx, nx)
     b = oracle.bev_pool(ctx.reshape(-1, C), geom, B, lo, dx, nx, depth=depth.reshape(-1), D=D, fHW=fH * fW)
     assert np.array_equal(a.view(np.int32), b.view(np.int32)) and np.abs(a).sum() > 0
+
+
+def test_regime_case_builder_holds_every_list_regime_and_the_oracle_equals_torch(oracle):
+    """The input of tests/test_bevpool_regimes_gpu.py.  Precondition first: recounted with the reference's
+    ((geom - lo) / dx).long(), the named cells hold exactly 0 / 1 / 127 / 128 | 129 / 8192 | 8193 / 9000 members (the three
+    list regimes of csrc/bev_pool.hip and both boundaries), on consecutive cell ids, so the GPU test cannot silently lose a
+    regime; the fused-form input likewise.  Then the oracle equals the torch statement on it, bit for bit."""
+    geom = cases.regimes_geom()
+    n = cases.assert_counts(geom, cases.REGIME_COUNTS)
+    assert geom.shape[0] % cases.B == 0 and 70000 < geom.shape[0] < 82000
+    named = set(cases.REGIME_COUNTS[0])
+    rest = np.array([n[0, c] for c in range(n.shape[1]) if c not in named])
+    assert rest.min() == 0 and rest.max() == 24                                  # the background everywhere else
+    assert n[1].max() == 1000 and (n[1] > 256).sum() == 4 and n.sum() < geom.shape[0]     # and padding outside the grid
+    assert not np.array_equal(np.argsort(geom[:, 0], kind="stable"), np.arange(len(geom)))
+    lss = cases.lss_geom()
+    Bs, N, D, fH, fW = cases.LSS_SHAPE
+    assert lss.shape[0] == Bs * N * D * fH * fW
+    cases.assert_counts(lss, cases.LSS_COUNTS)
+    lo = cases.grid_lo()
+    rng = np.random.default_rng(2)
+    for C in (80, 6):
+        x = rng.normal(size=(geom.shape[0], C)).astype(np.float32)
+        ref = _torch_bev_pool(x, geom, cases.B, cases.DX, cases.BX, cases.NX).numpy()
+        got = oracle.bev_pool(x, geom, cases.B, lo, cases.DX, cases.NX)
+        assert np.array_equal(cases.as_reference_layout(got).view(np.int32), ref.view(np.int32))
+
+
+def test_boundary_case_oracle_equals_torch_statement(oracle):
+    """Hand-placed points at every edge of the cell rule (t = 0, (-1, 0), -1, nx - 2^-k, nx, NaN, inf, 1e30; first and last
+    cell; first and last index of a sample): the reference's expression keeps exactly the expected number, and the oracle
+    equals the torch statement."""
+    geom, kept = cases.boundary_geom()
+    n = cases.cell_counts(geom, cases.B)
+    assert n.sum() == kept and n[0, 0] >= 1 and n[1, 0] >= 1 and n[0, -1] >= 1 and n[1, -1] >= 1
+    assert np.array_equal(n[0], n[1])
+    x = np.random.default_rng(3).normal(size=(geom.shape[0], 5)).astype(np.float32)
+    ref = _torch_bev_pool(x, geom, cases.B, cases.DX, cases.BX, cases.NX).numpy()
+    got = oracle.bev_pool(x, geom, cases.B, cases.grid_lo(), cases.DX, cases.NX)
+    assert np.array_equal(cases.as_reference_layout(got).view(np.int32), ref.view(np.int32))

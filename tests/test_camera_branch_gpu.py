@@ -112,6 +112,142 @@ def test_depth_image_stores_the_clamped_depth_for_points_behind_the_camera():
     assert torch.equal(got, ref)
 
 
+def test_depth_image_collisions_last_point_wins_exactly():
+    """lss_depth_scatter_kernel's rule -- the highest point index that lands on a pixel sets its depth -- with real
+    collisions and an exact comparison.  Identity lidar2image; about 3,000 points with z = d in {0.5, 1, 2, 4},
+    x = (col + 0.5) d, y = (row + 0.5) d, so every product, division and sum of the projection is exact in float32 and the
+    float64 reference loop lands on the same pixels; 50 pixels receive 20 - 100 points each, and on each of them the last
+    point's depth occurs on no other point of that pixel, so any other winner is a different number.  Two cameras: the
+    second one's image augmentation is an integer translation, which moves some points out of the image and others in;
+    points beyond every border included.  torch.equal with the last-point-wins loop, and twice the same."""
+    from al3d.models.bevfusion_camera import DepthLSSTransform
+    image_size, feature_size = (64, 176), (8, 22)
+    iH, iW = image_size
+    vt = DepthLSSTransform(32, 16, image_size, feature_size, [-54.0, 54.0, 0.6], [-54.0, 54.0, 0.6], [-10.0, 10.0, 20.0],
+                           [1.0, 60.0, 1.0], downsample=2).to(DEV)
+    rng = np.random.default_rng(12)
+    depths = np.array([0.5, 1.0, 2.0, 4.0])
+    tx, ty = 9, -5                                                       # camera 1: col + 9, row - 5
+    rows_, cols_, ds_, ms = [], [], [], []
+    pix = rng.permutation(iH * iW)
+    hot, cold = pix[:50], pix[50:]
+    for k, px in enumerate(hot):
+        m = int(rng.integers(20, 101))
+        last = depths[k % 4]
+        d = rng.choice(depths[depths != last], m)
+        d[-1] = last                                                     # appended in order: the pixel's highest index
+        ms.append(m)
+        rows_ += [px // iW] * m
+        cols_ += [px % iW] * m
+        ds_ += d.tolist()
+    n_hot = len(ds_)
+    n_lone = 300                                                         # single hits on the other pixels, a few shared by chance
+    lone = rng.choice(cold, n_lone)
+    rows_ += (lone // iW).tolist()
+    cols_ += (lone % iW).tolist()
+    ds_ += rng.choice(depths, n_lone).tolist()
+    n_out = 200                                                          # beyond a corner: outside on camera 0, some inside on camera 1
+    rows_ += rng.choice(np.r_[-12:0, iH:iH + 12], n_out).tolist()
+    cols_ += rng.choice(np.r_[-12:0, iW:iW + 12], n_out).tolist()
+    ds_ += rng.choice(depths, n_out).tolist()
+    rows_ += rng.integers(0, iH, 100).tolist()                           # beyond the left / right border only
+    cols_ += rng.choice(np.r_[-12:0, iW:iW + 12], 100).tolist()
+    ds_ += rng.choice(depths, 100).tolist()
+    row, col, d = np.asarray(rows_, np.float64), np.asarray(cols_, np.float64), np.asarray(ds_, np.float64)
+    # shuffle the points, keeping the order inside every hot pixel: each group gets the positions it drew, ascending
+    n = len(d)
+    pos = rng.permutation(n)
+    start = 0
+    for m in ms:
+        pos[start:start + m] = np.sort(pos[start:start + m])
+        start += m
+    assert start == n_hot >= 1000
+    pts = np.zeros((n, 5), np.float32)
+    pts[pos, 0], pts[pos, 1], pts[pos, 2] = (col + 0.5) * d, (row + 0.5) * d, d
+    pts = torch.from_numpy(pts)
+    eye = torch.eye(4)
+    aug = torch.stack([eye, eye.clone()]).reshape(1, 2, 4, 4)
+    aug[0, 1, 0, 3], aug[0, 1, 1, 3] = tx, ty
+    l2i = torch.stack([eye, eye]).reshape(1, 2, 4, 4)
+    lidar_aug = eye.reshape(1, 4, 4)
+    ref = _depth_image_reference([pts], l2i, aug, lidar_aug, image_size)
+    # the input does what it claims: every hot pixel shows its last point's depth on camera 0, many points share pixels
+    for k, px in enumerate(hot):
+        assert ref[0, 0, px // iW, px % iW] == depths[k % 4]
+    assert 50 < int((ref[0, 0] > 0).sum()) <= 50 + n_lone and not torch.equal(ref[0, 0], ref[0, 1])
+    assert int((ref[0, 1, iH + ty:] > 0).sum()) + int((ref[0, 1, :, :tx] > 0).sum()) > 0          # moved in from outside
+    assert torch.equal(ref[0, 1, :iH + ty, tx:], ref[0, 0, -ty:, :iW - tx])        # camera 1 == camera 0 moved, inside both
+    run = lambda: vt.depth_image([pts.to(DEV)], l2i.to(DEV), aug.to(DEV), lidar_aug.to(DEV)).cpu().reshape(ref.shape)
+    got, got2 = run(), run()
+    assert torch.equal(got, ref), f"{int((got != ref).sum())} pixels differ"
+    assert torch.equal(got, got2)
+
+
+SOFTMAX_D = [1, 2, 59, 64, 65, 118, 128, 129, 192, 193, 255, 256]
+
+
+@pytest.mark.parametrize("pad", [0, 80])
+@pytest.mark.parametrize("D", SOFTMAX_D)
+def test_depth_softmax_kernel_matches_float64(D, pad):
+    """``al3d_lss_depth_softmax_f32`` called directly: one wave per pixel, four register slots per lane (D <= 64, 128, 192,
+    256), transposed store to [BN, D, fH, fW].  Every slot boundary (64 | 65, 128 | 129, 192 | 193, 256), the shipped D = 118,
+    row strides ldy = D and D + 80 (context channels behind the logits, here large values that must not be read), 70
+    pixels (the last workgroup holds two of four waves).  Logits randn * 4; one row shifted by +1e4 (no overflow), one
+    with -inf entries (exact zeros there), one all -inf (NaN, as torch.softmax).
+    Reference: torch.softmax in float64 on the CPU.  Gate: e = max |got - ref64| <= 3 * e32 + 2^-23 with
+    e32 = max |torch float32 CPU softmax - ref64| on the same input (3 x: this suite's "not worse than torch's own fp32";
+    2^-23: one float32 ulp at 1.0 for the final division); rows sum to 1 within D * 2^-24.
+    A kernel that mishandled register slot t (t = 1, 2, 3: its load, its share of max / sum, or its store at depth
+    lane + 64 t) fails the gate -- or leaves untouched output, which is pre-filled with NaN -- at D = 65 ... 128,
+    129 ... 192, 193 ... 256 respectively."""
+    import ctypes
+    from al3d import lib
+    BN, fH, fW = 2, 5, 7
+    ldy = D + pad
+    g = torch.Generator().manual_seed(1000 + D)
+    y = torch.randn(BN, fH, fW, ldy, generator=g) * 4.0
+    y[..., D:] = 1.0e6                                                  # not logits: reading them would swamp the row
+    y[0, 1, 2, :D] += 1.0e4
+    holes = torch.zeros(D, dtype=torch.bool)
+    if D >= 2:
+        holes[torch.randperm(D, generator=g)[:max(1, D // 3)]] = True
+        y[1, 0, 3, :D][holes] = -float("inf")
+    y[1, 4, 6, :D] = -float("inf")                                      # the very last pixel: all -inf
+    logits = y[..., :D]
+    ref = torch.softmax(logits.double(), -1).permute(0, 3, 1, 2).contiguous()             # [BN, D, fH, fW]
+    ref32 = torch.softmax(logits, -1).permute(0, 3, 1, 2).double()
+    yd = y.to(DEV)
+    out = torch.full((BN, D, fH, fW), float("nan"), device=DEV)
+    lib.call("al3d_lss_depth_softmax_f32", ctypes.c_void_p(yd.data_ptr()), BN, fH, fW, D, ldy, ctypes.c_void_p(out.data_ptr()),
+             torch.cuda.current_stream().cuda_stream)
+    got = out.cpu().double()
+    nan_ref = torch.isnan(ref)
+    assert nan_ref[1, :, 4, 6].all() and int(nan_ref.sum()) == D and torch.equal(torch.isnan(got), nan_ref)
+    if D >= 2:
+        assert (got[1, :, 0, 3][holes] == 0).all() and (ref[1, :, 0, 3][holes] == 0).all()
+    ok = ~nan_ref
+    e = float((got - ref)[ok].abs().max())
+    e32 = float((ref32 - ref)[ok].abs().max())
+    s = got.sum(1)
+    s_err = float((s - 1.0)[~torch.isnan(s)].abs().max())
+    print(f"depth softmax D={D} ldy={ldy}: e={e:.3e} e32={e32:.3e} gate={3 * e32 + 2.0 ** -23:.3e} "
+          f"|rowsum-1|={s_err:.3e} bound={D * 2.0 ** -24:.3e}")
+    assert e <= 3 * e32 + 2.0 ** -23
+    assert s_err <= D * 2.0 ** -24
+
+
+def test_depth_softmax_refuses_what_it_cannot_hold():
+    """More depth bins than the four register slots hold (D > 256), or a row stride shorter than D: Al3dError, no launch."""
+    import ctypes
+    from al3d import lib
+    y = torch.zeros(1, 2, 2, 300, device=DEV)
+    out = torch.zeros(1, 300, 2, 2, device=DEV)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    for D, ldy in ((257, 257), (300, 300), (64, 63), (2, 1)):
+        with pytest.raises(lib.Al3dError):
+            lib.call("al3d_lss_depth_softmax_f32", p(y), 1, 2, 2, D, ldy, p(out), torch.cuda.current_stream().cuda_stream)
+
+
 def test_depth_lss_transform_matches_torch_restatement():
     """Whole DepthLSSTransform.forward: depth image -> dtransform -> depthnet -> softmax x context -> BEV pooling
     -> downsample, against torch fp32 modules for the conv stacks and the materialised outer product pooled by
@@ -200,12 +336,14 @@ def test_cat2_kernel_equals_torch_cat(swapped):
 
 
 @pytest.mark.parametrize("align", [True, False])
-@pytest.mark.parametrize("shape", [((2, 32, 88, 192), (16, 44, 384)), ((1, 7, 5, 8), (3, 2, 12)), ((1, 4, 4, 4), (1, 1, 4))])
+@pytest.mark.parametrize("shape", [((2, 32, 88, 192), (16, 44, 384)), ((1, 7, 5, 8), (3, 2, 12)), ((1, 4, 4, 4), (1, 1, 4)),
+                                   ((2, 1, 6, 8), (3, 4, 12)), ((1, 5, 1, 4), (2, 3, 8)), ((1, 1, 1, 4), (2, 2, 4))])
 def test_upsample_cat_kernel_matches_torch(shape, align):
     """``al3d_lss_upsample_cat_f32`` (generalized_lss.py:88-101: bilinear upsample with align_corners=True of the coarser
     level + channel concatenation, one kernel on channels-last maps) against ``F.interpolate`` + ``torch.cat``: the
     copied half bit for bit, the interpolated half to fp32 rounding of a four-tap blend against torch's float32 result;
-    odd sizes and a 1 x 1 source (every weight on one tap) included."""
+    odd sizes and a 1 x 1 source (every weight on one tap) included, and outputs one row high / one column wide / a single
+    pixel (the align_corners scale (in - 1) / (out - 1) is then defined as 0: the `H > 1 ? ... : 0` branch)."""
     import ctypes
     from al3d import lib
     (N, H, W, C1), (h, w, C2) = shape
