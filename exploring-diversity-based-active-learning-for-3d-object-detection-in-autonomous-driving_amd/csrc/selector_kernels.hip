@@ -277,38 +277,88 @@ extern "C" int al3d_max_finite_f64(const double* a, int64_t count, double* out_d
 // argmax), so one persistent 1024-thread workgroup runs all of it: per pick one
 // coalesced pass over D[last] fused with the fps min-update and a first-index
 // argmax (wave shuffle -> LDS -> wave 0), two barriers, no host round trip.
+// NaN follows numpy/torch: the min update propagates it and the argmax returns
+// the first NaN if there is one.
 // fps lives in a global scratch row each thread owns privately.
 #define GREEDY_THREADS 1024
 
-template <typename T>
-struct GreedyBest { T v; int64_t i; };
+// The argmax runs on an integer key of the value: order-preserving bits, +0 and -0 on one key,
+// every NaN on the largest key (np.argmax / torch.argmax: a NaN is the maximum).  Larger key
+// wins, equal keys -> lower index (first hit).  The key of "no element yet" lies below the
+// key of -inf and carries the largest index, so it loses against every element.
+template <typename T> struct GreedyKey;
+template <> struct GreedyKey<double> {
+    typedef long long type;
+    static __device__ __forceinline__ type of(double v)
+    {
+        const type b = __double_as_longlong(v);
+        if (v != v) return 0x7fffffffffffffffLL;
+        return b < 0 ? (type)(0x8000000000000000ULL - (unsigned long long)b) : b;   // -0.0 -> 0
+    }
+    static __device__ __forceinline__ type none() { return (type)0x8000000000000000ULL; }
+};
+template <> struct GreedyKey<float> {
+    typedef int type;
+    static __device__ __forceinline__ type of(float v)
+    {
+        const type b = __float_as_int(v);
+        if (v != v) return 0x7fffffff;
+        return b < 0 ? (type)(0x80000000u - (unsigned)b) : b;                       // -0.0f -> 0
+    }
+    static __device__ __forceinline__ type none() { return (type)0x80000000u; }
+};
 
 template <typename T>
-__device__ __forceinline__ void greedy_take(GreedyBest<T>& b, T ov, int64_t oi)
+struct GreedyBest { typename GreedyKey<T>::type k; int64_t i; };
+
+template <typename T>
+__device__ __forceinline__ GreedyBest<T> greedy_none()
 {
-    // larger value wins; equal values -> lower index (np.argmax / torch.argmax first hit)
-    if (oi >= 0 && (b.i < 0 || ov > b.v || (ov == b.v && oi < b.i))) { b.v = ov; b.i = oi; }
+    GreedyBest<T> b;
+    b.k = GreedyKey<T>::none(); b.i = 0x7fffffffffffffffLL;
+    return b;
+}
+
+// stack([a, b]).min(0): NaN if either side is NaN, else the smaller one
+template <typename T>
+__device__ __forceinline__ T greedy_min(T a, T b)
+{
+    return (b < a || b != b) ? b : a;
+}
+
+// one thread scans ascending j, so a later element only wins with a strictly larger key
+template <typename T>
+__device__ __forceinline__ void greedy_scan(GreedyBest<T>& b, T v, int64_t j)
+{
+    const typename GreedyKey<T>::type k = GreedyKey<T>::of(v);
+    if (k > b.k) { b.k = k; b.i = j; }
 }
 
 template <typename T>
-__device__ __forceinline__ GreedyBest<T> greedy_block_argmax(GreedyBest<T> b, T* s_v, int64_t* s_i)
+__device__ __forceinline__ void greedy_take(GreedyBest<T>& b, typename GreedyKey<T>::type ok, int64_t oi)
+{
+    if (ok > b.k || (ok == b.k && oi < b.i)) { b.k = ok; b.i = oi; }
+}
+
+template <typename T>
+__device__ __forceinline__ GreedyBest<T> greedy_block_argmax(GreedyBest<T> b, typename GreedyKey<T>::type* s_k,
+                                                             int64_t* s_i)
 {
     for (int off = 32; off > 0; off >>= 1) {
-        T ov = __shfl_down(b.v, off);
-        int64_t oi = __shfl_down(b.i, off);
-        greedy_take(b, ov, oi);
+        const typename GreedyKey<T>::type ok = __shfl_down(b.k, off);
+        const int64_t oi = __shfl_down(b.i, off);
+        greedy_take(b, ok, oi);
     }
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) { s_v[wave] = b.v; s_i[wave] = b.i; }
+    if (lane == 0) { s_k[wave] = b.k; s_i[wave] = b.i; }
     __syncthreads();
     if (wave == 0) {
-        GreedyBest<T> w;
-        w.i = lane < GREEDY_THREADS / 64 ? s_i[lane] : -1;
-        w.v = lane < GREEDY_THREADS / 64 ? s_v[lane] : (T)0;
+        GreedyBest<T> w = greedy_none<T>();
+        if (lane < GREEDY_THREADS / 64) { w.k = s_k[lane]; w.i = s_i[lane]; }
         for (int off = 8; off > 0; off >>= 1) {
-            T ov = __shfl_down(w.v, off);
-            int64_t oi = __shfl_down(w.i, off);
-            greedy_take(w, ov, oi);
+            const typename GreedyKey<T>::type ok = __shfl_down(w.k, off);
+            const int64_t oi = __shfl_down(w.i, off);
+            greedy_take(w, ok, oi);
         }
         b = w;
     }
@@ -323,7 +373,7 @@ __global__ __launch_bounds__(GREEDY_THREADS) void greedy_kernel(
     int check_seeded, int64_t* __restrict__ out_idx, int64_t cap, int64_t* __restrict__ out_meta,
     T* __restrict__ fps, unsigned char* __restrict__ flags)
 {
-    __shared__ T s_v[GREEDY_THREADS / 64];
+    __shared__ typename GreedyKey<T>::type s_k[GREEDY_THREADS / 64];
     __shared__ int64_t s_i[GREEDY_THREADS / 64];
     __shared__ int64_t s_sel;
     __shared__ int s_stop;
@@ -335,20 +385,19 @@ __global__ __launch_bounds__(GREEDY_THREADS) void greedy_kernel(
     for (int64_t s = tid; s < n_seeded; s += GREEDY_THREADS) flags[seeded[s]] = 2;
     __syncthreads();
 
-    GreedyBest<T> best;
-    best.i = -1; best.v = (T)0;
+    GreedyBest<T> best = greedy_none<T>();
     if (n_seeded > 0) {
         // fps = column-wise min over the seeded rows, first pick = argmax
         for (int64_t j = tid; j < n; j += GREEDY_THREADS) {
             T m = seed_map[seeded[0] * n + j];
             for (int64_t s = 1; s < n_seeded; ++s) {
                 T v = seed_map[seeded[s] * n + j];
-                if (v < m) m = v;
+                m = greedy_min(m, v);
             }
             fps[j] = m;
-            if (best.i < 0 || m > best.v) { best.v = m; best.i = j; }
+            greedy_scan(best, m, j);
         }
-        best = greedy_block_argmax(best, s_v, s_i);
+        best = greedy_block_argmax(best, s_k, s_i);
         if (tid == 0) s_sel = best.i;
     } else {
         for (int64_t j = tid; j < n; j += GREEDY_THREADS) fps[j] = seed_map[first * n + j];
@@ -371,15 +420,13 @@ __global__ __launch_bounds__(GREEDY_THREADS) void greedy_kernel(
     for (;;) {
         const int64_t sel = s_sel;
         const T* __restrict__ row = D + sel * n;
-        best.i = -1; best.v = (T)0;
+        best = greedy_none<T>();
         for (int64_t j = tid; j < n; j += GREEDY_THREADS) {
-            T f = fps[j];
-            T r = row[j];
-            if (r < f) f = r;
+            const T f = greedy_min(fps[j], row[j]);
             fps[j] = f;
-            if (best.i < 0 || f > best.v) { best.v = f; best.i = j; }
+            greedy_scan(best, f, j);
         }
-        best = greedy_block_argmax(best, s_v, s_i);
+        best = greedy_block_argmax(best, s_k, s_i);
         if (tid == 0) {
             const int64_t b = best.i;
             const unsigned char fl = flags[b];

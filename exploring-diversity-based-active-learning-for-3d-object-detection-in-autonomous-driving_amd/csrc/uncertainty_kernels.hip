@@ -5,6 +5,7 @@
 // Reference: det3d/selectors/entropy_selector.py:50-86,121-147, badge_selector.py:50-90,
 // uwe_selector.py:51-111.
 #include "al3d_common.h"
+#include "al3d_sort_key.h"
 
 // H = -s log s - (1-s) log(1-s), mean over the kept boxes of the frame; empty frame -> NaN
 // (torch.mean of an empty tensor).
@@ -95,25 +96,13 @@ extern "C" int al3d_minmax_norm_f32(const float* x, int64_t n, float* out, void*
     return AL3D_OK;
 }
 
-// argsort descending (torch.argsort(-x)): NaN last, equal values by ascending index.
-// keys = (order-preserving bits of x) << 32 | ~index, bitonic sort by one workgroup.
-__device__ __forceinline__ unsigned long long sort_key(float v, unsigned idx)
-{
-    unsigned u;
-    if (v != v) u = 0u;                                    // NaN: smallest key -> last
-    else {
-        u = __float_as_uint(v);
-        u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);     // total order, larger float -> larger key
-        if (u == 0u) u = 1u;
-    }
-    return ((unsigned long long)u << 32) | (unsigned)(0xffffffffu - idx);
-}
-
+// argsort descending (torch.argsort(-x)): NaN last, equal values (+0.0 and -0.0 included) by
+// ascending index.  Keys from al3d_sort_key.h, bitonic sort by one workgroup.
 __global__ __launch_bounds__(1024) void argsort_desc_kernel(const float* __restrict__ x, int64_t n, int64_t np2,
                                                             unsigned long long* __restrict__ keys,
                                                             int64_t* __restrict__ out)
 {
-    for (int64_t i = threadIdx.x; i < np2; i += 1024) keys[i] = i < n ? sort_key(x[i], (unsigned)i) : 0ull;
+    for (int64_t i = threadIdx.x; i < np2; i += 1024) keys[i] = i < n ? al3d_sort_key(x[i], (unsigned)i) : 0ull;
     __syncthreads();
     for (int64_t size = 2; size <= np2; size <<= 1)
         for (int64_t stride = size >> 1; stride > 0; stride >>= 1) {
@@ -152,6 +141,7 @@ extern "C" int al3d_argsort_desc_f32(const float* x, int64_t n, int64_t* out_idx
 
 // PPAL (det3d/selectors/ppal_selector.py:99-109): class-weighted entropy SUM per frame,
 // weight looked up by the merged label id.  Empty frame -> 0 (sum of an empty tensor).
+// A label outside [0, ncls) is weighted 0; the reference's lookup raises there instead.
 __global__ __launch_bounds__(64) void frame_weighted_entropy_kernel(const float* __restrict__ scores,
                                                                     const int* __restrict__ labels,
                                                                     const int* __restrict__ counts, int nt,

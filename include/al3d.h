@@ -88,7 +88,13 @@ int al3d_max_finite_f64(const double* a, int64_t count, double* out_dev, void* s
  *                 the initial pick (python random.choice on the host)
  *   box_cost      [n] f64 = n_boxes[i] * cost_b
  *   out_idx       [cap] picks in order;  out_meta[0] = count, out_meta[1] = status
- *   workspace     >= al3d_greedy_workspace_bytes(n, elem_size) bytes */
+ *   workspace     >= al3d_greedy_workspace_bytes(n, elem_size) bytes
+ * NaN, inf and -0 as in numpy / torch: the running minimum (`stack([fps, row]).min(0)`) is NaN
+ * where either side is NaN, and the argmax returns the first NaN if there is one, else the
+ * first index of the maximum (+0 == -0).  A frame whose map row and column are NaN (Badge /
+ * UWE embedding of a frame without boxes) is therefore picked first, the next pick is frame
+ * 0, and the pick after that ends the loop with AL3D_GREEDY_DUPLICATE, as the reference's
+ * assert does. */
 int64_t al3d_greedy_workspace_bytes(int64_t n, int elem_size);
 int al3d_greedy_kcenter_f64(const double* D, const double* seed_map, int64_t n,
                             const int64_t* seeded, int64_t n_seeded, int64_t first,
@@ -110,7 +116,10 @@ int al3d_greedy_kcenter_f32(const float* D, const float* seed_map, int64_t n,
 int al3d_frame_entropy_f32(const float* scores, const int* counts, int B, int nt, int post,
                            float* out, void* stream);
 /* PPAL: sum over a frame's kept boxes of entropy * class_weight[label] (labels [B,nt,post] i32,
- * class_weight [ncls] f32); empty frame -> 0.  Replaces det3d/selectors/ppal_selector.py:99-109. */
+ * class_weight [ncls] f32); empty frame -> 0.  Replaces det3d/selectors/ppal_selector.py:99-109.
+ * A score of exactly 0 or 1 gives NaN (0 * log 0), as in torch; entries beyond counts are never
+ * read.  Differs from the reference on purpose: a label outside [0, ncls) is weighted 0 here,
+ * where the reference's table lookup raises. */
 int al3d_frame_weighted_entropy_f32(const float* scores, const int* labels, const int* counts, int B,
                                     int nt, int post, const float* class_weight, int ncls, float* out,
                                     void* stream);
@@ -121,7 +130,9 @@ int al3d_scale_rows_f32(const float* feats, const float* w, const int64_t* widx,
                         float* out, void* stream);
 /* (x - min) / (max - min), NaN-propagating like torch (uwe_selector.py:78) */
 int al3d_minmax_norm_f32(const float* x, int64_t n, float* out, void* stream);
-/* torch.argsort(-x): descending, NaN last, ties by ascending index (entropy_selector.py:121) */
+/* torch.argsort(-x, stable=True): descending, NaN (either sign) last, equal values by ascending
+ * index, +0.0 and -0.0 being equal (entropy_selector.py:121; the reference's own call is not
+ * stable, so its order among equal values is unspecified and this is the choice made here) */
 int64_t al3d_argsort_workspace_bytes(int64_t n);
 int al3d_argsort_desc_f32(const float* x, int64_t n, int64_t* out_idx, void* workspace, void* stream);
 

@@ -350,6 +350,8 @@ void al3d_oracle_l1_map_f32(const float* feats, int64_t n, int64_t c, int p, flo
  *   cost         start_cost (= get_cost_amount()); per pick  += cost_f ; += box_cost[i]
  *   stop         when cost > budget_int; the overflowing frame is not appended
  *   check_seeded also assert picks are not in the seeded list (spatial/temporal selectors)
+ * NaN as in numpy/torch: stack(..).min(0) gives NaN if either side is NaN, and
+ * argmax returns the first NaN if there is one, else the first maximum.
  * returns 0, -1 when the duplicate-pick assertion would fire, -2 when out_idx
  * is full; picks made so far are out_idx[0..*out_count). */
 #define GREEDY_IMPL(NAME, T)                                                                   \
@@ -368,10 +370,11 @@ int NAME(const T* D, const T* seed_map, int64_t n, const int64_t* seeded, int64_
         for (int64_t s = 1; s < n_seeded; ++s)                                                  \
             for (int64_t j = 0; j < n; ++j) {                                                   \
                 T v = seed_map[seeded[s] * n + j];                                              \
-                if (v < fps[j]) fps[j] = v;                                                     \
+                if (v < fps[j] || v != v) fps[j] = v;                                           \
             }                                                                                   \
         sel = 0;                                                                                \
-        for (int64_t j = 1; j < n; ++j) if (fps[j] > fps[sel]) sel = j;                         \
+        for (int64_t j = 1; j < n; ++j)                                                         \
+            if (fps[j] > fps[sel] || (fps[j] != fps[j] && fps[sel] == fps[sel])) sel = j;       \
     } else {                                                                                    \
         sel = first;                                                                            \
         for (int64_t j = 0; j < n; ++j) fps[j] = seed_map[sel * n + j];                         \
@@ -384,9 +387,11 @@ int NAME(const T* D, const T* seed_map, int64_t n, const int64_t* seeded, int64_
     int rc = 0;                                                                                 \
     for (;;) {                                                                                  \
         const T* row = D + sel * n;                                                             \
-        for (int64_t j = 0; j < n; ++j) if (row[j] < fps[j]) fps[j] = row[j];                   \
+        for (int64_t j = 0; j < n; ++j)                                                         \
+            if (row[j] < fps[j] || row[j] != row[j]) fps[j] = row[j];                           \
         int64_t best = 0;                                                                       \
-        for (int64_t j = 1; j < n; ++j) if (fps[j] > fps[best]) best = j;                       \
+        for (int64_t j = 1; j < n; ++j)                                                         \
+            if (fps[j] > fps[best] || (fps[j] != fps[j] && fps[best] == fps[best])) best = j;   \
         if (picked[best] || (check_seeded && in_seed[best])) { rc = -1; break; }                \
         cost += cost_f;                                                                         \
         cost += box_cost[best];                                                                 \

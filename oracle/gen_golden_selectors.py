@@ -5,7 +5,7 @@ Runs the *reference's own* selector classes (imported unmodified from
 /root/reference through ``ref_import``) on synthetic pools and records inputs
 and outputs.  Run in the build container only:
 
-    python oracle/gen_golden_selectors.py
+    python oracle/gen_golden_selectors.py [case name ...]
 
 Each fixture holds the flat inputs the selectors read (``car_from_global``,
 logfile ids, ``n_boxes``), the buffer, the constructor arguments, and the
@@ -34,6 +34,7 @@ from al3d import synthetic  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden")
 SEED = 3407  # tools/active_select.py:76-80
+ONLY = set(sys.argv[1:])  # case names to (re)generate; none given = all
 
 
 def _capture_locals(func, names):
@@ -61,11 +62,17 @@ def _capture_locals(func, names):
 
 def run_case(name, cls_name, module, infos, logs, buffer, budget, kwargs=None,
              feats_seed=None, feats_scale=0.01, capture=False, expect_assert=False,
-             entropy=None, modname=None):
+             entropy=None, modname=None, feats_nan_rows=None):
+    if ONLY and name not in ONLY:
+        return
     kwargs = dict(kwargs or {})
     feats = None
     if feats_seed is not None:
         feats = synthetic.make_embeddings(len(infos), seed=feats_seed, scale=feats_scale)
+        if feats_nan_rows is not None:
+            # frames without a surviving box: their entropy weight, and with it the whole
+            # weighted embedding, is NaN (badge_selector.py:76-78)
+            feats[list(feats_nan_rows)] = np.nan
     mods = ref_import.import_selectors()
     if module not in mods:
         import importlib
@@ -153,6 +160,8 @@ def run_case(name, cls_name, module, infos, logs, buffer, budget, kwargs=None,
         out["feats_seed"] = np.int64(feats_seed)
         out["feats_scale"] = np.float64(feats_scale)
         out["feats_sha256"] = np.array(hashlib.sha256(feats.tobytes()).hexdigest())
+        if feats_nan_rows is not None:
+            out["feats_nan_rows"] = np.array(list(feats_nan_rows), dtype=np.int64)
     if capture:
         for k, v in got.items():
             if isinstance(v, torch.Tensor):
@@ -170,6 +179,7 @@ def run_case(name, cls_name, module, infos, logs, buffer, budget, kwargs=None,
 def main():
     os.makedirs(OUT, exist_ok=True)
     logging.basicConfig(level=logging.ERROR)
+    ref_import.import_selectors()                   # puts the reference on sys.path
     small, small_logs = synthetic.make_pool(6, seed=1)          # N = 240
     empty = {"0": []}
     seeded = {"0": [], "50": [5, 17, 200]}
@@ -235,6 +245,12 @@ def main():
              kwargs=dict(p=2), feats_seed=5)
     run_case("uwe_seeded", "UWESelector", "uwe_selector", small, small_logs, seeded, 30,
              kwargs=dict(p=1), feats_seed=7)
+    # two frames whose weighted embedding is all NaN, one of them above pool index 64: the
+    # reference picks the first NaN frame, then frame 0, then trips its duplicate-pick assert
+    run_case("badge_nan_frame", "BadgeSelector", "badge_selector", small, small_logs, seeded, 30,
+             kwargs=dict(p=2), feats_seed=5, feats_nan_rows=[40, 133], expect_assert=True)
+    run_case("uwe_nan_frame", "UWESelector", "uwe_selector", small, small_logs, seeded, 30,
+             kwargs=dict(p=1), feats_seed=7, feats_nan_rows=[40, 133], expect_assert=True)
     ent_sum = rng.uniform(0.5, 30.0, size=len(small)).astype(np.float32)     # PPAL: weighted entropy sums
     run_case("ppal_seeded", "PPALSelector", "ppal_selector", small, small_logs, seeded, 15,
              kwargs=dict(p=2, delta=4), feats_seed=8, entropy=ent_sum)

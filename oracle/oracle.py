@@ -5,6 +5,7 @@ bench.py, never by the product package.  ``build()`` compiles the plain-C
 restatement with gcc (oracle/Makefile).
 """
 import ctypes
+import glob
 import os
 import subprocess
 
@@ -20,6 +21,7 @@ _P = ctypes.c_void_p
 
 def build(force=False):
     srcs = [os.path.join(HERE, f) for f in os.listdir(HERE) if f.endswith((".c", ".h"))]
+    srcs += glob.glob(os.path.join(HERE, "..", "*_amd", "csrc", "al3d_sort_key.h"))
     if force or not os.path.exists(LIB_PATH) or any(
             os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs):
         subprocess.run(["make", "-C", HERE, "-B", "libal3d_oracle.so"], check=True,
@@ -299,6 +301,15 @@ def argsort_desc(x):
     """torch.argsort(-x) restated: descending, NaN last, ties by ascending index (stable)."""
     x = np.asarray(x, dtype=np.float32)
     return np.argsort(-x, kind="stable")
+
+
+def sort_keys(x):
+    """The argsort kernel's 64-bit keys (csrc/al3d_sort_key.h) evaluated on the CPU; sorting them
+    in descending order gives the order the kernel returns."""
+    x = _c(x, np.float32)
+    keys = np.empty(x.shape[0], dtype=np.uint64)
+    lib().al3d_oracle_sort_keys_f32(_p(x), c_i64(x.shape[0]), _p(keys))
+    return keys
 
 
 def frame_entropy(scores):

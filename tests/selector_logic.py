@@ -26,6 +26,19 @@ def load_case(path):
     return fx
 
 
+def case_feats(fx):
+    """The embeddings of a golden case, regenerated from its seed; ``feats_nan_rows`` lists the
+    rows that are all NaN (frames whose entropy weight was NaN).  None if the case has none."""
+    from al3d import synthetic
+    if "feats_seed" not in fx:
+        return None
+    f = synthetic.make_embeddings(fx["n_boxes"].shape[0], seed=int(fx["feats_seed"]),
+                                  scale=float(fx["feats_scale"]))
+    if "feats_nan_rows" in fx:
+        f[fx["feats_nan_rows"]] = np.nan
+    return f
+
+
 def group_ids(logfiles):
     """TemporalSelector groups by logfile *name* (temporal_selector.py:49-54)."""
     seen = {}

@@ -8,16 +8,14 @@ import numpy as np
 import pytest
 
 import selector_logic as L
-from al3d import synthetic
 
 CASES = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "selector_*.npz")))
 
 
 def _feats(fx):
-    if "feats_seed" not in fx:
+    f = L.case_feats(fx)
+    if f is None:
         return None
-    f = synthetic.make_embeddings(fx["n_boxes"].shape[0], seed=int(fx["feats_seed"]),
-                                  scale=float(fx["feats_scale"]))
     assert hashlib.sha256(f.tobytes()).hexdigest() == str(fx["feats_sha256"]), \
         "synthetic.make_embeddings drifted from the generator the fixtures were made with"
     return f

@@ -28,10 +28,7 @@ def hip():
 
 
 def _feats(fx):
-    if "feats_seed" not in fx:
-        return None
-    return synthetic.make_embeddings(fx["n_boxes"].shape[0], seed=int(fx["feats_seed"]),
-                                     scale=float(fx["feats_scale"]))
+    return L.case_feats(fx)
 
 
 # ---------------------------------------------------------------- primitives vs oracle
