@@ -105,6 +105,8 @@ def apsp_knn(knn_d, knn_i, row0=0, nrows=None):
     n, kq = knn_d.shape
     nrows = n - row0 if nrows is None else nrows
     out = torch.empty((nrows, n), dtype=torch.float64, device=knn_d.device)
+    if nrows == 0 and 0 <= row0 <= n:
+        return out      # an empty block has no storage (data_ptr() is null): nothing to hand over
     ws = torch.empty(max(1, lib.load().al3d_apsp_workspace_bytes(n, kq)), dtype=torch.uint8,
                      device=knn_d.device)
     lib.call("al3d_apsp_knn_rows_f64", _ptr(knn_d), _ptr(knn_i), n, kq, int(row0), int(nrows), _ptr(out),

@@ -17,6 +17,10 @@ def knn(xy, kq):
     return d.cpu().numpy(), i.cpu().numpy()
 
 
+def apsp_rows(knn_d, knn_i, row0, nrows):
+    return ops.apsp_knn(_t(knn_d, np.float64), _t(knn_i, np.int64), row0, nrows).cpu().numpy()
+
+
 def spatial_map(xy, k=8):
     return ops.spatial_map(_t(xy, np.float64), k).cpu().numpy()
 
