@@ -1,29 +1,17 @@
-// Dense 2-D convolution with fp32-faithful arithmetic on the bf16 matrix cores (gfx950).
-//
-// Every fp32 operand is split exactly into three bf16 pieces x = x1 + x2 + x3 (8+8+8
-// significand bits); a product x*w is formed as the six partial products of total order <= 2
-// (x1w1, x1w2, x2w1, x1w3, x2w2, x3w1), each exact in fp32, accumulated in fp32 by
-// v_mfma_f32_32x32x16_bf16.  The three dropped terms are below 2^-25 |x w| -- smaller than the
-// rounding of the fp32 product itself -- so results agree with an fp32 FMA chain to fp32
-// rounding noise (tests compare both kernels against an fp64 reference).  Six bf16 MFMAs cost
-// 6/16 of the fp32-input MFMA they replace (MI355X: v_mfma_f32_32x32x2_f32 runs at 1/16 of the
-// bf16 rate), i.e. up to 2.67x the fp32 matrix-core roof.
+// Dense 2-D convolution in bf16x6 arithmetic: fp32-faithful on the bf16 matrix cores (gfx950).  The arithmetic -- the
+// exact three-way split, the six products and their order -- is al3d_bf16x6.h's.
 //
 // Same role, layouts and tiling as conv2d_mfma.hip (NHWC f32 activations in HBM; 128 px x 128
 // ch tile; 4 waves 2x2; double-buffered LDS); activations are split while they are staged
 // (registers -> LDS), weights are pre-split once into [3][Cout][taps][Cin] bf16.
 #include "al3d_common.h"
+#include "al3d_bf16x6.h"
 
 #define C6_BM 128
 #define C6_BN 128
 #define C6_BK 16
-#define C6_LDB 48          // bytes per LDS row: 16 bf16 (32 B) + 16 B pad (conflict-free b128 reads)
 #define C6_TH 8
 #define C6_TW 16
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 struct Conv6Params {
     const float* in;        // [B, H, W, Cin] f32
@@ -37,24 +25,12 @@ struct Conv6Params {
     int64_t plane;          // elements per weight plane = Cout * taps * Cin
 };
 
-__device__ __forceinline__ void split3(float x, __bf16& a, __bf16& b, __bf16& c)
-{
-    a = (__bf16)x;
-    const float r1 = x - (float)a;
-    b = (__bf16)r1;
-    const float r2 = r1 - (float)b;
-    c = (__bf16)r2;
-}
-
+// MODE 0: convolution, a tile = 8 x 16 output pixels.  MODE 1: 2x2 stride-2 deconvolution, a tile = 8 x 16 INPUT pixels
+// and blockIdx.z = the tap, i.e. which of the four output pixels of each input pixel.  The loop is b6_tile_pipeline.
 template <int MODE>
 __global__ __launch_bounds__(256, 2) void conv2d_bf16x6_kernel(Conv6Params p)
 {
-    // [buf][A|B][plane][row * 48 B]
-    // (Loading the pre-split weight fragments straight from L2 into registers instead of staging
-    // them was measured 17 % slower: fragment-shaped loads touch 32 lines for 1 KiB.)
-    __shared__ __attribute__((aligned(16))) unsigned char lds[2][2][3][C6_BM * C6_LDB];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave & 1, wn = wave >> 1;
     int tile = blockIdx.x;
     const int tx_ = tile % p.tiles_x; tile /= p.tiles_x;
@@ -65,99 +41,39 @@ __global__ __launch_bounds__(256, 2) void conv2d_bf16x6_kernel(Conv6Params p)
     const int taps = MODE == 0 ? p.ksize * p.ksize : 1;
     const int tap0 = MODE == 0 ? 0 : blockIdx.z;
     const int wtaps = MODE == 0 ? taps : 4;
-
-    // A staging: 128 rows x 16 ch f32 = 4 float4 per row -> 512 float4, 2 per thread
-    const int aq = tid & 3, ar = tid >> 2;            // piece, row (0..63), +64 on pass 1
-    int py[2], px[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int m = ar + 64 * i;
-        py[i] = ty_ * C6_TH + m / C6_TW;
-        px[i] = tx_ * C6_TW + m % C6_TW;
-    }
-    // B staging: per plane 128 rows x 16 bf16 = 2 x 16 B per row -> 256 pieces, 1 per thread
-    const int bq = tid & 1, br = tid >> 1;
     const int kchunks = p.Cin / C6_BK;
-    const int nsteps = taps * kchunks;
 
-    float4 ra[2];
-    uint4 rb[3];
-    auto load_step = [&](int step) {
-        const int tap = step / kchunks, c0 = (step - tap * kchunks) * C6_BK;
+    // step = tap * kchunks + chunk (the deconvolution has one tap per launch); A row m of the tile = pixel (m / 16, m % 16)
+    auto tap_of = [&](int step) { return MODE == 0 ? step / kchunks : 0; };
+    auto load_a = [&](int step, int row, int q, float4 (&ra)[2]) {
+        const int tap = tap_of(step), c0 = (step - tap * kchunks) * C6_BK;
         const int ky = MODE == 0 ? tap / p.ksize : 0, kx = MODE == 0 ? tap % p.ksize : 0;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
+            const int m = row + 64 * i;
+            const int py = ty_ * C6_TH + m / C6_TW, px = tx_ * C6_TW + m % C6_TW;
             int iy, ix;
-            if (MODE == 0) { iy = py[i] * p.stride - p.pad + ky; ix = px[i] * p.stride - p.pad + kx; }
-            else { iy = py[i]; ix = px[i]; }
-            const bool ok = py[i] < MH && px[i] < MW && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
+            if (MODE == 0) { iy = py * p.stride - p.pad + ky; ix = px * p.stride - p.pad + kx; }
+            else { iy = py; ix = px; }
+            const bool ok = py < MH && px < MW && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
             ra[i] = ok ? *reinterpret_cast<const float4*>(
-                             p.in + (((int64_t)b * p.H + iy) * p.W + ix) * p.Cin + c0 + 4 * aq)
+                             p.in + (((int64_t)b * p.H + iy) * p.W + ix) * p.Cin + c0 + 4 * q)
                        : make_float4(0.f, 0.f, 0.f, 0.f);
         }
-        const int n = n0 + br;
+    };
+    auto load_b = [&](int step, int row, int q, uint4 (&rb)[3]) {
+        const int tap = tap_of(step), c0 = (step - tap * kchunks) * C6_BK;
+        const int n = n0 + row;
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl)
             rb[pl] = n < p.Cout ? *reinterpret_cast<const uint4*>(
-                                      p.wgt + pl * p.plane + ((int64_t)n * wtaps + tap0 + tap) * p.Cin + c0 + 8 * bq)
+                                      p.wgt + pl * p.plane + ((int64_t)n * wtaps + tap0 + tap) * p.Cin + c0 + 8 * q)
                                 : make_uint4(0u, 0u, 0u, 0u);
     };
-    auto store_step = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const float v[4] = {ra[i].x, ra[i].y, ra[i].z, ra[i].w};
-            bf16x4 h, m, l;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { __bf16 a, bb, c; split3(v[e], a, bb, c); h[e] = a; m[e] = bb; l[e] = c; }
-            const int off = (ar + 64 * i) * C6_LDB + 8 * aq;
-            *reinterpret_cast<bf16x4*>(&lds[buf][0][0][off]) = h;
-            *reinterpret_cast<bf16x4*>(&lds[buf][0][1][off]) = m;
-            *reinterpret_cast<bf16x4*>(&lds[buf][0][2][off]) = l;
-        }
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-            *reinterpret_cast<uint4*>(&lds[buf][1][pl][br * C6_LDB + 16 * bq]) = rb[pl];
-    };
-
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    b6_tile_pipeline(taps * kchunks, load_a, load_b, acc);
 
-    load_step(0);
-    store_step(0);
-    __syncthreads();
     const int fr = lane & 31, fh = lane >> 5;
-    for (int step = 0; step < nsteps; ++step) {
-        const int buf = step & 1;
-        if (step + 1 < nsteps) load_step(step + 1);
-        bf16x8 a[3][2], bb[3][2];
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                a[pl][t] = *reinterpret_cast<const bf16x8*>(&lds[buf][0][pl][(wm * 64 + t * 32 + fr) * C6_LDB + 16 * fh]);
-                bb[pl][t] = *reinterpret_cast<const bf16x8*>(&lds[buf][1][pl][(wn * 64 + t * 32 + fr) * C6_LDB + 16 * fh]);
-            }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                // smallest partial products first
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2][i], bb[0][j], acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][i], bb[1][j], acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][i], bb[2][j], acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][i], bb[0][j], acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][i], bb[1][j], acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][i], bb[0][j], acc[i][j], 0, 0, 0);
-            }
-        if (step + 1 < nsteps) store_step(buf ^ 1);
-        __syncthreads();
-    }
-
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int n = n0 + wn * 64 + j * 32 + fr;
@@ -168,7 +84,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_bf16x6_kernel(Conv6Params p)
         for (int i = 0; i < 2; ++i) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+                const int m = wm * 64 + i * 32 + b6_crow(r, fh);
                 const int y = ty_ * C6_TH + m / C6_TW, x = tx_ * C6_TW + m % C6_TW;
                 if (y >= MH || x >= MW) continue;
                 float v = acc[i][j][r] * sc + sh;
@@ -210,7 +126,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_bf16x6_kernel(Conv6Params p)
 #define H3_BROW 32                     // bytes per weight row in LDS (16 bf16, swizzled halves)
 __global__ __launch_bounds__(256, 2) void conv3x3_bf16x6_halo_kernel(Conv6Params p)
 {
-    __shared__ __attribute__((aligned(16))) unsigned char Ah[3][H3_HP * C6_LDB];          // 29.4 KB
+    __shared__ __attribute__((aligned(16))) unsigned char Ah[3][H3_HP * B6_PITCH];          // 29.4 KB
     __shared__ __attribute__((aligned(16))) unsigned char Bs[3][3][C6_BN * H3_BROW];     // 36.9 KB
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
@@ -246,14 +162,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16x6_halo_kernel(Conv6Params
             const int piece = tid + 256 * i;
             const int hp = piece >> 2, q = piece & 3;
             if (hp >= H3_HP) continue;
-            const float v[4] = {rh[i].x, rh[i].y, rh[i].z, rh[i].w};
-            bf16x4 h, m, l;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { __bf16 a, bb, c; split3(v[e], a, bb, c); h[e] = a; m[e] = bb; l[e] = c; }
-            const int off = hp * C6_LDB + 8 * q;
-            *reinterpret_cast<bf16x4*>(&Ah[0][off]) = h;
-            *reinterpret_cast<bf16x4*>(&Ah[1][off]) = m;
-            *reinterpret_cast<bf16x4*>(&Ah[2][off]) = l;
+            b6_stage4(Ah, hp * B6_PITCH + 8 * q, rh[i]);
         }
     };
     const int nb = n0 + br;
@@ -288,9 +197,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16x6_halo_kernel(Conv6Params
     load_b(0, 1);
     store_b(1);
     __syncthreads();
-    const int a_off = ((2 * wm) * H3_HW + fr) * C6_LDB + 16 * fh;
+    const int a_off = ((2 * wm) * H3_HW + fr) * B6_PITCH + 16 * fh;
     const int b_off = (wn * 64 + fr) * H3_BROW + 16 * (fh ^ ((fr >> 3) & 1));   // +32 rows keeps bit 3
-    bf16x8 fa[2][3][2], fb[2][3][2];                  // [set][plane][tile]
+    // [set][tile]; read plane-major with A and B interleaved, not fragment by fragment: that issue order is one VGPR
+    // cheaper here (and the weight rows are 32-byte swizzled rows, not b6_frag's)
+    B6Frag fa[2][2], fb[2][2];
     for (int chunk = 0; chunk < nchunks; ++chunk) {
         const bool more = chunk + 1 < nchunks;
 #pragma unroll
@@ -306,8 +217,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16x6_halo_kernel(Conv6Params
                 for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
                     for (int t = 0; t < 2; ++t) {
-                        fa[0][pl][t] = *reinterpret_cast<const bf16x8*>(&Ah[pl][a_off + (t * H3_HW) * C6_LDB]);
-                        fb[0][pl][t] = *reinterpret_cast<const bf16x8*>(&Bs[0][pl][b_off + t * 32 * H3_BROW]);
+                        fa[0][t].p[pl] = *reinterpret_cast<const bf16x8*>(&Ah[pl][a_off + (t * H3_HW) * B6_PITCH]);
+                        fb[0][t].p[pl] = *reinterpret_cast<const bf16x8*>(&Bs[0][pl][b_off + t * 32 * H3_BROW]);
                     }
             }
             if (tap < 8) {                                          // fragments of the next tap
@@ -316,23 +227,20 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16x6_halo_kernel(Conv6Params
                 for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
                     for (int t = 0; t < 2; ++t) {
-                        fa[ns][pl][t] = *reinterpret_cast<const bf16x8*>(
-                            &Ah[pl][a_off + ((t + ky) * H3_HW + kx) * C6_LDB]);
-                        fb[ns][pl][t] = *reinterpret_cast<const bf16x8*>(
+                        fa[ns][t].p[pl] = *reinterpret_cast<const bf16x8*>(
+                            &Ah[pl][a_off + ((t + ky) * H3_HW + kx) * B6_PITCH]);
+                        fb[ns][t].p[pl] = *reinterpret_cast<const bf16x8*>(
                             &Bs[(tap + 1) % 3][pl][b_off + t * 32 * H3_BROW]);
                     }
             }
             if (tap == 8 && more) store_halo();                     // halo(chunk) was last read during tap 7
-            {
-                constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
+            // product-major over the four tiles: four independent accumulators between two MFMAs into the same one
 #pragma unroll
-                for (int t = 0; t < 6; ++t)
+            for (int t = 0; t < 6; ++t)
 #pragma unroll
-                    for (int i = 0; i < 2; ++i)
+                for (int i = 0; i < 2; ++i)
 #pragma unroll
-                        for (int j = 0; j < 2; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[cs][PA[t]][i], fb[cs][PB[t]][j], acc[i][j], 0, 0, 0);
-            }
+                    for (int j = 0; j < 2; ++j) b6_product(t, fa[cs][i], fb[cs][j], acc[i][j]);
             if (has2) store_b((tap + 2) % 3);
             __syncthreads();
         }
@@ -349,7 +257,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16x6_halo_kernel(Conv6Params
             const int y = ty_ * H3_TH + 2 * wm + i;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int x = tx_ * H3_TW + (r & 3) + 8 * (r >> 2) + 4 * fh;
+                const int x = tx_ * H3_TW + b6_crow(r, fh);
                 if (y >= p.OH || x >= p.OW) continue;
                 float v = acc[i][j][r] * sc + sh;
                 if (p.relu) v = v <= 0.f ? 0.f : v;                   // NaN propagates, like torch.relu
@@ -365,7 +273,7 @@ __global__ void split_weights_kernel(const float* __restrict__ w, int64_t count,
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
     __bf16 a, b, c;
-    split3(w[i], a, b, c);
+    b6_split(w[i], a, b, c);
     out[i] = a; out[count + i] = b; out[2 * count + i] = c;
 }
 

@@ -1,28 +1,13 @@
-// Sparse convolution, fp32-faithful on the bf16 matrix cores ("bf16x6", see
-// conv2d_bf16x6.hip for the arithmetic): same tiling, rulebook handling, empty-offset skipping
-// and fused epilogue as sp_conv_mfma_kernel (spconv_mfma.hip); the gathered fp32 rows are split
-// into three bf16 planes while they are staged into LDS, the weights are pre-split once into
-// [3][Cout][K][Cin] bf16, and every K-chunk of 16 channels costs six
-// v_mfma_f32_32x32x16_bf16 per output tile instead of eight v_mfma_f32_32x32x2_f32 at 1/16 of
-// the rate.
+// Sparse convolution in bf16x6 arithmetic (al3d_bf16x6.h: fp32-faithful on the bf16 matrix cores): same tiling,
+// rulebook handling, empty-offset skipping and fused epilogue as sp_conv_mfma_kernel (spconv_mfma.hip); the gathered
+// fp32 rows are split into three bf16 planes while they are staged into LDS, the weights are pre-split once into
+// [3][Cout][K][Cin] bf16.  The loop is not al3d_bf16x6.h's tile pipeline: the tile shape and wave layout depend on
+// COUT, A tiles are skipped per wave, and the step list is built in LDS; it uses the header's pieces.
 #include "al3d_common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+#include "al3d_bf16x6.h"
 
 #define S6_BM 128
 #define S6_BK 16
-#define S6_LDB 48
-
-__device__ __forceinline__ void s6_split3(float x, __bf16& a, __bf16& b, __bf16& c)
-{
-    a = (__bf16)x;
-    const float r1 = x - (float)a;
-    b = (__bf16)r1;
-    const float r2 = r1 - (float)b;
-    c = (__bf16)r2;
-}
 
 template <int CIN, int COUT>
 __global__ __launch_bounds__(256, 2) void sp_conv_bf16x6_kernel(const float* __restrict__ fin,
@@ -42,8 +27,8 @@ __global__ __launch_bounds__(256, 2) void sp_conv_bf16x6_kernel(const float* __r
     constexpr int KCHUNKS = CIN / S6_BK;
     constexpr int B_PIECES = NP * 2;                 // 16-byte pieces per weight plane and step
     constexpr int B_PASSES = (B_PIECES + 255) / 256;
-    __shared__ __attribute__((aligned(16))) unsigned char As[2][3][S6_BM * S6_LDB];
-    __shared__ __attribute__((aligned(16))) unsigned char Bs[2][3][NP * S6_LDB];
+    __shared__ __attribute__((aligned(16))) unsigned char As[2][3][S6_BM * B6_PITCH];
+    __shared__ __attribute__((aligned(16))) unsigned char Bs[2][3][NP * B6_PITCH];
     __shared__ unsigned s_mask;
     __shared__ int s_taps[32];
     __shared__ int s_ntaps;
@@ -136,16 +121,7 @@ __global__ __launch_bounds__(256, 2) void sp_conv_bf16x6_kernel(const float* __r
     };
     auto store_step = [&](int buf) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int off = (ar + 64 * i) * S6_LDB + 8 * aq;
-            const float v[4] = {ra[i].x, ra[i].y, ra[i].z, ra[i].w};
-            bf16x4 h, m, l;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { __bf16 a, b, c; s6_split3(v[e], a, b, c); h[e] = a; m[e] = b; l[e] = c; }
-            *reinterpret_cast<bf16x4*>(&As[buf][0][off]) = h;
-            *reinterpret_cast<bf16x4*>(&As[buf][1][off]) = m;
-            *reinterpret_cast<bf16x4*>(&As[buf][2][off]) = l;
-        }
+        for (int i = 0; i < 2; ++i) b6_stage4(As[buf], (ar + 64 * i) * B6_PITCH + 8 * aq, ra[i]);
 #pragma unroll
         for (int q = 0; q < B_PASSES; ++q) {
             const int piece = tid + 256 * q;
@@ -153,7 +129,7 @@ __global__ __launch_bounds__(256, 2) void sp_conv_bf16x6_kernel(const float* __r
                 const int n = piece >> 1, half = piece & 1;
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl)
-                    *reinterpret_cast<uint4*>(&Bs[buf][pl][n * S6_LDB + 16 * half]) = rb[pl][q];
+                    *reinterpret_cast<uint4*>(&Bs[buf][pl][n * B6_PITCH + 16 * half]) = rb[pl][q];
             }
         }
     };
@@ -167,28 +143,15 @@ __global__ __launch_bounds__(256, 2) void sp_conv_bf16x6_kernel(const float* __r
         const int buf = step & 1;
         const int tap_now = s_taps[step / KCHUNKS];
         if (step + 1 < nsteps) load_step(step + 1);
-        bf16x8 b[3][TN];
+        B6Frag b[TN];
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-                b[pl][j] = *reinterpret_cast<const bf16x8*>(&Bs[buf][pl][(wn * WN + j * 32 + fr) * S6_LDB + 16 * fh]);
+        for (int j = 0; j < TN; ++j) b[j] = b6_frag(Bs[buf], wn * WN + j * 32 + fr, fh);
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             if (!(wmask[i] >> tap_now & 1u)) continue;          // wave-uniform
-            bf16x8 a[3];
+            const B6Frag a = b6_frag(As[buf], wm * WM + i * 32 + fr, fh);
 #pragma unroll
-            for (int pl = 0; pl < 3; ++pl)
-                a[pl] = *reinterpret_cast<const bf16x8*>(&As[buf][pl][(wm * WM + i * 32 + fr) * S6_LDB + 16 * fh]);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0][j], acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1][j], acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2][j], acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0][j], acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1][j], acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0][j], acc[i][j], 0, 0, 0);
-            }
+            for (int j = 0; j < TN; ++j) b6_mac6(a, b[j], acc[i][j]);
         }
         if (step + 1 < nsteps) store_step(buf ^ 1);
         __syncthreads();
@@ -204,7 +167,7 @@ __global__ __launch_bounds__(256, 2) void sp_conv_bf16x6_kernel(const float* __r
         for (int i = 0; i < TM; ++i) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = row0 + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+                const int row = row0 + wm * WM + i * 32 + b6_crow(r, fh);
                 if (row >= n_out) continue;
                 float v = acc[i][j][r] * sc + sh;
                 const int64_t o = (int64_t)row * COUT + n;

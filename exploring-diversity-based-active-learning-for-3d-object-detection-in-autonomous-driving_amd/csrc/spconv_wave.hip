@@ -1,4 +1,4 @@
-// Sparse convolution, wave-autonomous gather + bf16x6 MFMA (gfx950).
+// Sparse convolution, wave-autonomous gather + bf16x6 MFMA (gfx950; the arithmetic is al3d_bf16x6.h's).
 //
 // sp_conv_bf16x6_kernel stages the gathered input rows through LDS like a dense GEMM tile; for
 // the sparse layers that costs an LDS write + barrier per (offset, 16-channel) step whose MFMA
@@ -11,13 +11,12 @@
 // are empty for their own 32 rows and otherwise run unsynchronised, so gather latency is hidden
 // by the other waves on the SIMD instead of by a software pipeline.
 #include "glds_common.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "al3d_bf16x6.h"
 
 #define SW_ROWS 128                 // rows per workgroup (4 waves x 32)
-#define SW_PITCH 48                 // bytes per LDS weight row: 16 bf16 + 16 B pad
+#define SW_PITCH B6_PITCH           // bytes per LDS weight row (both arithmetics)
 
-// Exact 3-way split of 8 floats into bf16 planes, written pair-wise so that each level is ONE
+// b6_split of 8 floats into a fragment (same bits), written pair-wise so that each level is ONE
 // v_cvt_pk_bf16_f32 per pair and the residuals are plain v_sub_f32 (this file is built with
 // -fno-slp-vectorize: hipcc otherwise fuses the subtractions into v_pk_add_f32, which is several
 // times dearer than two scalar subtractions next to MFMAs -- MI355X_MICROARCH.md, issue costs).
@@ -28,7 +27,7 @@ __device__ __forceinline__ unsigned sw_cvt_pk(float a, float b)
     const sw_f32x2 v = {a, b};
     return __builtin_bit_cast(unsigned, __builtin_convertvector(v, sw_bf16x2));
 }
-__device__ __forceinline__ void sw_split8(const float4& lo, const float4& hi, bf16x8& p0, bf16x8& p1, bf16x8& p2)
+__device__ __forceinline__ void sw_split8(const float4& lo, const float4& hi, B6Frag& f)
 {
     const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
     unsigned h[4], m[4], l[4];
@@ -45,9 +44,22 @@ __device__ __forceinline__ void sw_split8(const float4& lo, const float4& hi, bf
     }
     const uint4 hv = make_uint4(h[0], h[1], h[2], h[3]), mv = make_uint4(m[0], m[1], m[2], m[3]),
                 lv = make_uint4(l[0], l[1], l[2], l[3]);
-    p0 = __builtin_bit_cast(bf16x8, hv);
-    p1 = __builtin_bit_cast(bf16x8, mv);
-    p2 = __builtin_bit_cast(bf16x8, lv);
+    f.p[0] = __builtin_bit_cast(bf16x8, hv);
+    f.p[1] = __builtin_bit_cast(bf16x8, mv);
+    f.p[2] = __builtin_bit_cast(bf16x8, lv);
+}
+// acc += a B for output tile j of a weight unit at ub: lane (fr, fh) reads the three planes of weight row n = 32 j + fr
+// (the zero row where n >= NROWS), then the six products
+template <int NROWS>
+__device__ __forceinline__ void sw_mac_tile(const B6Frag& a, const unsigned char* ub, const unsigned char* zrow, int n, int fh,
+                                            f32x16& acc)
+{
+    const bool live = n < NROWS;
+    B6Frag b;
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl)
+        b.p[pl] = *reinterpret_cast<const bf16x8*>(live ? ub + (pl * NROWS + n) * SW_PITCH + 16 * fh : zrow);
+    b6_mac6(a, b, acc);
 }
 
 template <int CIN, int COUT>
@@ -151,29 +163,17 @@ __global__ __launch_bounds__(256) void sp_conv_wave_kernel(const float* __restri
                 cur_tap = tap;
                 src = my_row < n_out ? nbr[(int64_t)tap * n_out + my_row] : -1;
             }
-            bf16x8 a0, a1, a2;
+            B6Frag a;
             float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
             if (src >= 0) {
                 const float* rp = fin + (int64_t)src * CIN + 16 * g + 8 * fh;
                 lo = *reinterpret_cast<const float4*>(rp);
                 hi = *reinterpret_cast<const float4*>(rp + 4);
             }
-            sw_split8(lo, hi, a0, a1, a2);
+            sw_split8(lo, hi, a);
             const unsigned char* ub = &Ws[buf][(unit - u0) * UNIT_BYTES];
 #pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int n = j * 32 + fr;
-                const bool live = n < COUT;
-                const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(live ? ub + (0 * NROWS + n) * SW_PITCH + 16 * fh : zrow);
-                const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(live ? ub + (1 * NROWS + n) * SW_PITCH + 16 * fh : zrow);
-                const bf16x8 b2 = *reinterpret_cast<const bf16x8*>(live ? ub + (2 * NROWS + n) * SW_PITCH + 16 * fh : zrow);
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b0, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b2, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc[j], 0, 0, 0);
-            }
+            for (int j = 0; j < TN; ++j) sw_mac_tile<NROWS>(a, ub, zrow, j * 32 + fr, fh, acc[j]);
         }
         if (slab + 1 < nslabs) store_slab(buf ^ 1);
         __syncthreads();
@@ -187,7 +187,7 @@ __global__ __launch_bounds__(256) void sp_conv_wave_kernel(const float* __restri
         const float sh = shift ? shift[n] : 0.0f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = row0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+            const int row = row0 + wave * 32 + b6_crow(r, fh);
             if (row >= n_out) continue;
             float v = acc[j][r] * sc + sh;
             const int64_t o = (int64_t)row * COUT + n;
@@ -395,22 +395,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 8)))
                 if (cur_tap(cc) >= 0) {
                     const unsigned char* ub = &Ws[buf][i * UNIT_BYTES];
                     if constexpr (NPL == 3) {
-                        bf16x8 a0, a1, a2;
-                        sw_split8(dlo[slot], dhi[slot], a0, a1, a2);
+                        B6Frag a;
+                        sw_split8(dlo[slot], dhi[slot], a);
 #pragma unroll
-                        for (int j = 0; j < TN; ++j) {
-                            const int n = j * 32 + fr;
-                            const bool live = n < COUT;
-                            const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(live ? ub + (0 * NROWS + n) * SW_PITCH + 16 * fh : zrow);
-                            const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(live ? ub + (1 * NROWS + n) * SW_PITCH + 16 * fh : zrow);
-                            const bf16x8 b2 = *reinterpret_cast<const bf16x8*>(live ? ub + (2 * NROWS + n) * SW_PITCH + 16 * fh : zrow);
-                            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b0, acc[j], 0, 0, 0);
-                            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc[j], 0, 0, 0);
-                            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b2, acc[j], 0, 0, 0);
-                            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc[j], 0, 0, 0);
-                            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc[j], 0, 0, 0);
-                            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc[j], 0, 0, 0);
-                        }
+                        for (int j = 0; j < TN; ++j) sw_mac_tile<NROWS>(a, ub, zrow, j * 32 + fr, fh, acc[j]);
                     } else {
                         f16x8 ah, al;
                         if (io & SP_IO_IN_PAIR) {                              // pair rows: the fragment IS the operand pair
@@ -467,7 +455,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 8)))
         for (int j = 0; j < TN; ++j) {
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                scr[((r & 3) + 8 * (r >> 2) + 4 * fh) * EP_PITCH + fr] = acc[j][r];
+                scr[b6_crow(r, fh) * EP_PITCH + fr] = acc[j][r];
             __builtin_amdgcn_s_waitcnt(0xc07f);                       // lgkmcnt(0): the tile is in LDS (wave-private)
             __builtin_amdgcn_wave_barrier();
             sp_store_tile<COUT, EP_PITCH>(scr, lane, j, wrow0, n_out, scale, shift, residual, relu, fout, io);

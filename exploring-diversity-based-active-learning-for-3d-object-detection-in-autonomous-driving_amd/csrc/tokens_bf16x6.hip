@@ -1,14 +1,11 @@
 // Token-matrix kernels in fp32-faithful bf16x6 arithmetic (AL3D_MATH=bf16x6 / f32 on the token path): the token GEMM,
 // the 7 x 7 window attention (both row orders) and the head-dim-16 attention of tokens.hip with every matrix product
-// formed as in conv2d_bf16x6.hip -- each fp32 operand split exactly into three bf16 pieces x = x1 + x2 + x3, a product
-// as the six partial products of total order <= 2 (x1w1, x1w2, x2w1, x1w3, x2w2, x3w1), accumulated in fp32 by
-// v_mfma_f32_32x32x16_bf16, smallest first.  bf16 has fp32's exponent: no operand needs |x| < 65504, no piece needs a
-// power-of-two lift, and all six products go into ONE accumulator.  The bf16 product has the fragment shapes of the f16
-// one, so the two attention kernels are tok_attention.h's templates -- the code tokens.hip runs -- instantiated for this
-// file's arithmetic TkBf16x6 (split three ways, six products).  f32 rows in and out: pair rows are f16 planes and do not
+// formed by al3d_bf16x6.h's rule (three-way exact split, six products into ONE accumulator).  The bf16 product has the
+// fragment shapes of the f16 one, so the two attention kernels are tok_attention.h's templates -- the code tokens.hip
+// runs -- instantiated for this file's arithmetic TkBf16x6.  f32 rows in and out: pair rows are f16 planes and do not
 // exist here.
 //
-//   tok_linear_bf16x6_kernel               128 x 128 x 16 tile staged through LDS like conv2d_bf16x6_kernel; activations
+//   tok_linear_bf16x6_kernel               al3d_bf16x6.h's 128 x 128 x 16 tile pipeline on token rows; activations
 //                                          split while they are staged, weights pre-split [3][N][K]; epilogue: scale,
 //                                          bias, exact GELU / ReLU, residual, row scatter
 //   tok_window_attention_kernel<TkBf16x6>  q (scaled), k, v and the probabilities split three ways; softmax in fp32 VALU
@@ -16,48 +13,25 @@
 //
 // Written for correctness over the full fp32 range, not for speed.  gfx950 only.
 #include "al3d_common.h"
+#include "al3d_bf16x6.h"
 #include "tok_attention.h"
 
-typedef __bf16 tb_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 tb_bf16x4 __attribute__((ext_vector_type(4)));
-
-#define TB_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
-
-// x = a + b + c exactly (8 + 8 + 8 significand bits).  x is pinned to ONE rounded fp32 value first (tokens.hip's
-// tk_split: with the producer's arithmetic visible the high piece and the residual must see the same value).
+// The shared split of a value PINNED to one rounded fp32 value first (tokens.hip's tk_split: with the producer's
+// arithmetic visible the high piece and the residual must see the same value).
 __device__ __forceinline__ void tb_split(float x, __bf16& a, __bf16& b, __bf16& c)
 {
     asm volatile("" : "+v"(x));
-    a = (__bf16)x;
-    const float r1 = x - (float)a;
-    b = (__bf16)r1;
-    const float r2 = r1 - (float)b;
-    c = (__bf16)r2;
+    b6_split(x, a, b, c);
 }
-struct TbOp {
-    tb_bf16x8 p[3];         // hi, mid, lo
-};
-__device__ __forceinline__ void tb_split8(const float (&v)[8], TbOp& o)
+__device__ __forceinline__ void tb_split8(const float (&v)[8], B6Frag& o)
 {
 #pragma unroll
     for (int e = 0; e < 8; ++e) { __bf16 a, b, c; tb_split(v[e], a, b, c); o.p[0][e] = a; o.p[1][e] = b; o.p[2][e] = c; }
-}
-// acc += A B over one 16-channel step: the six products, smallest first
-__device__ __forceinline__ void tb_mac6(const TbOp& a, const TbOp& b, f32x16& acc)
-{
-    acc = TB_MFMA(a.p[2], b.p[0], acc);
-    acc = TB_MFMA(a.p[1], b.p[1], acc);
-    acc = TB_MFMA(a.p[0], b.p[2], acc);
-    acc = TB_MFMA(a.p[1], b.p[0], acc);
-    acc = TB_MFMA(a.p[0], b.p[1], acc);
-    acc = TB_MFMA(a.p[0], b.p[0], acc);
 }
 
 // ------------------------------------------------------------------ token GEMM, bf16x6
 #define TB_BM 128
 #define TB_BN 128
-#define TB_BK 16
-#define TB_LDB 48          // bytes per LDS row: 16 bf16 (32 B) + 16 B pad (conflict-free b128 reads)
 
 struct TokGemm6Params {
     const float* a;         // [M][K] f32 rows
@@ -71,93 +45,39 @@ struct TokGemm6Params {
     int64_t plane;          // elements per weight plane = N * K
 };
 
-// Tile 128 rows x 128 columns x 16 channels per step, four waves of 64 x 64, double-buffered LDS: staging, fragment
-// reads and product order of conv2d_bf16x6_kernel with a pixel = a row.  Each output element is read (residual) and
-// written by one lane, so `residual` may be `out`.
+// al3d_bf16x6.h's tile pipeline: A rows = token rows, B rows = output columns; staged values go through the pinned
+// split like every other token operand.  Each output element is read (residual) and written by one lane, so `residual`
+// may be `out`.
 __global__ __launch_bounds__(256, 2) void tok_linear_bf16x6_kernel(TokGemm6Params p)
 {
-    __shared__ __attribute__((aligned(16))) unsigned char lds[2][2][3][TB_BM * TB_LDB];    // [buf][A|B][plane][row * 48 B]
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave & 1, wn = wave >> 1;
     const int m0 = blockIdx.x * TB_BM, n0 = blockIdx.y * TB_BN;
 
-    // A staging: 128 rows x 16 ch f32 = 4 float4 per row -> 512 float4, 2 per thread
-    const int aq = tid & 3, ar = tid >> 2;            // piece, row (0..63), +64 on pass 1
-    // B staging: per plane 128 rows x 16 bf16 = 2 x 16 B per row -> 256 pieces, 1 per thread
-    const int bq = tid & 1, br = tid >> 1;
-    const int nsteps = p.K / TB_BK;
-
-    float4 ra[2];
-    uint4 rb[3];
-    auto load_step = [&](int step) {
-        const int c0 = step * TB_BK;
+    auto load_a = [&](int step, int row, int q, float4 (&ra)[2]) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const int m = m0 + ar + 64 * i;
-            ra[i] = m < p.M ? *reinterpret_cast<const float4*>(p.a + (int64_t)m * p.K + c0 + 4 * aq)
+            const int m = m0 + row + 64 * i;
+            ra[i] = m < p.M ? *reinterpret_cast<const float4*>(p.a + (int64_t)m * p.K + step * 16 + 4 * q)
                             : make_float4(0.f, 0.f, 0.f, 0.f);
         }
-        const int n = n0 + br;
+    };
+    auto load_b = [&](int step, int row, int q, uint4 (&rb)[3]) {
+        const int n = n0 + row;
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl)
-            rb[pl] = n < p.N ? *reinterpret_cast<const uint4*>(p.wgt + pl * p.plane + (int64_t)n * p.K + c0 + 8 * bq)
+            rb[pl] = n < p.N ? *reinterpret_cast<const uint4*>(p.wgt + pl * p.plane + (int64_t)n * p.K + step * 16 + 8 * q)
                              : make_uint4(0u, 0u, 0u, 0u);
     };
-    auto store_step = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const float v[4] = {ra[i].x, ra[i].y, ra[i].z, ra[i].w};
-            tb_bf16x4 h, m, l;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { __bf16 a, bb, c; tb_split(v[e], a, bb, c); h[e] = a; m[e] = bb; l[e] = c; }
-            const int off = (ar + 64 * i) * TB_LDB + 8 * aq;
-            *reinterpret_cast<tb_bf16x4*>(&lds[buf][0][0][off]) = h;
-            *reinterpret_cast<tb_bf16x4*>(&lds[buf][0][1][off]) = m;
-            *reinterpret_cast<tb_bf16x4*>(&lds[buf][0][2][off]) = l;
-        }
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-            *reinterpret_cast<uint4*>(&lds[buf][1][pl][br * TB_LDB + 16 * bq]) = rb[pl];
-    };
-
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    b6_tile_pipeline<tb_split>(p.K / 16, load_a, load_b, acc);
 
-    load_step(0);
-    store_step(0);
-    __syncthreads();
     const int fr = lane & 31, fh = lane >> 5;
-    for (int step = 0; step < nsteps; ++step) {
-        const int buf = step & 1;
-        if (step + 1 < nsteps) load_step(step + 1);
-        TbOp a[2], b[2];
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                a[t].p[pl] = *reinterpret_cast<const tb_bf16x8*>(&lds[buf][0][pl][(wm * 64 + t * 32 + fr) * TB_LDB + 16 * fh]);
-                b[t].p[pl] = *reinterpret_cast<const tb_bf16x8*>(&lds[buf][1][pl][(wn * 64 + t * 32 + fr) * TB_LDB + 16 * fh]);
-            }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) tb_mac6(a[i], b[j], acc[i][j]);
-        if (step + 1 < nsteps) store_step(buf ^ 1);
-        __syncthreads();
-    }
-
-    // C layout: column = fr, rows (r & 3) + 8 (r >> 2) + 4 fh down the registers
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+            const int m = m0 + wm * 64 + i * 32 + b6_crow(r, fh);
             if (m >= p.M) continue;
             const int orow = p.rowmap ? p.rowmap[m] : m;
             if (orow < 0) continue;
@@ -205,12 +125,12 @@ extern "C" int al3d_tok_linear_bf16x6(const float* a, const void* wgt_bf16x3, co
 // q (scaled), k, v and the probabilities split three ways; each product is six bf16 MFMAs into one accumulator.  f32 rows
 // out: pair rows are f16 planes and do not exist here.
 struct TkBf16x6 {
-    using Frag = TbOp;
+    using Frag = B6Frag;
     using Acc = f32x16;
     static constexpr int kWavesPerSimd = 2;
     static constexpr bool kPairRows = false;
     static __device__ __forceinline__ void split8(float (&v)[8], Frag& o) { tb_split8(v, o); }
-    static __device__ __forceinline__ void mac(const Frag& a, const Frag& b, Acc& acc) { tb_mac6(a, b, acc); }
+    static __device__ __forceinline__ void mac(const Frag& a, const Frag& b, Acc& acc) { b6_mac6(a, b, acc); }
     static __device__ __forceinline__ float value(const Acc& a, int r) { return a[r]; }
     static __device__ __forceinline__ void rescale(Acc& a, float f) { a *= f; }
 };

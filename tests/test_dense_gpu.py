@@ -121,6 +121,37 @@ def test_deconv_bf16x6_matches_f32_kernel():
     torch.testing.assert_close(a, b, rtol=2e-6, atol=2e-6)
 
 
+@pytest.mark.parametrize("path", ["halo3x3", "generic1x1", "deconv2x2"])
+def test_bf16x6_epilogue_scale_shift_relu_and_window(path):
+    """Every branch of the three bf16x6 dense epilogues: folded scale/shift, ReLU, a channel window of a wider buffer,
+    Cout not a multiple of 32, and an image smaller than one tile in y and ragged in x for both tile shapes (4 x 32
+    and 8 x 16).  Same call on the f32-structure weights as the reference (tolerance of the deconv test above); the
+    fp32-input kernels need Cin % 32 == 0, so they get the 16 input channels followed by 16 of exact zeros."""
+    from al3d import detector_ops as D
+    B, H, W, Cin, Cout, ldc, coff = 1, 5, 33, 16, 40, 64, 8
+    g = torch.Generator().manual_seed(11)
+    x = _nhwc(torch.randn(B, Cin, H, W, generator=g)).to(DEV)
+    scale = (torch.rand(Cout, generator=g) + 0.5).to(DEV)
+    shift = (torch.randn(Cout, generator=g) * 0.1).to(DEV)
+    if path == "deconv2x2":
+        wp = D.pack_deconv_weight(torch.randn(Cin, Cout, 2, 2, generator=g) / (Cin * 4) ** 0.5).to(DEV)
+        OH, OW = 2 * H, 2 * W
+        run = lambda x, w, out: D.deconv2x2_nhwc(x, w, scale, shift, True, out=out, coff=coff)
+    else:
+        k, pad = (3, 1) if path == "halo3x3" else (1, 0)
+        wp = D.pack_conv_weight(torch.randn(Cout, Cin, k, k, generator=g) / (Cin * k * k) ** 0.5).to(DEV)
+        OH, OW = H, W
+        run = lambda x, w, out: D.conv2d_nhwc(x, w, scale, shift, k, 1, pad, True, out=out, coff=coff)
+    ref = torch.full((B, OH, OW, ldc), -7.0, device=DEV)
+    got = torch.full((B, OH, OW, ldc), -7.0, device=DEV)
+    run(F.pad(x, (0, 16)), F.pad(wp, (0, 16)), ref)
+    run(x, D.split_bf16x3(wp), got)
+    win = got[..., coff:coff + Cout]
+    torch.testing.assert_close(win, ref[..., coff:coff + Cout], rtol=2e-6, atol=2e-6)
+    assert bool((win == 0).any()) and bool((win > 0).any())          # ReLU clipped some outputs, not all
+    assert torch.all(got[..., :coff] == -7.0) and torch.all(got[..., coff + Cout:] == -7.0)   # window respected
+
+
 # ---------------------------------------------------------------- f16x3 (fp32-class) kernels
 @pytest.mark.parametrize("B,H,W,Cin,Cout,k,s,p", [(1, 16, 16, 32, 128, 3, 1, 1), (2, 24, 40, 64, 128, 3, 1, 1),
                                                   (1, 32, 32, 128, 256, 3, 2, 1), (2, 13, 19, 32, 40, 1, 1, 0),
