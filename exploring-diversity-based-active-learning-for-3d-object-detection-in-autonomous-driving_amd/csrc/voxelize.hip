@@ -15,31 +15,9 @@
 // the float32 subtract/divide/floor must round like numpy.
 #include "al3d_common.h"
 #include "al3d_scan.h"
+#include "vox_cell.h"
 
 #define VX_EMPTY 0x7fffffff
-
-struct VoxCfg {
-    float min_x, min_y, min_z, vs_x, vs_y, vs_z;
-    int gx, gy, gz;         // grid size (x, y, z)
-    int max_points, max_voxels, nfeat;
-};
-
-__device__ __forceinline__ int64_t vox_cell(const float* __restrict__ p, const VoxCfg& c)
-{
-    const float fx = floorf((p[0] - c.min_x) / c.vs_x);
-    const float fy = floorf((p[1] - c.min_y) / c.vs_y);
-    const float fz = floorf((p[2] - c.min_z) / c.vs_z);
-    if (!(fx >= 0.f && fx < (float)c.gx && fy >= 0.f && fy < (float)c.gy && fz >= 0.f && fz < (float)c.gz))
-        return -1;
-    return ((int64_t)(int)fz * c.gy + (int)fy) * c.gx + (int)fx;
-}
-
-__device__ __forceinline__ int frame_of(const int64_t* __restrict__ off, int B, int64_t i)
-{
-    int lo = 0, hi = B;  // largest b with off[b] <= i
-    while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (off[mid] <= i) lo = mid; else hi = mid; }
-    return lo;
-}
 
 // pass 1: cell id per point; first[b][cell] = min point index (frame-local)
 __global__ void vox_first_kernel(const float* __restrict__ pts, const int64_t* __restrict__ off, int B,

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from .. import lib
-from ..detector_ops import Voxelizer
+from ..detector_ops import build_voxelizer
 
 
 def usable_cores():
@@ -103,9 +103,9 @@ class FileSweepLoader:
         self.nsweeps, self.root, self.min_distance = int(nsweeps), root, float(min_distance)
         self.indices = list(range(len(infos))) if indices is None else list(indices)
         self.depth = max(1, int(depth))
+        # hard voxelizer, or the dynamic one when the config's caps are -1 (refuses with_points before any thread starts)
+        self.voxelizer = build_voxelizer(voxel_cfg, self.batch_size, self.device, with_points=self.with_points)
         self.reader = SweepFileReader(threads)
-        self.voxelizer = Voxelizer(voxel_cfg["range"], voxel_cfg["voxel_size"], voxel_cfg["max_points_in_voxel"],
-                                   voxel_cfg["max_voxel_num"], max_batch=self.batch_size, device=self.device)
         self.anchors = [torch.as_tensor(a, dtype=torch.float32, device=self.device) for a in (anchors or [])]
         self.dataset = infos
         self.sampler = self.indices

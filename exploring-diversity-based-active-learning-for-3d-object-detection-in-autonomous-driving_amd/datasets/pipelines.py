@@ -103,10 +103,11 @@ class Voxelization:
         self._vox = None
 
     def _voxelizer(self, device):
-        from ..detector_ops import Voxelizer
+        from ..detector_ops import build_voxelizer
         if self._vox is None or self._vox.device != torch.device(device):
-            self._vox = Voxelizer(self.range, self.voxel_size, self.max_points_in_voxel, self.max_voxel_num,
-                                  max_batch=1, device=device)
+            cfg = dict(range=self.range, voxel_size=self.voxel_size, max_points_in_voxel=self.max_points_in_voxel,
+                       max_voxel_num=self.max_voxel_num)
+            self._vox = build_voxelizer(cfg, 1, device)           # dynamic when a cap is -1
         return self._vox
 
     def __call__(self, res, info):
@@ -120,7 +121,8 @@ class Voxelization:
         pts = pts.to(self.device).contiguous()
         vox = self._voxelizer(pts.device)
         off = torch.tensor([0, pts.shape[0]], dtype=torch.int64, device=pts.device)
-        v = vox(pts, off, want_voxels=True)
+        from ..detector_ops import DynamicVoxelizer
+        v = vox(pts, off, want_voxels=not isinstance(vox, DynamicVoxelizer))   # no padded slots without a cap
         res["lidar"]["voxels"] = dict(
             voxels=v["voxels"],
             coordinates=v["coords"][:, 1:],                 # (z, y, x) like the reference

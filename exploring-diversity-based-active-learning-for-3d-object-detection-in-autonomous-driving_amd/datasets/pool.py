@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from .. import synthetic
-from ..detector_ops import Voxelizer
+from ..detector_ops import build_voxelizer
 
 
 class PoolFrames:
@@ -82,9 +82,8 @@ class DeviceSweepLoader:
         self.batch_size = int(batch_size)
         self.device = torch.device(device)
         self.indices = list(range(len(pool))) if indices is None else list(indices)
-        self.voxelizer = Voxelizer(voxel_cfg["range"], voxel_cfg["voxel_size"],
-                                   voxel_cfg["max_points_in_voxel"], voxel_cfg["max_voxel_num"],
-                                   max_batch=self.batch_size, device=self.device)
+        # hard voxelizer, or the dynamic one when the config's caps are -1
+        self.voxelizer = build_voxelizer(voxel_cfg, self.batch_size, self.device, with_points=self.with_points)
         # anchors=None: embedding-only models (no detection head)
         self.anchors = [torch.as_tensor(a, dtype=torch.float32, device=self.device) for a in (anchors or [])]
         self.dataset = pool          # len(loader.dataset) like a torch DataLoader

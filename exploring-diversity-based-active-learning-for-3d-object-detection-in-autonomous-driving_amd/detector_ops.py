@@ -953,6 +953,140 @@ class Voxelizer:
                     voxels=None if voxels is None else voxels[:m])
 
 
+_DYN_REDUCE = {"sum": 0, "mean": 1, "max": 2}
+_DYN_ORDER = {"zyx": 0, "xyz": 1}
+
+
+def _dyn_status(status, who):
+    """Raise on the status word of the dynamic kernels (a host value: it came with the batch's one D2H)."""
+    st = int(status)
+    if st & 1:
+        raise lib.Al3dError(f"{who}: more voxels than rows_cap")
+    if st & 2:
+        raise lib.Al3dError(f"{who}: a coordinate lies beyond the stated extents")
+
+
+class DynamicVoxelizer:
+    """Batched dynamic voxelizer (csrc/voxelize_dyn.hip): every in-range point takes part, no cap per voxel or per frame,
+    no resident grid -- the scratch is one presence bit per cell per frame plus arrays per point, allocated per call.
+
+    Voxels of a frame come in ascending order of the coordinate triple named by ``order`` ("zyx": this project's encoder
+    rows (b, z, y, x); "xyz": the reference's unique_dim order, rows (b, x, y, z)); ``reduce`` is "mean", "sum" or "max"
+    over all points of the voxel (ops/voxel/scatter_points.py:73-75 uses mean or max)."""
+
+    def __init__(self, point_cloud_range, voxel_size, reduce="mean", order="zyx", device="cuda"):
+        import ctypes
+        import numpy as np
+        if reduce not in _DYN_REDUCE or order not in _DYN_ORDER:
+            raise ValueError(f"reduce must be one of {sorted(_DYN_REDUCE)}, order one of {sorted(_DYN_ORDER)}")
+        self.device = torch.device(device)
+        rng = np.asarray(point_cloud_range, dtype=np.float32)
+        vs = np.asarray(voxel_size, dtype=np.float32)
+        grid = np.round((rng[3:] - rng[:3]) / vs).astype(np.int64)
+        self.grid_size = grid                      # (x, y, z)
+        self.range_min = (ctypes.c_float * 3)(*rng[:3].tolist())
+        self.voxel_size = (ctypes.c_float * 3)(*vs.tolist())
+        self.grid_c = (ctypes.c_int * 3)(*[int(g) for g in grid])
+        self.reduce, self.order = reduce, order
+
+    def workspace_bytes(self, npts, B):
+        return lib.load().al3d_voxelize_dynamic_workspace_bytes(int(npts), int(B), *[int(g) for g in self.grid_size])
+
+    def __call__(self, points, point_offsets, want_voxels=False, want_point_coords=False, rows_cap=None):
+        """points [P,F] f32 (frames concatenated), point_offsets [B+1] i64 (device).  Returns the dictionary of
+        ``Voxelizer.__call__`` (``num_points``: unclipped counts; ``voxel_cap``: the largest per-frame voxel count) plus
+        ``point2voxel [P]`` i32 (row or -1) and, on request, ``point_coords [P,3]`` i32 (x, y, z) or -1."""
+        if want_voxels:
+            raise NotImplementedError("dynamic voxelization has no padded point slots (there is no dynamic pillar net)")
+        points = _dev(points, torch.float32, "points")
+        point_offsets = _dev(point_offsets, torch.int64, "point_offsets")
+        B = point_offsets.numel() - 1
+        npts, F = points.shape
+        dev = points.device
+        if npts == 0:                               # nothing to launch on (an empty tensor has no address)
+            out = dict(feat=points.new_empty((0, F)), coords=torch.empty((0, 4), dtype=torch.int32, device=dev),
+                       num_points=torch.empty((0,), dtype=torch.int32, device=dev),
+                       num_voxels=torch.zeros((B,), dtype=torch.int32, device=dev),
+                       row_base=torch.zeros((B + 1,), dtype=torch.int32, device=dev), voxel_cap=1, voxels=None,
+                       point2voxel=torch.empty((0,), dtype=torch.int32, device=dev))
+            if want_point_coords:
+                out["point_coords"] = torch.empty((0, 3), dtype=torch.int32, device=dev)
+            return out
+        rows = npts if rows_cap is None else int(rows_cap)
+        ws = torch.empty(max(self.workspace_bytes(npts, B), 1), dtype=torch.uint8, device=dev)
+        feat = torch.empty((rows, F), dtype=torch.float32, device=dev)
+        coords = torch.empty((rows, 4), dtype=torch.int32, device=dev)
+        counts = torch.empty((rows,), dtype=torch.int32, device=dev)
+        pcoords = torch.empty((npts, 3), dtype=torch.int32, device=dev) if want_point_coords else None
+        p2v = torch.empty((npts,), dtype=torch.int32, device=dev)
+        num_voxels = torch.empty((B,), dtype=torch.int32, device=dev)
+        # row_base [B+1] and the status word share one tensor: one D2H per batch
+        tail = torch.empty((B + 2,), dtype=torch.int32, device=dev)
+        lib.call("al3d_voxelize_dynamic_f32", _ptr(points), _ptr(point_offsets), npts, B, F, self.range_min,
+                 self.voxel_size, self.grid_c, _DYN_ORDER[self.order], _DYN_REDUCE[self.reduce], rows, _ptr(ws),
+                 _ptr(feat), _ptr(coords), _ptr(counts), _ptr(pcoords), _ptr(p2v), _ptr(num_voxels), _ptr(tail),
+                 tail.data_ptr() + 4 * (B + 1), _stream())
+        host = tail.cpu()
+        _dyn_status(host[B + 1], "al3d_voxelize_dynamic_f32")
+        m = int(host[B])
+        cap = int((host[1:B + 1] - host[:B]).max()) if B > 0 else 0
+        out = dict(feat=feat[:m], coords=coords[:m], num_points=counts[:m], num_voxels=num_voxels,
+                   row_base=tail[:B + 1], voxel_cap=max(cap, 1), voxels=None, point2voxel=p2v)
+        if want_point_coords:
+            out["point_coords"] = pcoords
+        return out
+
+
+def dynamic_scatter_rows(feats, coors, reduce="max"):
+    """``dynamic_scatter`` on given coordinates (ops/voxel/scatter_points.py:8-50): feats [N,C] f32, coors [N,3] int; rows
+    with a negative coordinate are dropped.  Returns (voxel_feats [M,C], voxel_coors [M,3] i32 sorted ascending,
+    point2voxel [N] i32, counts [M] i32)."""
+    import ctypes
+    feats = _dev(feats, torch.float32, "feats")
+    coors = _dev(coors.to(torch.int32), torch.int32, "coors")
+    if coors.dim() != 2 or coors.shape[1] != 3 or coors.shape[0] != feats.shape[0]:
+        raise ValueError("coors must be [N, 3] with one row per feature row")
+    if reduce not in _DYN_REDUCE:
+        raise ValueError(f"reduce_type must be one of {sorted(_DYN_REDUCE)}")
+    n, C = feats.shape
+    dev = feats.device
+    if n == 0:                                      # scatter_points_cuda.cu:192-196
+        empty = torch.empty((0,), dtype=torch.int32, device=dev)
+        return feats.new_empty((0, C)), torch.empty((0, 3), dtype=torch.int32, device=dev), empty, empty
+    ext = [max(int(v) + 1, 1) for v in coors.max(dim=0).values.tolist()]
+    dims = (ctypes.c_int * 3)(*ext)
+    ws = torch.empty(max(lib.load().al3d_voxelize_dynamic_workspace_bytes(n, 1, *ext), 1), dtype=torch.uint8, device=dev)
+    out = torch.empty((n, C), dtype=torch.float32, device=dev)
+    ocoors = torch.empty((n, 3), dtype=torch.int32, device=dev)
+    counts = torch.empty((n,), dtype=torch.int32, device=dev)
+    p2v = torch.empty((n,), dtype=torch.int32, device=dev)
+    tail = torch.empty((2,), dtype=torch.int32, device=dev)        # num_voxels, status
+    lib.call("al3d_dynamic_scatter_f32", _ptr(feats), _ptr(coors), n, C, dims, _DYN_REDUCE[reduce], n, _ptr(ws),
+             _ptr(out), _ptr(ocoors), _ptr(counts), _ptr(p2v), _ptr(tail), tail.data_ptr() + 4, _stream())
+    host = tail.cpu()
+    _dyn_status(host[1], "al3d_dynamic_scatter_f32")
+    m = int(host[0])
+    return out[:m], ocoors[:m], p2v, counts[:m]
+
+
+def voxelizer_class(voxel_cfg):
+    """The voxelizer class a ``voxel_generator`` dict selects (pure: builds nothing): the dynamic one iff
+    ``max_points_in_voxel == -1`` or ``max_voxel_num == -1`` (ops/voxel/voxelize.py:47)."""
+    dynamic = int(voxel_cfg["max_points_in_voxel"]) == -1 or int(voxel_cfg["max_voxel_num"]) == -1
+    return DynamicVoxelizer if dynamic else Voxelizer
+
+
+def build_voxelizer(voxel_cfg, max_batch, device, with_points=False):
+    """The voxelizer of a ``voxel_generator`` dict, for the loaders and the pipeline stage."""
+    if voxelizer_class(voxel_cfg) is DynamicVoxelizer:
+        if with_points:
+            raise NotImplementedError("with_points=True (PointPillars) needs the padded point slots of the hard voxelizer; "
+                                      "there is no dynamic pillar net -- set max_points_in_voxel and max_voxel_num")
+        return DynamicVoxelizer(voxel_cfg["range"], voxel_cfg["voxel_size"], reduce="mean", order="zyx", device=device)
+    return Voxelizer(voxel_cfg["range"], voxel_cfg["voxel_size"], voxel_cfg["max_points_in_voxel"],
+                     voxel_cfg["max_voxel_num"], max_batch=max_batch, device=device)
+
+
 # ------------------------------------------------------------------ PointPillars pillar net
 class PillarNet:
     """Folded PFN layers of a ``PillarFeatureNet`` for ``al3d_pillar_net_*`` (csrc/pillars.hip).  ``layers``: one or

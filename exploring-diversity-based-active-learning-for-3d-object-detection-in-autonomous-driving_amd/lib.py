@@ -55,6 +55,11 @@ SIGNATURES = {
     "al3d_voxelize_workspace_bytes": (c_i64, [c_i64, c_int, c_int]),
     "al3d_voxelize_mean_f32": (c_int, [c_p, c_p, c_i64, c_int, c_int, c_p, c_p, c_p, c_int, c_int,
                                        c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "al3d_voxelize_dynamic_workspace_bytes": (c_i64, [c_i64, c_int, c_int, c_int, c_int]),
+    "al3d_voxelize_dynamic_f32": (c_int, [c_p, c_p, c_i64, c_int, c_int, c_p, c_p, c_p, c_int, c_int, c_i64, c_p,
+                                          c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "al3d_dynamic_scatter_f32": (c_int, [c_p, c_p, c_i64, c_int, c_p, c_int, c_i64, c_p, c_p, c_p, c_p, c_p, c_p,
+                                         c_p, c_p]),
     "al3d_sp_fill_i32": (c_int, [c_p, c_i64, c_int, c_p]),
     "al3d_sp_scatter_index": (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_int, c_p]),
     "al3d_sp_subm_table": (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_int, c_int, c_int,

@@ -14,6 +14,7 @@ from .swin import SwinTransformer
 from .bevfusion_model import BEVFusion, BEVFusionCameraLidar
 from .bevfusion_camera_only import BEVFusionCameraOnly, GeneralizedResNet, LSSFPN, LSSTransform
 from .bev_seg_head import BEVGridTransform, BEVSegmentationHead
+from .voxel_layers import DynamicScatter, Voxelization, dynamic_scatter
 
 __all__ = ["READERS", "BACKBONES", "NECKS", "HEADS", "DETECTORS", "build_detector",
            "build_reader", "build_backbone", "build_neck", "build_head", "build_box_coder"]

@@ -202,6 +202,42 @@ int al3d_voxelize_mean_f32(const float* points, const int64_t* point_offsets, in
                            void* workspace, float* feat, int* coords, int* num_points, float* voxels,
                            int* num_voxels, int* row_base, void* stream);
 
+/* Dynamic voxelisation: no cap per voxel or per frame, no resident grid (csrc/voxelize_dyn.hip).
+ * Replaces Voxelization(max_num_points=-1) -> dynamic_voxelize (bevfusion/mmdet3d/ops/voxel/voxelize.py:47-50,
+ * src/voxelization_cuda.cu:19-60) followed by DynamicScatter / dynamic_scatter (ops/voxel/scatter_points.py:85-94,
+ * src/scatter_points_cuda.cu:183-239), which BEVFusion selects when voxelize.max_num_points <= 0
+ * (models/fusion_models/bevfusion.py:46-49), for every frame of the batch.
+ *   points / point_offsets / range_min / voxel_size / grid_size   as al3d_voxelize_mean_f32; points past
+ *                 point_offsets[B] belong to no frame.  A point with a NaN coordinate is dropped (the reference's
+ *                 int c = floor(NaN) is undefined).
+ *   order         0: voxels sorted by (z, y, x) per frame, coords rows (b, z, y, x);
+ *                 1: sorted by (x, y, z) like the reference's unique_dim, coords rows (b, x, y, z)
+ *   reduce        0 sum, 1 mean, 2 max over ALL points of the voxel; the float32 sum starts at 0.f and adds in ascending
+ *                 point index, mean = sum / (float)count
+ *   rows_cap      rows of feat / coords / counts; more voxels than that set bit 0 of *status and nothing is written
+ *                 past the cap (rows_cap = npts always suffices)
+ *   workspace     al3d_voxelize_dynamic_workspace_bytes(): one presence bit per cell per frame + arrays per point
+ *   feat [rows_cap, nfeat] f32; coords [rows_cap, 4] i32 (16-byte aligned); counts [rows_cap] i32 unclipped
+ *   point_coords  [npts, 3] i32 (x, y, z) or (-1, -1, -1), or NULL; point2voxel [npts] i32 row or -1, or NULL
+ *   num_voxels [B] i32; row_base [B+1] i32 (row_base[B] = total voxels); status: one device word.
+ * Every output is a pure function of the inputs (integer atomics only). */
+int64_t al3d_voxelize_dynamic_workspace_bytes(int64_t npts, int B, int gx, int gy, int gz);
+int al3d_voxelize_dynamic_f32(const float* points, const int64_t* point_offsets, int64_t npts, int B, int nfeat,
+                              const float* range_min, const float* voxel_size, const int* grid_size, int order,
+                              int reduce, int64_t rows_cap, void* workspace, float* feat, int* coords, int* counts,
+                              int* point_coords, int* point2voxel, int* num_voxels, int* row_base, int* status,
+                              void* stream);
+
+/* dynamic_scatter on given coordinates (ops/voxel/scatter_points.py:8-50, src/scatter_points_cuda.cu:183-239): the same
+ * ranking and reduction passes behind a second front end.  coors [n, 3] i32; a row with a negative coordinate is dropped
+ * (scatter_points_cuda.cu:202); dims = HOST array of 3 exclusive upper bounds, a coordinate at or above its bound sets
+ * bit 1 of *status.  Output rows are the distinct kept triples in ascending lexicographic order: out_feats
+ * [rows_cap, nfeat], out_coors [rows_cap, 3], counts [rows_cap], point2voxel [n] or NULL, num_voxels [1].
+ * workspace: al3d_voxelize_dynamic_workspace_bytes(n, 1, dims[0], dims[1], dims[2]). */
+int al3d_dynamic_scatter_f32(const float* feats, const int* coors, int64_t n, int nfeat, const int* dims, int reduce,
+                             int64_t rows_cap, void* workspace, float* out_feats, int* out_coors, int* counts,
+                             int* point2voxel, int* num_voxels, int* status, void* stream);
+
 /* Mean VFE on reference-format input: voxels [m,max_points,nfeat] zero-padded, counts [m] i32
  * -> feat [m,nfeat].  Replaces VoxelFeatureExtractorV3.forward
  * (det3d/models/readers/voxel_encoder.py:206-211). */
