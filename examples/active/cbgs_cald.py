@@ -8,3 +8,7 @@ selector = dict(
     buffer_file="data/buffers/cald.json",
     infos_origin="data/nuScenes/infos_train_10sweeps_withvelo.pkl",
 )
+# The two rankings CaldSelector replays (buffer_path, jsdiv_path) come from tools/active_prepass.py --mode cald, or from the
+# selector itself when it is given a detector and a dataloader (tools/active_select.py --pred):
+#   selector.update(prepass=True, prepass_view=(True, False, 0.0, 1.0),        # flip_x, flip_y, rot, scale
+#                   buffer_path="data/buffers/cald_ent_sorted_idx.json", jsdiv_path="data/buffers/idx_to_jsdiv.pkl")

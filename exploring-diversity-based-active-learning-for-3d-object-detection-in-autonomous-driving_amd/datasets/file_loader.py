@@ -95,8 +95,11 @@ class FileSweepLoader:
     therefore not reproducible)."""
 
     def __init__(self, infos, voxel_cfg, anchors, batch_size=8, device="cuda", nsweeps=10, root=None, threads=8,
-                 indices=None, depth=2, min_distance=1.0, with_points=False):
+                 indices=None, depth=2, min_distance=1.0, with_points=False, view=None):
         self.with_points = bool(with_points)   # also yield the padded point slots (``voxels``) for PillarFeatureNet
+        # (flip_x, flip_y, rot, scale): the merged points of every batch are augmented in place before they are voxelized
+        # (selector_ops.points_view_, CALD's second sweep); None launches nothing
+        self.view = view
         self.infos = infos
         self.batch_size = int(batch_size)
         self.device = torch.device(device)
@@ -211,6 +214,9 @@ class FileSweepLoader:
         lib.call("al3d_merge_sweeps_batch_range_f32", base, base + st.o_off, st.nf, st.total, base + st.o_xf, base + st.o_has,
                  base + st.o_tl, base + st.o_key, base + st.o_ff, st.B, self.min_distance, int(self.rule), rg, out.data_ptr(),
                  frame_off.data_ptr(), ws.data_ptr(), stream.cuda_stream)
+        if self.view is not None:
+            from ..selector_ops import points_view_
+            points_view_(out[:st.total], self.view)
         v = self.voxelizer(out, frame_off, want_voxels=self.with_points)
         gs = self.voxelizer.grid_size
         ex = {

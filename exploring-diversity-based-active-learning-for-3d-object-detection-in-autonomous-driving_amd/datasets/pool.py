@@ -76,8 +76,11 @@ class DeviceSweepLoader:
     keys the detector reads (voxelnet.py:84-97, mg_head.py:710-724): ``voxel_features``,
     ``coordinates``, ``num_points``, ``num_voxels``, ``shape``, ``anchors``, ``metadata``."""
 
-    def __init__(self, pool, voxel_cfg, anchors, batch_size=4, indices=None, device="cuda", with_points=False):
+    def __init__(self, pool, voxel_cfg, anchors, batch_size=4, indices=None, device="cuda", with_points=False, view=None):
         self.with_points = bool(with_points)   # also yield the padded point slots (``voxels``) for PillarFeatureNet
+        # (flip_x, flip_y, rot, scale): every batch is voxelized from an augmented COPY of its points
+        # (selector_ops.points_view_, CALD's second sweep); None launches nothing
+        self.view = view
         self.pool = pool
         self.batch_size = int(batch_size)
         self.device = torch.device(device)
@@ -104,6 +107,9 @@ class DeviceSweepLoader:
                 pts = self.pool.flat[self.pool.offsets[ids[0]]:self.pool.offsets[ids[-1] + 1]]
             else:
                 pts = torch.cat(frames, dim=0) if len(frames) > 1 else frames[0]
+            if self.view is not None:
+                from ..selector_ops import points_view_
+                pts = points_view_(pts.clone(), self.view)      # the pool's own points stay as they are
             v = self.voxelizer(pts, off, want_voxels=self.with_points)
             B = len(ids)
             ex = {

@@ -71,6 +71,16 @@ class LazyDetections:
         torch.cuda.current_stream(boxes.device).wait_event(done)
         return ops.frame_weighted_entropy(scores, labels, counts, class_weight)
 
+    def match(self, refs, **kw):
+        """The frames' detections matched to reference boxes by the nuScenes rule (``selector_ops.match_boxes``: the
+        PPAL / CALD pre-passes), from the raw NMS buffers without materialising the detection dicts.  ``refs``:
+        ``(ref_boxes [R,>=6], ref_labels [R] i32, ref_scores [R], ref_off [B+1] i32)`` device tensors; ``kw``: ``ncls``,
+        ``dist_th``, ``max_boxes``, ``class_range``, ``origin``, ``view``."""
+        from .. import selector_ops as ops
+        boxes, scores, labels, counts, done, meta = self._raw
+        torch.cuda.current_stream(boxes.device).wait_event(done)
+        return ops.match_boxes(boxes, scores, labels, counts, *refs, **kw)
+
     def __len__(self):
         return self._batch if self._raw_ is None else self._raw_[3].shape[0]
 
@@ -79,6 +89,24 @@ class LazyDetections:
 
     def __iter__(self):
         return iter(self._materialize())
+
+
+def pack_detections(preds):
+    """Plain per-frame dicts (``CenterHead.predict``, ``TransFusionHead.predict``) -> the raw layout with one task:
+    ``(boxes [B,1,post,D], scores [B,1,post], labels [B,1,post] i32, counts [B,1] i32)``, ``post`` = the largest frame."""
+    B = len(preds)
+    first = preds[0]["box3d_lidar"]
+    post = max([1] + [int(p["scores"].shape[0]) for p in preds])
+    boxes = torch.zeros((B, 1, post, first.shape[1]), dtype=torch.float32, device=first.device)
+    scores = torch.zeros((B, 1, post), dtype=torch.float32, device=first.device)
+    labels = torch.zeros((B, 1, post), dtype=torch.int32, device=first.device)
+    for b, p in enumerate(preds):
+        k = int(p["scores"].shape[0])
+        boxes[b, 0, :k] = p["box3d_lidar"]
+        scores[b, 0, :k] = p["scores"]
+        labels[b, 0, :k] = p["label_preds"]
+    counts = torch.tensor([[int(p["scores"].shape[0])] for p in preds], dtype=torch.int32, device=first.device)
+    return boxes, scores, labels, counts
 
 
 @HEADS.register_module

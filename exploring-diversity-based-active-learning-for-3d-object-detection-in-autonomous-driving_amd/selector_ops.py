@@ -158,6 +158,86 @@ def frame_weighted_entropy(scores, labels, counts, class_weight):
     return out
 
 
+MATCH_TOO_MANY_BOXES, MATCH_CLASS_TOO_LARGE, MATCH_BAD_OFFSETS = 1, 2, 4      # AL3D_MATCH_* of include/al3d.h
+
+
+def _view4(view):
+    """``(flip_x, flip_y, rot, scale)`` -> the four host floats of the C ABI (None stays None: the identity)."""
+    if view is None:
+        return None
+    fx, fy, rot, scale = view
+    return (lib.c_flt * 4)(1.0 if fx else 0.0, 1.0 if fy else 0.0, float(rot), float(scale))
+
+
+def match_boxes(boxes, scores, labels, counts, ref_boxes, ref_labels, ref_scores, ref_off, ncls, dist_th=1.0,
+                max_boxes=500, class_range=None, origin=None, view=None):
+    """The nuScenes matching rule per frame (classwise_weight/algo.py:36-106) on the raw NMS buffers.
+
+    ``boxes [B,nt,post,D]`` f32, ``scores`` / ``labels [B,nt,post]`` f32 / i32, ``counts [B,nt]`` i32; reference boxes
+    concatenated by frame: ``ref_boxes [R,>=6]`` f32, ``ref_labels [R]`` i32, ``ref_scores [R]`` f32, ``ref_off [B+1]`` i32.
+    ``class_range [ncls]`` + ``origin [B,2]``: the range rule of the devkit's ``filter_eval_boxes``; ``view`` =
+    ``(flip_x, flip_y, rot, scale)``: the predictions come from a cloud augmented by ``points_view_`` and are mapped back.
+    Returns ``dict(match_ref [B,nt,post] i32, match_iou [B,nt,post] f32, cls_count [B,ncls] i32, cls_quality, cls_cons
+    [B,ncls] f32)``; see ``al3d_match_boxes_f32`` in include/al3d.h.  Reads the status word back (one small D2H) and raises
+    ``AssertionError`` for a frame with more than ``max_boxes`` predictions, as the devkit's ``load_prediction`` does.
+
+    Not built: the bike-rack and ``num_pts == 0`` filters of ``filter_eval_boxes`` (they need devkit tables the infos files
+    do not carry) and the lidar -> global conversion (centre distance and scale IoU are invariant under it)."""
+    boxes = _dev(boxes, torch.float32, "boxes")
+    scores = _dev(scores, torch.float32, "scores")
+    labels = _dev(labels, torch.int32, "labels")
+    counts = _dev(counts, torch.int32, "counts")
+    ref_boxes = _dev(ref_boxes, torch.float32, "ref_boxes")
+    ref_labels = _dev(ref_labels, torch.int32, "ref_labels")
+    ref_scores = _dev(ref_scores, torch.float32, "ref_scores")
+    ref_off = _dev(ref_off, torch.int32, "ref_off")
+    class_range = _dev(class_range, torch.float32, "class_range")
+    origin = _dev(origin, torch.float32, "origin")
+    if boxes.dim() != 4 or scores.shape != boxes.shape[:3] or labels.shape != boxes.shape[:3] or \
+            counts.shape != boxes.shape[:2]:
+        raise lib.Al3dError("match_boxes: boxes [B,nt,post,D], scores / labels [B,nt,post], counts [B,nt] expected")
+    B, nt, post, bd = boxes.shape
+    R = ref_boxes.shape[0]
+    if ref_boxes.dim() != 2 or ref_labels.shape != (R,) or ref_scores.shape != (R,) or ref_off.shape != (B + 1,):
+        raise lib.Al3dError("match_boxes: ref_boxes [R,>=6], ref_labels / ref_scores [R], ref_off [B+1] expected")
+    if (class_range is None) != (origin is None):
+        raise lib.Al3dError("match_boxes: class_range and origin go together")
+    if class_range is not None and (class_range.shape != (ncls,) or origin.shape != (B, 2)):
+        raise lib.Al3dError("match_boxes: class_range [ncls] and origin [B,2] expected")
+    dev = boxes.device
+    out = dict(match_ref=torch.empty((B, nt, post), dtype=torch.int32, device=dev),
+               match_iou=torch.empty((B, nt, post), dtype=torch.float32, device=dev),
+               cls_count=torch.empty((B, ncls), dtype=torch.int32, device=dev),
+               cls_quality=torch.empty((B, ncls), dtype=torch.float32, device=dev),
+               cls_cons=torch.empty((B, ncls), dtype=torch.float32, device=dev))
+    status = torch.empty((1,), dtype=torch.int32, device=dev)
+    lib.call("al3d_match_boxes_f32", _ptr(boxes), _ptr(scores), _ptr(labels), _ptr(counts), B, nt, post, bd,
+             _ptr(ref_boxes) if R else None, _ptr(ref_labels) if R else None, _ptr(ref_scores) if R else None,
+             _ptr(ref_off), R, ref_boxes.shape[1], int(ncls), float(dist_th), int(max_boxes), _ptr(class_range),
+             _ptr(origin), _view4(view), _ptr(out["match_ref"]), _ptr(out["match_iou"]), _ptr(out["cls_count"]),
+             _ptr(out["cls_quality"]), _ptr(out["cls_cons"]), _ptr(status), _stream())
+    st = int(status.item())
+    if st & MATCH_TOO_MANY_BOXES:
+        raise AssertionError(f"Error: Only <= {int(max_boxes)} boxes per sample allowed!")      # the devkit's message
+    if st & MATCH_CLASS_TOO_LARGE:
+        raise lib.Al3dError("match_boxes: one class of one frame holds more than 512 predictions or 1024 reference boxes")
+    if st:
+        raise lib.Al3dError(f"match_boxes: ref_off is not ascending inside [0, {R}] (status {st})")
+    return out
+
+
+def points_view_(points, view):
+    """In place on the xyz columns of ``points [P,F]``: ``view = (flip_x, flip_y, rot, scale)`` -- y negated if ``flip_x``,
+    x negated if ``flip_y`` (det3d's naming), then the rotation about z, then the scaling (preprocess.py:787-854)."""
+    if not isinstance(points, torch.Tensor) or not points.is_cuda or points.dtype != torch.float32 or \
+            points.dim() != 2 or not points.is_contiguous():
+        raise lib.Al3dError("points_view_: expected a contiguous [P,F] float32 device tensor (no CPU fallback)")
+    fx, fy, rot, scale = view
+    lib.call("al3d_points_view_f32", _ptr(points), points.shape[0], points.shape[1], 1 if fx else 0, 1 if fy else 0,
+             float(rot), float(scale), _stream())
+    return points
+
+
 def mask_map_(D, keep):
     """In place: D[i,j] = -inf unless keep[i] and keep[j] (keep: uint8 [n])."""
     D = _dev(D, torch.float32, "D")

@@ -1,7 +1,10 @@
 """CALD replay selector (reference det3d/selectors/cald_selector.py:18-140).
 
-Host-only: the reference's CALD numbers come from separate tools (``tools/cald_pred_list.py``,
-``tools/cald_ent.py``) that write two rankings; this class only replays them under the cost model:
+The reference's CALD numbers come from separate tools (``tools/cald_pred_list.py``, ``tools/cald_ent.py``) that write
+two rankings; this class replays them under the cost model (host-only list logic).  ``prepass=True`` first computes the
+two files with this package's own pre-pass (``selectors/prepass.py::run_cald_prepass``: two sweeps of ``detector`` over
+``dataloader``, the second over the augmented view ``prepass_view = (flip_x, flip_y, rot, scale)``, matched on the device)
+and writes them to ``buffer_path`` / ``jsdiv_path``; the replay that follows is the same either way:
 
 1. ``buffer_path`` -- a JSON list of frame ids sorted by entropy.  After dropping the labelled
    frames the list is consumed in order until the cost exceeds ``int(current_budget) + 0.5*budget``
@@ -56,12 +59,25 @@ class CaldSelector(BaseSelector):
             cost_f: float = 0.12,
             pred: bool = False,
             jsdiv_path: str = _DEFAULT_JSDIV,
+            prepass: bool = False,
+            prepass_view=(True, False, 0.0, 1.0),
     ) -> None:
         super().__init__(budget, buffer_file, dump_file_name, infos_origin=infos_origin,
                          detector=detector, dataloader=dataloader, logger=logger, cost_b=cost_b,
                          cost_f=cost_f, pred=pred)
         self.buffer_path = buffer_path
         self.jsdiv_path = jsdiv_path
+        self.prepass = prepass
+        self.prepass_view = tuple(prepass_view)
+
+    def run_prepass(self, **kwargs) -> None:
+        """Write ``buffer_path`` and ``jsdiv_path`` from two sweeps of the selector's own detector and dataloader."""
+        from .prepass import run_cald_prepass
+        if self.detector is None or self.dataloader is None:
+            raise ValueError("CaldSelector(prepass=True) needs a detector and a dataloader")
+        run_cald_prepass(self.detector, self.dataloader, self._device(kwargs), len(self.infos_origin),
+                         list(self.buffer[self.get_max_key()]), self.prepass_view, self.buffer_path, self.jsdiv_path)
+        self.detector = None
 
     def _frame_cost(self, idx: int) -> float:
         return self.infos_origin[idx]["gt_names"].shape[0] * self.cost_b
@@ -74,6 +90,8 @@ class CaldSelector(BaseSelector):
             return pickle.load(f)
 
     def select_samples(self, **kwargs) -> None:
+        if self.prepass:
+            self.run_prepass(**kwargs)
         sampled = list(self.buffer[self.get_max_key()])
         with open(self.buffer_path) as f:
             ranking = json.load(f)

@@ -1026,6 +1026,46 @@ int al3d_sp_up_table_tiles(const int* coords_out, int n_out, const int* ksize, c
 int al3d_sp_conv_any_f32(const float* fin, const int* nbr, int K, const float* wgt, int cin, int cout, const float* scale,
                          const float* shift, const float* residual, int relu, float* fout, int n_out, void* stream);
 
+/* ---------------------------------------------------------------- PPAL / CALD pre-passes
+ * The nuScenes matching rule on the raw NMS buffers, per frame.  Replaces classwise_weight/algo.py:36-106 (accumulate:
+ * sort by confidence :54, nearest free ground truth of the class :70-89, scale_iou of the match :94-103; the same lines in
+ * classwise_weight_cald/algo.py) with the range rule of the devkit's filter_eval_boxes, and the per-match reductions of
+ * tools/ppal_unc.py:74-91 (quality = score^0.6 * iou^0.4 summed per class) and tools/cald_ent.py:73-89 (consistency).
+ *
+ * Predictions: boxes [B,nt,post,box_dim] f32, scores [B,nt,post] f32, labels [B,nt,post] i32 (merged class id), counts
+ * [B,nt] i32 (clamped to [0, post]) -- the layout of al3d_head_decode_nms / al3d_center_decode_nms_f32.  Reference boxes
+ * concatenated by frame: ref_boxes [R,ref_dim] f32, ref_labels [R] i32, ref_scores [R] f32, ref_off [B+1] i32.  Of a box only
+ * columns 0, 1 (centre x, y) and 3, 4, 5 (sizes) are read.
+ *
+ * Per frame and class c: the valid predictions of label c by descending score, among equal scores the LATER position in
+ * the frame's task-major list first; each takes the nearest (xy centre distance, strictly smallest, so the earliest row
+ * wins a tie) reference row of class c that is not taken yet, iff that distance < dist_th.  Labels outside [0, ncls)
+ * never match.  class_range [ncls] + origin [B,2] (both device, or both null): a prediction or reference box whose
+ * centre lies >= class_range[label] from origin[b] is ignored.  view (HOST float[4] = flip_x, flip_y, rot, scale; null =
+ * identity): predictions are mapped back through the inverse of al3d_points_view_f32 as they are loaded (centre
+ * un-scaled, un-rotated, un-flipped; sizes divided by scale).
+ *
+ * Outputs: match_ref [B,nt,post] i32 (row of ref_boxes or -1), match_iou [B,nt,post] f32 (the devkit's scale_iou =
+ * prod(min(size_a, size_b)) / (vol_a + vol_b - that); 0 where unmatched), cls_count [B,ncls] i32, cls_quality [B,ncls]
+ * f32 (summed in matching order), cls_cons [B,ncls] f32 = min over the class's matches of |iou + 0.5 (p + q) - 1.3| with
+ * p = ref_score, q = score, seeded with 1.0 (cald_ent.py's js factor is identically 1: scipy's entropy of two scalars is
+ * 0), and *status (device int): an OR of the AL3D_MATCH_* bits, 0 when every frame was matched.  Not built: the bike-rack
+ * and num_pts == 0 filters of filter_eval_boxes (they need devkit tables) and the lidar -> global conversion (centre
+ * distance and scale IoU are invariant under it). */
+#define AL3D_MATCH_TOO_MANY_BOXES 1   /* a frame holds more than max_boxes valid predictions (load_prediction's assert) */
+#define AL3D_MATCH_CLASS_TOO_LARGE 2  /* one class of one frame: more than 512 predictions or 1024 reference rows */
+#define AL3D_MATCH_BAD_OFFSETS 4      /* ref_off is not ascending inside [0, R] */
+int al3d_match_boxes_f32(const float* boxes, const float* scores, const int* labels, const int* counts, int B, int nt,
+                         int post, int box_dim, const float* ref_boxes, const int* ref_labels, const float* ref_scores,
+                         const int* ref_off, int R, int ref_dim, int ncls, float dist_th, int max_boxes,
+                         const float* class_range, const float* origin, const float* view, int* match_ref,
+                         float* match_iou, int* cls_count, float* cls_quality, float* cls_cons, int* status, void* stream);
+/* The augmented view CALD compares against, in place on the xyz columns of points [P,F] (F >= 3): y negated if flip_x, x
+ * negated if flip_y (det3d/core/sampler/preprocess.py:829-854, random_flip_both's naming), then the rotation about z of
+ * box_np_ops.py:396-418 (x' = cos x + sin y, y' = -sin x + cos y; preprocess.py:796-813), then xyz times scale
+ * (preprocess.py:787-793). */
+int al3d_points_view_f32(float* points, int64_t P, int F, int flip_x, int flip_y, float rot, float scale, void* stream);
+
 /* ---------------------------------------------------------------- runtime
  * A HIP stream restricted to n_cus compute units starting at first_cu (hipExtStreamCreateWithCUMask); the
  * reference has no analogue (its loader workers are host processes, det3d/datasets/loader/build_loader.py:23-59):
