@@ -26,14 +26,48 @@ def pack_deconv_weight(w):
     return w.detach().permute(1, 2, 3, 0).reshape(co, 4, ci).contiguous().float()
 
 
-def fold_bn(bn):
-    """eval BatchNorm -> (scale, shift): y = x*scale + shift."""
+def fold_bn(bn, bias=None):
+    """eval BatchNorm -> (scale, shift): y = x*scale + shift.  ``bias``: the bias of the layer in front of it, folded in as
+    (x + b) * s + t in float32 on the rounded scale and shift."""
     inv = torch.rsqrt(bn.running_var.detach().double() + bn.eps)
     g = bn.weight.detach().double() if bn.weight is not None else torch.ones_like(inv)
     b = bn.bias.detach().double() if bn.bias is not None else torch.zeros_like(inv)
     scale = g * inv
     shift = b - bn.running_mean.detach().double() * scale
-    return scale.float().contiguous(), shift.float().contiguous()
+    scale, shift = scale.float().contiguous(), shift.float().contiguous()
+    if bias is not None:
+        shift = shift + bias.detach().float().to(scale.device) * scale
+    return scale, shift
+
+
+def fold_conv_bn(pairs, swap_hw=False, first=0, pad_cin=False, deconv=False):
+    """[(conv, eval BatchNorm2d or None)] reading ONE input -> (w [Cout_total, taps, Cin] f32, scale, shift) of the single
+    launch with their output channels side by side: y = conv(x, w) * scale + shift (no BatchNorm: scale 1, shift 0; a
+    conv bias is folded as ``fold_bn`` does).  ``swap_hw``: the kernels' two spatial axes swapped (the map is [y, x], the
+    weights [x, y]); ``first``: the map holds the input channels rotated, [channels first: | channels :first];
+    ``pad_cin``: Cin zero-padded to a multiple of 16 (the matrix-core kernels' step; the caller pads the map);
+    ``deconv``: ConvTranspose2d 2x2 weights (``pack_deconv_weight``).  Pure torch, on the parameters' device."""
+    ws, scales, shifts = [], [], []
+    for conv, bn in pairs:
+        w = conv.weight.detach().float()
+        if bn is not None:
+            scale, shift = fold_bn(bn, conv.bias)
+        else:
+            scale = torch.ones(conv.out_channels, device=w.device)
+            shift = torch.zeros(conv.out_channels, device=w.device)
+            if conv.bias is not None:
+                shift = shift + conv.bias.detach().float() * scale
+        if swap_hw:
+            w = w.transpose(2, 3)
+        if first:
+            w = torch.cat([w[:, first:], w[:, :first]], dim=1)
+        ws.append(pack_deconv_weight(w) if deconv else pack_conv_weight(w))
+        scales.append(scale)
+        shifts.append(shift)
+    w = torch.cat(ws)
+    if pad_cin and w.shape[2] % 16:
+        w = torch.nn.functional.pad(w, (0, 16 - w.shape[2] % 16))
+    return w, torch.cat(scales), torch.cat(shifts)
 
 
 def split_bf16x3(w_packed):

@@ -13,6 +13,7 @@ from .. import lib
 from .. import detector_ops as D
 from ..detector_ops import fold_bn
 from ..selector_ops import _ptr, _stream
+from ..weight_cache import PackCache
 from .registry import BACKBONES
 
 
@@ -89,6 +90,10 @@ class _Level:
 
 
 class _SparseEncoderBase(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.packs = PackCache()
+
     def _stages(self):
         raise NotImplementedError
 
@@ -121,26 +126,18 @@ class _SparseEncoderBase(nn.Module):
             m = s_["mod"]
             s_["sp"], s_["cin"], s_["cols"] = D.sparse_structure(m.in_channels, m.out_channels, int(np.prod(m.kernel_size)),
                                                                  m.subm, raster_ok)
-        key = (device, tuple((s_["sp"], s_["cin"], s_["cols"]) for s_ in convs))
-        if getattr(self, "_packed_dev", None) == key:
-            return
-        # one pack per structure list (see RPN._prepare).  The level grids do not depend on the pack and every call leaves
-        # them clean: a new pack keeps them
-        packs = self.__dict__.setdefault("_packs", {})
-        if getattr(self, "_packed_dev", None) is None:
-            packs.clear()
-        if key not in packs:
+        def build():
             for s_ in convs:
                 m = s_["mod"]
-                scale, shift = fold_bn(s_.pop("bn"))
-                if s_.pop("bias", False) and m.bias is not None:   # (x + b) * s + t
-                    shift = shift + m.bias.detach().float().to(scale.device) * scale
+                scale, shift = fold_bn(s_["bn"], m.bias if s_.get("bias") else None)
                 w = m.weight.detach().reshape(-1, m.in_channels, m.out_channels).float().to(device)
                 s_["w"], s_["scale"] = D.sparse_pack(s_["sp"], w, scale.to(device), s_["cin"])
                 s_["shift"] = shift.to(device)
-            packs[key] = plan
-        self._plan = packs[key]
-        self._packed_dev = key
+            return plan
+        # one pack per structure list (see RPN._prepare).  The level grids do not depend on the pack and every call leaves
+        # them clean: a new pack keeps them
+        self._plan = self.packs.get(device, [m_ for s_ in convs for m_ in (s_["mod"], s_["bn"])],
+                                    tuple((s_["sp"], s_["cin"], s_["cols"]) for s_ in convs), build)
         self.__dict__.setdefault("_levels", {})
 
     @staticmethod

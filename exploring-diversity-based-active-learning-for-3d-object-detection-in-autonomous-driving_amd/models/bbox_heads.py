@@ -11,6 +11,7 @@ from torch import nn
 from .. import detector_ops as D
 from .. import lib
 from ..selector_ops import _ptr, _stream
+from ..weight_cache import PackCache
 from .registry import HEADS
 
 
@@ -150,6 +151,17 @@ class MultiGroupHead(nn.Module):
         self.tasks = nn.ModuleList()
         for nc, na in zip(num_classes, self.num_anchor_per_locs):
             self.tasks.append(Head(in_channels, na * self.box_n_dim, na * nc, header=False))
+        # channel order of the fused output: the box regressions of all tasks, then the class logits of all tasks.
+        # The score pre-pass of the decode reads ONLY the class logits: kept together (36 of 236 channels for the six
+        # CBGS tasks) they are two 128-byte lines of a pixel's 944-byte record instead of pieces of all eight
+        # (head_score_kernel 1.04 -> 0.3 ms per batch of 128).  The offsets travel with the C call.
+        self._convs = [t.conv_box for t in self.tasks] + [t.conv_cls for t in self.tasks]
+        offs = [0]
+        for c in self._convs:
+            offs.append(offs[-1] + c.out_channels)
+        nt = len(self.tasks)
+        self._box_off, self._cls_off, self._ch = offs[:nt], offs[nt:-1], offs[-1]
+        self.packs = PackCache()
         self.logger.info("Finish MultiGroupHead Initialization")
 
     def init_weights(self, pretrained=None):
@@ -161,39 +173,14 @@ class MultiGroupHead(nn.Module):
 
     # ------------------------------------------------------------ fused 1x1 convs
     def _prepare(self, device):
-        key = (device, D.MATH, D.DENSE)
-        if getattr(self, "_packed_dev", None) == key:
-            return
+        convs = self._convs
+
+        def build():
+            w, scale = D.pack_dense(D.pack_conv_weight(torch.cat([c.weight.detach() for c in convs], dim=0)).to(device),
+                                    None, 1, 1, 0)
+            return w, scale, torch.cat([c.bias.detach() for c in convs]).float().contiguous().to(device)
         # one pack per arithmetic (see RPN._prepare)
-        packs = self.__dict__.setdefault("_packs", {})
-        if getattr(self, "_packed_dev", None) is None:
-            packs.clear()
-        if key in packs:
-            self._box_off, self._cls_off, self._ch, self._w, self._wscale, self._b = packs[key]
-            self._packed_dev = key
-            return
-        # channel order of the fused output: the box regressions of all tasks, then the class logits of all tasks.
-        # The score pre-pass of the decode reads ONLY the class logits: kept together (36 of 236 channels for the six
-        # CBGS tasks) they are two 128-byte lines of a pixel's 944-byte record instead of pieces of all eight
-        # (head_score_kernel 1.04 -> 0.3 ms per batch of 128).  The offsets travel with the C call.
-        ws, bs, self._box_off, self._cls_off = [], [], [], []
-        off = 0
-        for t in self.tasks:
-            self._box_off.append(off)
-            ws.append(t.conv_box.weight)
-            bs.append(t.conv_box.bias)
-            off += t.conv_box.out_channels
-        for t in self.tasks:
-            self._cls_off.append(off)
-            ws.append(t.conv_cls.weight)
-            bs.append(t.conv_cls.bias)
-            off += t.conv_cls.out_channels
-        self._ch = off
-        self._w, self._wscale = D.pack_dense(
-            D.pack_conv_weight(torch.cat([w.detach() for w in ws], dim=0)).to(device), None, 1, 1, 0)
-        self._b = torch.cat([b.detach() for b in bs]).float().contiguous().to(device)
-        packs[key] = (self._box_off, self._cls_off, self._ch, self._w, self._wscale, self._b)
-        self._packed_dev = key
+        self._w, self._wscale, self._b = self.packs.get(device, convs, (D.MATH, D.DENSE), build)
 
     def accepts_pair(self, device):
         """True when the fused head convolution runs on the LDS-DMA kernel and can read pair pixels."""

@@ -13,7 +13,7 @@ from torch import nn
 
 from .. import detector_ops as D
 from .. import lib
-from .bevfusion_camera import _ConvAffine
+from .conv_layers import FoldedConv
 from .registry import HEADS
 
 
@@ -64,9 +64,7 @@ class BEVSegmentationHead(nn.Module):
             nn.Conv2d(in_channels, in_channels, 3, padding=1, bias=False), nn.BatchNorm2d(in_channels), nn.ReLU(True),
             nn.Conv2d(in_channels, in_channels, 3, padding=1, bias=False), nn.BatchNorm2d(in_channels), nn.ReLU(True),
             nn.Conv2d(in_channels, len(classes), 1))
-        # kept OUT of the module tree: the state dict holds the reference's keys and nothing else
-        object.__setattr__(self, "_run", [_ConvAffine(self.classifier[0], self.classifier[1], True),
-                                          _ConvAffine(self.classifier[3], self.classifier[4], True)])
+        self._run = [FoldedConv([(self.classifier[0], self.classifier[1])]), FoldedConv([(self.classifier[3], self.classifier[4])])]
 
     def forward(self, x, target=None, with_stats=False):
         if self.training:

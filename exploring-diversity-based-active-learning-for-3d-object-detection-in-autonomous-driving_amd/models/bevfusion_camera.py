@@ -20,6 +20,8 @@ from torch import nn
 from .. import detector_ops as D
 from .. import lib
 from ..selector_ops import _dev, _ptr, _stream
+from ..weight_cache import PackCache
+from .conv_layers import FoldedConv
 from .registry import NECKS
 
 
@@ -63,38 +65,6 @@ def _mat3(a, b):
     return (a.unsqueeze(-1) * b.unsqueeze(-3)).sum(-2)
 
 
-def _versions(*mods):
-    """Version counters of every parameter / buffer of ``mods``: ``load_state_dict`` and in-place edits bump them, so a
-    packed-weight cache keyed on this is rebuilt after weights change."""
-    out = []
-    for m in mods:
-        if m is None:
-            continue
-        for t in list(m.parameters(recurse=False)) + list(m.buffers(recurse=False)):
-            out.append((t.data_ptr(), t._version))
-    return tuple(out)
-
-
-class _ConvBNReLU(nn.Module):
-    """Conv2d(bias=False) + BatchNorm2d + ReLU on channels-last maps through the f16x3 / bf16x6 / f32 conv kernels."""
-
-    def __init__(self, conv, bn):
-        super().__init__()
-        self.conv, self.bn = conv, bn
-        self._packed = None
-
-    def forward(self, x):
-        key = (x.device, D.MATH, D.DENSE, _versions(self.conv, self.bn))
-        if self._packed is None or self._packed[0] != key:
-            scale, shift = D.fold_bn(self.bn)
-            c = self.conv
-            geom = (c.kernel_size[0], c.stride[0], c.padding[0]) if c.in_channels % 16 == 0 else (None, None, None)
-            w, scale = D.pack_dense(D.pack_conv_weight(c.weight).to(x.device), scale.to(x.device), *geom)
-            self._packed = (key, w, scale, shift.to(x.device))
-        _, w, scale, shift = self._packed
-        return D.conv2d_nhwc(x, w, scale, shift, self.conv.kernel_size[0], self.conv.stride[0], self.conv.padding[0], True)
-
-
 class LSSViewTransform(nn.Module):
     """``DepthLSSTransform`` minus its depth net: frustum + geometry + BEV pooling + ``downsample``.
 
@@ -118,7 +88,7 @@ class LSSViewTransform(nn.Module):
                 nn.Conv2d(c, c, 3, padding=1, bias=False), nn.BatchNorm2d(c), nn.ReLU(True),
                 nn.Conv2d(c, c, 3, stride=downsample, padding=1, bias=False), nn.BatchNorm2d(c), nn.ReLU(True),
                 nn.Conv2d(c, c, 3, padding=1, bias=False), nn.BatchNorm2d(c), nn.ReLU(True))
-            self._ds = [_ConvBNReLU(self.downsample[i], self.downsample[i + 1]) for i in (0, 3, 6)]
+            self._ds = [FoldedConv([(self.downsample[i], self.downsample[i + 1])]) for i in (0, 3, 6)]
         else:
             self.downsample, self._ds = nn.Identity(), []
 
@@ -267,8 +237,7 @@ class ConvFuser(nn.Sequential):
         self.in_channels, self.out_channels = in_channels, out_channels
         super().__init__(nn.Conv2d(sum(in_channels), out_channels, 3, padding=1, bias=False),
                          nn.BatchNorm2d(out_channels), nn.ReLU(True))
-        # kept OUT of the module tree: the state dict holds the reference's keys (0.weight, 1.*) and nothing else
-        object.__setattr__(self, "_run", _ConvBNReLU(self[0], self[1]))
+        self._run = FoldedConv([(self[0], self[1])])     # no module: the state dict holds the reference's keys (0.weight, 1.*) only
 
     def forward(self, inputs, first_hw_swapped=False):
         """inputs: the channels-last BEV maps; ``first_hw_swapped``: the first one (the camera map) is still in the view
@@ -281,42 +250,6 @@ class ConvFuser(nn.Sequential):
         return self._run(torch.cat(inputs, dim=-1).contiguous())
 
 
-class _ConvAffine(nn.Module):
-    """Conv2d (+ bias) [+ BatchNorm2d] [+ ReLU] on channels-last maps through the dense conv kernels.  Input channels
-    are zero-padded to a multiple of 16 (weights too), which the matrix-core kernels need; any Cout."""
-
-    def __init__(self, conv, bn=None, relu=True):
-        super().__init__()
-        self.conv, self.bn, self.relu = conv, bn, relu
-        self._packed = None
-
-    def forward(self, x):
-        key = (x.device, D.MATH, D.DENSE, _versions(self.conv, self.bn))
-        conv = self.conv
-        cin = conv.in_channels
-        cpad = (cin + 15) // 16 * 16
-        if self._packed is None or self._packed[0] != key:
-            if self.bn is not None:
-                scale, shift = D.fold_bn(self.bn)
-                scale, shift = scale.cpu(), shift.cpu()
-            else:
-                scale = torch.ones(conv.out_channels)
-                shift = torch.zeros(conv.out_channels)
-            if conv.bias is not None:                                    # (x + b) * s + t
-                shift = shift + conv.bias.detach().float().cpu() * scale
-            w = conv.weight.detach().float()
-            if cpad != cin:
-                w = torch.nn.functional.pad(w, (0, 0, 0, 0, 0, cpad - cin))
-            k, s, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
-            wp, scale = D.pack_dense(D.pack_conv_weight(w).to(x.device), scale.to(x.device), k, s, p)
-            self._packed = (key, wp, scale, shift.to(x.device))
-        _, wp, scale, shift = self._packed
-        if cpad != cin:
-            x = torch.nn.functional.pad(x, (0, cpad - cin))
-        return D.conv2d_nhwc(x.contiguous(), wp, scale, shift, conv.kernel_size[0], conv.stride[0], conv.padding[0],
-                             self.relu)
-
-
 class _ConvModule(nn.Module):
     """mmcv ``ConvModule`` (conv -> bn -> ReLU) with its parameter names (``conv.weight``, ``bn.*``)."""
 
@@ -324,7 +257,7 @@ class _ConvModule(nn.Module):
         super().__init__()
         self.conv = nn.Conv2d(cin, cout, k, padding=padding, bias=False)
         self.bn = nn.BatchNorm2d(cout)
-        object.__setattr__(self, "_run", _ConvAffine(self.conv, self.bn, True))     # not a submodule: no duplicate keys
+        self._run = FoldedConv([(self.conv, self.bn)])
 
     def forward(self, x):
         return self._run(x)
@@ -399,9 +332,10 @@ class DepthLSSTransform(LSSViewTransform):
             nn.Conv2d(in_channels + 64, in_channels, 3, padding=1), nn.BatchNorm2d(in_channels), nn.ReLU(True),
             nn.Conv2d(in_channels, in_channels, 3, padding=1), nn.BatchNorm2d(in_channels), nn.ReLU(True),
             nn.Conv2d(in_channels, self.D + self.C, 1))
-        self._dt = [_ConvAffine(self.dtransform[i], self.dtransform[i + 1], True) for i in (0, 3, 6)]
-        self._dn = [_ConvAffine(self.depthnet[0], self.depthnet[1], True), _ConvAffine(self.depthnet[3], self.depthnet[4], True),
-                    _ConvAffine(self.depthnet[6], None, False)]
+        self._dt = [FoldedConv([(self.dtransform[i], self.dtransform[i + 1])]) for i in (0, 3, 6)]
+        self._dn = [FoldedConv([(self.depthnet[0], self.depthnet[1])]), FoldedConv([(self.depthnet[3], self.depthnet[4])]),
+                    FoldedConv([(self.depthnet[6], None)], relu=False)]
+        self._dt01 = PackCache()
 
     def _calib_cached(self, slot, calib_key, build):
         """Small tensors that are functions of the calibration matrices only (matrix rows for the depth image, the frustum
@@ -446,21 +380,13 @@ class DepthLSSTransform(LSSViewTransform):
         [BN, iH, iW] -> [BN, oH, oW, 32] (``al3d_lss_dtransform01_f32``): the eight-channel full-resolution map -- 554 MB per
         16 samples, written, zero-padded to 16 channels and read back by the matrix-core path -- is never formed."""
         c0, b0, c1, b1 = self.dtransform[0], self.dtransform[1], self.dtransform[3], self.dtransform[4]
-        key = (d.device, _versions(c0, b0, c1, b1))
-        if getattr(self, "_dt01", None) is None or self._dt01[0] != key:
-            def affine(conv, bn):
-                scale, shift = D.fold_bn(bn)
-                scale, shift = scale.cpu().float(), shift.cpu().float()
-                if conv.bias is not None:
-                    shift = shift + conv.bias.detach().float().cpu() * scale
-                return scale, shift
-            s0, t0 = affine(c0, b0)
-            s1, t1 = affine(c1, b1)
-            p0 = torch.cat([c0.weight.detach().float().cpu().reshape(8), s0, t0]).contiguous().to(d.device)
-            w1 = c1.weight.detach().float().cpu().permute(2, 3, 1, 0).contiguous().to(d.device)      # [ky][kx][c][co]
-            p1 = torch.cat([s1, t1]).contiguous().to(d.device)
-            self._dt01 = (key, p0, w1, p1)
-        _, p0, w1, p1 = self._dt01
+        def build():
+            s0, t0 = D.fold_bn(b0, c0.bias)
+            s1, t1 = D.fold_bn(b1, c1.bias)
+            p0 = torch.cat([c0.weight.detach().float().reshape(8), s0, t0]).contiguous().to(d.device)
+            w1 = c1.weight.detach().float().permute(2, 3, 1, 0).contiguous().to(d.device)      # [ky][kx][c][co]
+            return p0, w1, torch.cat([s1, t1]).contiguous().to(d.device)
+        p0, w1, p1 = self._dt01.get(d.device, (c0, b0, c1, b1), None, build)       # an fp32 kernel: one variant
         BN, iH, iW = d.shape
         d = _dev(d, torch.float32, "depth image")
         out = torch.empty((BN, (iH - 1) // 4 + 1, (iW - 1) // 4 + 1, 32), dtype=torch.float32, device=d.device)

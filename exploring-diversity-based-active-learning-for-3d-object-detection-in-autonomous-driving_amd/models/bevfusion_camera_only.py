@@ -20,8 +20,10 @@ from torch import nn
 from .. import detector_ops as D
 from .. import lib
 from ..selector_ops import _dev, _ptr, _stream
+from ..weight_cache import PackCache
 from . import builder
-from .bevfusion_camera import LSSViewTransform, _ConvAffine, _versions
+from .bevfusion_camera import LSSViewTransform
+from .conv_layers import FoldedConv
 from .registry import BACKBONES, DETECTORS, NECKS
 
 
@@ -44,22 +46,21 @@ class BasicBlock(nn.Module):
         self.conv2 = nn.Conv2d(planes, planes, 3, padding=1, bias=False)
         self.bn2 = nn.BatchNorm2d(planes)
         self.downsample = downsample
-        # kept OUT of the module tree: the state dict holds the block's own keys and nothing else
-        object.__setattr__(self, "_c1", _ConvAffine(self.conv1, self.bn1, True))
-        object.__setattr__(self, "_sc", None if downsample is None else _ConvAffine(downsample[0], downsample[1], False))
-        object.__setattr__(self, "_packed", None)
+        self._c1 = FoldedConv([(self.conv1, self.bn1)])
+        self._sc = None if downsample is None else FoldedConv([(downsample[0], downsample[1])], relu=False)
+        self._conv2 = PackCache()
 
     def forward(self, x):
         if self.training:
             raise RuntimeError("al3d BasicBlock implements the eval() path only")
         two_step = D.MATH == "f16x3" and D.RES == "two-step"
-        key = (x.device, D.MATH, D.DENSE, two_step, _versions(self.conv2, self.bn2))
-        if self._packed is None or self._packed[0] != key:
-            scale, shift = D.fold_bn(self.bn2)
-            w = D.pack_conv_weight(self.conv2.weight).to(x.device)
-            w, scale = D.pack_dense(w, scale.to(x.device), 3, 1, 1) if two_step else D.pack_res3x3(w, scale.to(x.device))
-            object.__setattr__(self, "_packed", (key, w, scale, shift.to(x.device)))
-        _, w, scale, shift = self._packed
+
+        def build():
+            w, scale, shift = D.fold_conv_bn([(self.conv2, self.bn2)])
+            w, scale = w.to(x.device), scale.to(x.device)
+            w, scale = D.pack_dense(w, scale, 3, 1, 1) if two_step else D.pack_res3x3(w, scale)
+            return w, scale, shift.to(x.device)
+        w, scale, shift = self._conv2.get(x.device, (self.conv2, self.bn2), (D.MATH, D.DENSE, two_step), build)
         y = self._c1(x)
         identity = x if self._sc is None else self._sc(x)
         if two_step:
@@ -101,28 +102,6 @@ class GeneralizedResNet(nn.ModuleList):
         return outputs
 
 
-class _ConvBNReLURotated(nn.Module):
-    """1x1 Conv2d(bias=False) + BatchNorm2d + ReLU whose input map holds the conv's input channels rotated: the map is
-    [channels first: | channels :first] (the upsample + concatenation kernel writes the lateral map before the
-    upsampled one, the reference concatenates them the other way round).  The weight columns are rotated when packed."""
-
-    def __init__(self, conv, bn, first):
-        super().__init__()
-        self.conv, self.bn, self.first = conv, bn, first
-        self._packed = None
-
-    def forward(self, x):
-        key = (x.device, D.MATH, D.DENSE, _versions(self.conv, self.bn))
-        if self._packed is None or self._packed[0] != key:
-            scale, shift = D.fold_bn(self.bn)
-            w = self.conv.weight.detach().float()
-            w = torch.cat([w[:, self.first:], w[:, :self.first]], dim=1)
-            wp, scale = D.pack_dense(D.pack_conv_weight(w).to(x.device), scale.to(x.device), 1, 1, 0)
-            self._packed = (key, wp, scale, shift.to(x.device))
-        _, wp, scale, shift = self._packed
-        return D.conv2d_nhwc(x, wp, scale, shift, 1, 1, 0, True)
-
-
 @NECKS.register_module
 class LSSFPN(nn.Module):
     """necks/lss.py:12-65: ``cat([interpolate(x[in_indices[0]], size of x[in_indices[1]], bilinear, align_corners=True),
@@ -138,13 +117,14 @@ class LSSFPN(nn.Module):
         self.fuse = nn.Sequential(
             nn.Conv2d(in_channels[0] + in_channels[1], out_channels, 1, bias=False), nn.BatchNorm2d(out_channels), nn.ReLU(True),
             nn.Conv2d(out_channels, out_channels, 3, padding=1, bias=False), nn.BatchNorm2d(out_channels), nn.ReLU(True))
-        run = [_ConvBNReLURotated(self.fuse[0], self.fuse[1], in_channels[0]), _ConvAffine(self.fuse[3], self.fuse[4], True)]
+        # the upsample + concatenation kernel writes the lateral map before the upsampled one, the reference concatenates
+        # them the other way round: the 1x1 conv's weight columns are rotated by in_channels[0] when packed
+        self._run = [FoldedConv([(self.fuse[0], self.fuse[1])], first=in_channels[0]), FoldedConv([(self.fuse[3], self.fuse[4])])]
         if self.scale_factor > 1:
             self.upsample = nn.Sequential(
                 nn.Upsample(scale_factor=scale_factor, mode="bilinear", align_corners=True),
                 nn.Conv2d(out_channels, out_channels, 3, padding=1, bias=False), nn.BatchNorm2d(out_channels), nn.ReLU(True))
-            run.append(_ConvAffine(self.upsample[1], self.upsample[2], True))
-        object.__setattr__(self, "_run", run)
+            self._run.append(FoldedConv([(self.upsample[1], self.upsample[2])]))
 
     def forward(self, x):
         if self.training:
@@ -181,7 +161,7 @@ class LSSTransform(LSSViewTransform):
                          list(dbound), downsample)
         self.in_channels = in_channels
         self.depthnet = nn.Conv2d(in_channels, self.D + self.C, 1)
-        object.__setattr__(self, "_dn", _ConvAffine(self.depthnet, None, False))
+        self._dn = FoldedConv([(self.depthnet, None)], relu=False)
 
     def get_cam_feats(self, x):
         """x [B,N,fH,fW,Cin] -> (depth probabilities [B*N,D,fH,fW], context [B*N,fH,fW,C]); the reference's return value

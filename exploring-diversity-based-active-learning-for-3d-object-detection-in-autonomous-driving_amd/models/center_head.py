@@ -22,7 +22,8 @@ import torch
 from torch import nn
 
 from .. import detector_ops as D
-from .bevfusion_camera import _versions
+from ..weight_cache import PackCache
+from .conv_layers import FoldedConv
 from .registry import HEADS
 
 
@@ -33,28 +34,6 @@ class _ConvModule2d(nn.Module):
         super().__init__()
         self.conv = nn.Conv2d(cin, cout, k, padding=k // 2, bias=False)
         self.bn = nn.BatchNorm2d(cout)
-
-
-def _pack_first(mods, transpose, device):
-    """[(conv, bn)] sharing one input -> (packed weights, scale, shift) of the single dense launch with their output
-    channels side by side.  ``transpose``: swap the kernels' two spatial axes (the map is [y, x], the weights [x, y])."""
-    ws, scales, shifts = [], [], []
-    for conv, bn in mods:
-        w = conv.weight.detach().float()
-        ws.append(w.transpose(2, 3) if transpose else w)
-        s, t = D.fold_bn(bn)
-        if conv.bias is not None:
-            t = t + conv.bias.detach().float() * s
-        scales.append(s)
-        shifts.append(t)
-    w = torch.cat(ws)
-    cin = w.shape[1]
-    cpad = (cin + 15) // 16 * 16
-    if cpad != cin:
-        w = nn.functional.pad(w, (0, 0, 0, 0, 0, cpad - cin))
-    k = w.shape[2]
-    wp, scale = D.pack_dense(D.pack_conv_weight(w).to(device), torch.cat(scales).to(device), k, 1, k // 2)
-    return wp, scale, torch.cat(shifts).to(device), k, cpad
 
 
 @HEADS.register_module
@@ -80,7 +59,11 @@ class SeparateHead(nn.Module):
             setattr(self, head, nn.Sequential(*layers))
         if "heatmap" in self.heads:
             getattr(self, "heatmap")[-1].bias.data.fill_(init_bias)
-        object.__setattr__(self, "_packed", None)
+        # all targets' first layers as ONE dense launch, their 64 channels side by side (other depths: _check refuses them)
+        if all(n == 2 for _, n in self.heads.values()):
+            self._first = FoldedConv([(getattr(self, h)[0].conv, getattr(self, h)[0].bn) for h in self.heads],
+                                     swap_hw=self.transpose_input)
+        self._last = PackCache()
 
     @property
     def out_channels(self):
@@ -101,34 +84,26 @@ class SeparateHead(nn.Module):
                                       "and <= 8 channels per target (every CenterHead config of the reference)")
 
     def pack(self, device):
+        """(grouped weights [sum of channels, 9, 64], bias) of the targets' last layers."""
         self._check()
-        names = list(self.heads)
-        mods = [m for h in names for m in (getattr(self, h)[0].conv, getattr(self, h)[0].bn, getattr(self, h)[1])]
-        key = (torch.device(device), D.MATH, D.DENSE, _versions(*mods))
-        if self._packed is None or self._packed[0] != key:
-            first = _pack_first([(getattr(self, h)[0].conv, getattr(self, h)[0].bn) for h in names], self.transpose_input, device)
-            lw = []
-            for h in names:
-                w = getattr(self, h)[1].weight.detach().float()
-                lw.append(D.pack_conv_weight(w.transpose(2, 3) if self.transpose_input else w))
-            w2 = torch.cat(lw).to(device).contiguous()
-            b2 = torch.cat([getattr(self, h)[1].bias.detach().float() for h in names]).to(device).contiguous()
-            object.__setattr__(self, "_packed", (key, first, w2, b2))
-        return self._packed[1:]
+        last = [getattr(self, h)[1] for h in self.heads]
+
+        def build():
+            ws = [m.weight.detach().float() for m in last]
+            w2 = torch.cat([D.pack_conv_weight(w.transpose(2, 3) if self.transpose_input else w) for w in ws])
+            return w2.to(device).contiguous(), torch.cat([m.bias.detach().float() for m in last]).to(device).contiguous()
+        return self._last.get(device, last, None, build)             # an fp32 kernel: one variant
 
     def run_into(self, x, out, base):
         """x [B,H,W,in] channels-last -> this task's channels written at ``base`` of ``out`` [B,H,W,CH]."""
-        (wp, scale, shift, k, cpad), w2, b2 = self.pack(x.device)
-        if cpad != x.shape[3]:
-            x = nn.functional.pad(x, (0, cpad - x.shape[3]))
+        w2, b2 = self.pack(x.device)
         B, H, W, _ = x.shape
         G = len(self.heads)
         cout = [c for c, _ in self.heads.values()]
         coff = [a for a, _ in self.spans(base).values()]
         n = max(1, self.CHUNK_BYTES // (H * W * G * 64 * 4))
         for s in range(0, B, n):
-            mid = D.conv2d_nhwc(x[s:s + n].contiguous(), wp, scale, shift, k, 1, k // 2, True)
-            D.conv3x3_grouped_nhwc(mid, w2, b2, cout, coff, out=out[s:s + n])
+            D.conv3x3_grouped_nhwc(self._first(x[s:s + n]), w2, b2, cout, coff, out=out[s:s + n])
         return out
 
     def forward(self, x):
@@ -181,7 +156,7 @@ class CenterHead(nn.Module):
             heads.update(dict(heatmap=(num_cls, num_heatmap_convs)))
             self.task_heads.append(SeparateHead(in_channels=share_conv_channel, heads=heads, transpose_input=self.transpose_input,
                                                 **{k: v for k, v in sep.items() if k not in ("in_channels", "heads", "num_cls")}))
-        object.__setattr__(self, "_shared", None)
+        self._shared = FoldedConv([(self.shared_conv.conv, self.shared_conv.bn)], swap_hw=self.transpose_input)
 
     # ---------------------------------------------------------------- graph
     def _layout(self):
@@ -195,14 +170,7 @@ class CenterHead(nn.Module):
     def forward(self, x, finetune=False, **_unused):
         if self.training:
             raise RuntimeError("al3d CenterHead implements the eval() path only")
-        sc = self.shared_conv
-        key = (x.device, D.MATH, D.DENSE, _versions(sc.conv, sc.bn))
-        if self._shared is None or self._shared[0] != key:
-            object.__setattr__(self, "_shared", (key, _pack_first([(sc.conv, sc.bn)], self.transpose_input, x.device)))
-        wp, scale, shift, k, cpad = self._shared[1]
-        if cpad != x.shape[3]:
-            x = nn.functional.pad(x, (0, cpad - x.shape[3]))
-        feat = D.conv2d_nhwc(x.contiguous(), wp, scale, shift, k, 1, k // 2, True)
+        feat = self._shared(x)
         B, H, W, _ = feat.shape
         CH, spans = self._layout()
         fused = torch.empty((B, H, W, CH), dtype=torch.float32, device=x.device)

@@ -10,6 +10,7 @@ import torch
 from torch import nn
 
 from .. import detector_ops as D
+from ..weight_cache import PackCache
 from .registry import NECKS
 
 
@@ -54,6 +55,7 @@ class RPN(nn.Module):
                 deblocks.append(nn.Sequential(up, bn(cout), nn.ReLU()))
         self.blocks = nn.ModuleList(blocks)
         self.deblocks = nn.ModuleList(deblocks)
+        self.packs = PackCache()
         if logger is not None:
             logger.info("Finish RPN Initialization")
 
@@ -70,45 +72,34 @@ class RPN(nn.Module):
                 nn.init.xavier_uniform_(m.weight)
 
     def _prepare(self, device):
-        key = (device, D.MATH, D.DENSE)
-        if getattr(self, "_packed_dev", None) == key:
-            return
-        # one pack per arithmetic: a sweep that re-runs a batch under bf16x6 (AL3D_MATH=auto) flips back without re-packing.
-        # _packed_dev = None (never packed, or a caller asking for a fresh pack) drops them all
-        packs = self.__dict__.setdefault("_packs", {})
-        if getattr(self, "_packed_dev", None) is None:
-            packs.clear()
-        if key in packs:
-            self._blocks_p, self._deblocks_p = packs[key]
-            self._packed_dev = key
-            return
-        self._blocks_p, self._deblocks_p = [], []
-        for blk in self.blocks:
-            mods = list(blk.children())
-            convs = []
-            for j, m in enumerate(mods):
-                if isinstance(m, nn.Conv2d):
-                    scale, shift = D.fold_bn(mods[j + 1])
-                    pad = 1 if (j > 0 and isinstance(mods[j - 1], nn.ZeroPad2d)) else m.padding[0]
-                    w, scale = D.pack_dense(D.pack_conv_weight(m.weight).to(device), scale.to(device),
-                                            m.kernel_size[0], m.stride[0], pad)
-                    convs.append(dict(w=w, scale=scale, shift=shift.to(device), k=m.kernel_size[0],
-                                      s=m.stride[0], p=pad))
-            self._blocks_p.append(convs)
-        for de in self.deblocks:
-            up, bn = de[0], de[1]
-            scale, shift = D.fold_bn(bn)
-            if isinstance(up, nn.ConvTranspose2d):
-                assert up.kernel_size == (2, 2) and up.stride == (2, 2), "only 2x2/s2 deconv is built"
-                w, scale = D.pack_dense(D.pack_deconv_weight(up.weight).to(device), scale.to(device), "deconv")
-                self._deblocks_p.append(dict(deconv=True, w=w, scale=scale, shift=shift.to(device)))
-            else:
-                w, scale = D.pack_dense(D.pack_conv_weight(up.weight).to(device), scale.to(device),
-                                        up.kernel_size[0], up.stride[0], 0)
-                self._deblocks_p.append(dict(deconv=False, w=w, scale=scale, shift=shift.to(device),
-                                             k=up.kernel_size[0], s=up.stride[0]))
-        packs[key] = (self._blocks_p, self._deblocks_p)
-        self._packed_dev = key
+        """Fold and pack every layer for the dense dispatch: once per arithmetic / structure (a sweep that re-runs a batch
+        under bf16x6, AL3D_MATH=auto, flips back without re-packing) and again after a parameter or buffer is written."""
+        def layer(conv, bn, *geom, deconv=False):
+            w, scale, shift = D.fold_conv_bn([(conv, bn)], deconv=deconv)
+            w, scale = D.pack_dense(w.to(device), scale.to(device), *geom)
+            return dict(w=w, scale=scale, shift=shift.to(device))
+
+        def build():
+            blocks, deblocks = [], []
+            for blk in self.blocks:
+                mods = list(blk.children())
+                convs = []
+                for j, m in enumerate(mods):
+                    if isinstance(m, nn.Conv2d):
+                        pad = 1 if (j > 0 and isinstance(mods[j - 1], nn.ZeroPad2d)) else m.padding[0]
+                        convs.append(dict(layer(m, mods[j + 1], m.kernel_size[0], m.stride[0], pad),
+                                          k=m.kernel_size[0], s=m.stride[0], p=pad))
+                blocks.append(convs)
+            for up, bn, _ in self.deblocks:
+                if isinstance(up, nn.ConvTranspose2d):
+                    assert up.kernel_size == (2, 2) and up.stride == (2, 2), "only 2x2/s2 deconv is built"
+                    deblocks.append(dict(layer(up, bn, "deconv", deconv=True), deconv=True))
+                else:
+                    deblocks.append(dict(layer(up, bn, up.kernel_size[0], up.stride[0], 0), deconv=False,
+                                         k=up.kernel_size[0], s=up.stride[0]))
+            return blocks, deblocks
+        layers = [m for seq in (*self.blocks, *self.deblocks) for m in seq]
+        self._blocks_p, self._deblocks_p = self.packs.get(device, layers, (D.MATH, D.DENSE), build)
 
     def _kind(self, w):
         return getattr(w, "kind", None)

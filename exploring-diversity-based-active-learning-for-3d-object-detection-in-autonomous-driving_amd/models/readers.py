@@ -5,6 +5,7 @@ from torch import nn
 from .. import detector_ops as D
 from .. import lib
 from ..selector_ops import _ptr, _stream
+from ..weight_cache import PackCache
 from .registry import READERS
 
 
@@ -84,17 +85,15 @@ class PillarFeatureNet(nn.Module):
         self.x_offset = self.vx / 2 + pc_range[0]
         self.y_offset = self.vy / 2 + pc_range[1]
         self.out_channels = self.pfn_layers[-1].units
+        self._packs = PackCache()
 
     def net(self, device):
         """The folded device weights (``detector_ops.PillarNet``), re-packed when a parameter or buffer changed."""
         if self.training:
             raise RuntimeError("al3d PillarFeatureNet implements the eval() sweep only")
-        key = (torch.device(device), tuple(t._version for t in self.state_dict().values()))
-        if getattr(self, "_net_key", None) != key:
-            self._net = D.PillarNet([(p.linear, p.norm) for p in self.pfn_layers], self.vx, self.vy, self.x_offset,
-                                    self.y_offset, self._with_distance, device)
-            self._net_key = key
-        return self._net
+        layers = [(p.linear, p.norm) for p in self.pfn_layers]
+        return self._packs.get(device, [m for pair in layers for m in pair], None, lambda: D.PillarNet(
+            layers, self.vx, self.vy, self.x_offset, self.y_offset, self._with_distance, device))      # fp32: one variant
 
     def forward(self, features, num_voxels, coors):
         if not features.is_cuda:

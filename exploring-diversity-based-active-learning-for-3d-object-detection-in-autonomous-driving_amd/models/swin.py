@@ -34,7 +34,7 @@ import torch
 from torch import nn
 
 from .. import token_ops as T
-from .bevfusion_camera import _versions
+from ..weight_cache import PackCache
 from .registry import BACKBONES
 
 
@@ -48,19 +48,6 @@ def _stream_pool(device, i):
     if key not in _STREAMS:
         _STREAMS[key] = torch.cuda.Stream(device=device)
     return _STREAMS[key]
-
-
-class _Packed:
-    """Per-module cache of kernel-format weights, rebuilt when the device or a parameter changes."""
-
-    def __init__(self):
-        self._key, self._val = None, None
-
-    def get(self, device, mods, build):
-        key = (device, _versions(*mods))
-        if self._key != key:
-            self._val, self._key = build(), key
-        return self._val
 
 
 class WindowMSA(nn.Module):
@@ -80,26 +67,26 @@ class WindowMSA(nn.Module):
         self.qkv = nn.Linear(embed_dims, embed_dims * 3, bias=qkv_bias)
         self.proj = nn.Linear(embed_dims, embed_dims)
         nn.init.trunc_normal_(self.relative_position_bias_table, std=0.02)
-        object.__setattr__(self, "_pk", _Packed())
+        object.__setattr__(self, "_pk", PackCache())
 
     def packed(self, device):
-        return self._pk.get(device, (self, self.qkv, self.proj), lambda: (
+        return self._pk.get(device, (self, self.qkv, self.proj), None, lambda: (
             T.PackedLinear(self.qkv.weight, self.qkv.bias), T.PackedLinear(self.proj.weight, self.proj.bias),
             self.relative_position_bias_table.detach().float().contiguous()))
 
     def qkv_bias_rows(self, device):
         """The qkv bias as the q / k / v row of a padded window position (zeros for a layer without bias)."""
         if getattr(self, "_pkb", None) is None:
-            object.__setattr__(self, "_pkb", _Packed())
-        return self._pkb.get(device, (self.qkv,), lambda: (
+            object.__setattr__(self, "_pkb", PackCache())
+        return self._pkb.get(device, (self.qkv,), None, lambda: (
             torch.zeros(3 * self.embed_dims, device=device) if self.qkv.bias is None
             else self.qkv.bias.detach().float().to(device).contiguous()))
 
     def packed_fused(self, device, norm):
         """LN1 + qkv + attention + proj in the fused kernel's format (``al3d_tok_attn_block_f16x3``; embed dim 96 / 192)."""
         if getattr(self, "_pkf", None) is None:
-            object.__setattr__(self, "_pkf", _Packed())
-        return self._pkf.get(device, (self, self.qkv, self.proj, norm), lambda: T.PackedAttnBlock(
+            object.__setattr__(self, "_pkf", PackCache())
+        return self._pkf.get(device, (self, self.qkv, self.proj, norm), None, lambda: T.PackedAttnBlock(
             norm.weight.to(device), norm.bias.to(device), norm.eps, self.qkv.weight.to(device), self.qkv.bias,
             self.proj.weight.to(device), self.proj.bias, self.relative_position_bias_table.to(device)))
 
@@ -136,19 +123,19 @@ class _FFN(nn.Module):
         super().__init__()
         self.layers = nn.Sequential(nn.Sequential(nn.Linear(embed_dims, feedforward_channels), nn.GELU(), nn.Identity()),
                                     nn.Linear(feedforward_channels, embed_dims), nn.Identity())
-        object.__setattr__(self, "_pk", _Packed())
+        object.__setattr__(self, "_pk", PackCache())
 
     def packed(self, device):
         fc1, fc2 = self.layers[0][0], self.layers[1]
-        return self._pk.get(device, (fc1, fc2), lambda: (T.PackedLinear(fc1.weight, fc1.bias),
+        return self._pk.get(device, (fc1, fc2), None, lambda: (T.PackedLinear(fc1.weight, fc1.bias),
                                                          T.PackedLinear(fc2.weight, fc2.bias)))
 
     def packed_fused(self, device, norm):
         """LN2 + fc1 + fc2 in the fused kernel's format (``al3d_tok_mlp_f16x3``; embed dims 96 / 192)."""
         fc1, fc2 = self.layers[0][0], self.layers[1]
         if getattr(self, "_pkf", None) is None:
-            object.__setattr__(self, "_pkf", _Packed())
-        return self._pkf.get(device, (fc1, fc2, norm), lambda: T.PackedMlp(
+            object.__setattr__(self, "_pkf", PackCache())
+        return self._pkf.get(device, (fc1, fc2, norm), None, lambda: T.PackedMlp(
             norm.weight.to(device), norm.bias.to(device), norm.eps, fc1.weight.to(device), fc1.bias, fc2.weight.to(device), fc2.bias))
 
 
@@ -205,7 +192,7 @@ class PatchMerging(nn.Module):
         self.in_channels = in_channels
         self.norm = nn.LayerNorm(4 * in_channels)
         self.reduction = nn.Linear(4 * in_channels, out_channels, bias=False)
-        object.__setattr__(self, "_pk", _Packed())
+        object.__setattr__(self, "_pk", PackCache())
 
     def packed(self, device):
         C = self.in_channels
@@ -216,7 +203,7 @@ class PatchMerging(nn.Module):
             g = self.norm.weight.detach().float().view(C, 4).t().reshape(-1).contiguous()
             b = self.norm.bias.detach().float().view(C, 4).t().reshape(-1).contiguous()
             return T.PackedLinear(w, None), g, b
-        return self._pk.get(device, (self.norm, self.reduction), build)
+        return self._pk.get(device, (self.norm, self.reduction), None, build)
 
     def forward(self, x, geom):
         rowmap, out_hw = geom.merge_map()
@@ -284,7 +271,7 @@ class _PatchEmbed(nn.Module):
         self.patch_size = patch_size
         self.projection = nn.Conv2d(in_channels, embed_dims, kernel_size=patch_size, stride=patch_size)
         self.norm = nn.LayerNorm(embed_dims) if patch_norm else None
-        object.__setattr__(self, "_pk", _Packed())
+        object.__setattr__(self, "_pk", PackCache())
 
     def forward(self, x):
         """x channels-last [B,H,W,3] -> token rows [B * H/4 * W/4, C], (H/4, W/4)."""
@@ -292,13 +279,13 @@ class _PatchEmbed(nn.Module):
         if T.pair_rows() and FUSED_PATCH_EMBED and pr.out_channels == 96 and x.shape[2] % 4 == 0:
             # projection + LayerNorm as one kernel: the image is read once, the tokens are written once
             if getattr(self, "_pkf", None) is None:
-                object.__setattr__(self, "_pkf", _Packed())
+                object.__setattr__(self, "_pkf", PackCache())
             n = self.norm
-            pk = self._pkf.get(x.device, (pr,) + ((n,) if n is not None else ()), lambda: T.PackedPatchEmbed(
+            pk = self._pkf.get(x.device, (pr, n), None, lambda: T.PackedPatchEmbed(
                 pr.weight.to(x.device), pr.bias, None if n is None else n.weight, None if n is None else n.bias,
                 1e-5 if n is None else n.eps))
             return T.patch_embed(x, pk)
-        w = self._pk.get(x.device, (pr,), lambda: T.PackedLinear(
+        w = self._pk.get(x.device, (pr,), None, lambda: T.PackedLinear(
             pr.weight.detach().permute(0, 2, 3, 1).reshape(pr.out_channels, -1), pr.bias))      # [C, (ky, kx, c)]
         rows, hw = T.patch_rows(x, pair=T.pair_rows())
         y = T.linear(rows, w, a_pair=T.pair_rows())

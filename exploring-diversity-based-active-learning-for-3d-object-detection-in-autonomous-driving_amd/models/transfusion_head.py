@@ -23,9 +23,9 @@ from torch import nn
 from .. import lib
 from .. import token_ops as T
 from ..selector_ops import _dev, _ptr, _stream
-from .bevfusion_camera import _ConvAffine
+from ..weight_cache import PackCache
+from .conv_layers import FoldedConv
 from .registry import HEADS
-from .swin import _Packed
 
 
 def _bn_fold(bn):
@@ -45,7 +45,7 @@ class PositionEmbeddingLearned(nn.Module):
         self.position_embedding_head = nn.Sequential(
             nn.Conv1d(input_channel, num_pos_feats, kernel_size=1), nn.BatchNorm1d(num_pos_feats), nn.ReLU(inplace=True),
             nn.Conv1d(num_pos_feats, num_pos_feats, kernel_size=1))
-        object.__setattr__(self, "_pk", _Packed())
+        object.__setattr__(self, "_pk", PackCache())
 
     def packed(self, device):
         c1, bn, _, c2 = self.position_embedding_head
@@ -54,7 +54,7 @@ class PositionEmbeddingLearned(nn.Module):
             s, t = _bn_fold(bn)
             return (T.PackedLinear(c1.weight, t + c1.bias.detach().float() * s, scale=s, pad_k=16),
                     T.PackedLinear(c2.weight, c2.bias))
-        return self._pk.get(device, (c1, bn, c2), build)
+        return self._pk.get(device, (c1, bn, c2), None, build)
 
     def hidden(self, pos_rows):
         """[M, 2] -> the ReLU'd hidden rows [M, F] (input of the second layer)."""
@@ -89,8 +89,8 @@ class TransformerDecoderLayer(nn.Module):
         self.norm1, self.norm2, self.norm3 = nn.LayerNorm(d_model), nn.LayerNorm(d_model), nn.LayerNorm(d_model)
         self.activation = activation
         self.self_posembed, self.cross_posembed = self_posembed, cross_posembed
-        object.__setattr__(self, "_pk", _Packed())
-        object.__setattr__(self, "_kpe", {})
+        object.__setattr__(self, "_pk", PackCache())
+        object.__setattr__(self, "_kpe", PackCache())
 
     def packed(self, device):
         sa, ca = self.self_attn, self.multihead_attn
@@ -103,7 +103,7 @@ class TransformerDecoderLayer(nn.Module):
                 ca_kv=T.PackedLinear(ca.in_proj_weight[C:], None),
                 ca_out=T.PackedLinear(ca.out_proj.weight, ca.out_proj.bias),
                 l1=T.PackedLinear(self.linear1.weight, self.linear1.bias), l2=T.PackedLinear(self.linear2.weight, self.linear2.bias))
-        return self._pk.get(device, (sa, sa.out_proj, ca, ca.out_proj, self.linear1, self.linear2), build)
+        return self._pk.get(device, (sa, sa.out_proj, ca, ca.out_proj, self.linear1, self.linear2), None, build)
 
     def key_pos_projection(self, key_pos_rows):
         """(cross_posembed(key_pos)) W_kv^T + b_kv, [HW, 2C]: depends on the parameters and the fixed BEV grid only, so it is
@@ -117,9 +117,7 @@ class TransformerDecoderLayer(nn.Module):
             return T.linear(kpe, T.PackedLinear(ca.in_proj_weight[C:], ca.in_proj_bias[C:]))
         # an ACTIVATION cache: one per arithmetic (a sweep that re-runs a batch under bf16x6 must not read f16x3 rows, nor
         # rebuild them when it flips back)
-        arith = T.arithmetic()
-        kpe = self._kpe.setdefault(arith, _Packed())
-        return kpe.get((key_pos_rows.device, key_pos_rows.data_ptr(), key_pos_rows.shape[0]), mods, build)
+        return self._kpe.get(key_pos_rows.device, (*mods, key_pos_rows), (T.arithmetic(), key_pos_rows.shape[0]), build)
 
     def forward(self, query, key, query_pos, key_pos, B):
         """query rows [B*Pq, C], key rows [B*Pk, C], query_pos rows [B*Pq, 2], key_pos rows [Pk, 2] (shared by the samples)
@@ -173,7 +171,7 @@ class FFN(nn.Module):
             layers.append(nn.Conv1d(head_conv, classes, 1, bias=True))
             setattr(self, head, nn.Sequential(*layers))
         getattr(self, "heatmap")[-1].bias.data.fill_(init_bias)
-        object.__setattr__(self, "_pk", _Packed())
+        object.__setattr__(self, "_pk", PackCache())
 
     def packed(self, device):
         names = list(self.heads)
@@ -195,7 +193,7 @@ class FFN(nn.Module):
                 spans[h] = (o, o + c)
                 o += c
             return (T.PackedLinear(w1, t1, scale=s1), T.PackedLinear(w2, torch.cat(b2), pad_n=(total + 3) // 4 * 4), spans)
-        return self._pk.get(device, mods, build)
+        return self._pk.get(device, mods, None, build)
 
     def forward(self, x, B):
         """x rows [B*P, C] -> dict of [B, classes, P] (the reference's layout)."""
@@ -281,9 +279,9 @@ class TransFusionHead(nn.Module):
         x_size = self.test_cfg["grid_size"][0] // self.test_cfg["out_size_factor"]
         y_size = self.test_cfg["grid_size"][1] // self.test_cfg["out_size_factor"]
         self.bev_pos = self.create_2D_grid(x_size, y_size)
-        object.__setattr__(self, "_convs", [_ConvAffine(self.shared_conv, None, False),
-                                            _ConvAffine(self.heatmap_head[0].conv, self.heatmap_head[0].bn, True),
-                                            _ConvAffine(self.heatmap_head[1], None, False)])
+        self._convs = [FoldedConv([(self.shared_conv, None)], relu=False),
+                       FoldedConv([(self.heatmap_head[0].conv, self.heatmap_head[0].bn)]),
+                       FoldedConv([(self.heatmap_head[1], None)], relu=False)]
         self.query_labels = None
 
     def _bev_pos_on(self, device):

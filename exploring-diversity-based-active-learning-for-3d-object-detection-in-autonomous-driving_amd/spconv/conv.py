@@ -20,6 +20,7 @@ from torch.nn import init
 from .. import detector_ops as D
 from .. import lib
 from ..selector_ops import _dev, _ptr, _stream
+from ..weight_cache import PackCache
 from . import ops
 from .modules import SparseModule
 from .structure import Sites, SparseConvTensor
@@ -101,6 +102,7 @@ class SparseConvolution(SparseModule):
             self.bias = nn.Parameter(torch.empty(out_channels))
         else:
             self.register_parameter("bias", None)
+        self._packs = PackCache()
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -186,31 +188,19 @@ class SparseConvolution(SparseModule):
     # ------------------------------------------------------------------ weights
     def _packed(self, dev, name, width, bn):
         """(weights in structure ``name``'s format, scale, shift) for this device, arithmetic and BatchNorm partner; packed
-        once (the way ``RPN._prepare`` keeps its packs) and again only when a parameter was written since."""
-        params = [self.weight, self.bias] + ([] if bn is None else [bn.weight, bn.bias, bn.running_mean, bn.running_var])
-        key = (dev, D.MATH, name, width, None if bn is None else id(bn))
-        stamp = tuple(None if p is None else (p.data_ptr(), p._version) for p in params)
-        packs = self.__dict__.setdefault("_packs", {})
-        held = packs.get(key)
-        if held is not None and held[0] == stamp:
-            return held[1]
-        for old in [k_ for k_, (st, _) in packs.items() if st[:2] != stamp[:2]]:     # packs of a weight since written or moved
-            del packs[old]
-        scale = shift = None
-        if bn is not None:
-            scale, shift = D.fold_bn(bn)
-            if self.bias is not None:                          # (x + b) * s + t
-                shift = shift + self.bias.detach().float().to(scale.device) * scale
-            scale, shift = scale.to(dev), shift.to(dev)
-        elif self.bias is not None:
-            shift = self.bias.detach().float().to(dev).contiguous()
-        w = self.weight.detach().reshape(-1, self.in_channels, self.out_channels).float().to(dev)
-        if name == "any":
-            pack = (w.contiguous(), scale, shift)
-        else:
-            pack = (*D.sparse_pack(name, w, scale, width), shift)
-        packs[key] = (stamp, pack)
-        return pack
+        once per variant and again only when a parameter or buffer of the layer or the partner was written since."""
+        def build():
+            scale = shift = None
+            if bn is not None:
+                scale, shift = D.fold_bn(bn, self.bias)
+                scale, shift = scale.to(dev), shift.to(dev)
+            elif self.bias is not None:
+                shift = self.bias.detach().float().to(dev).contiguous()
+            w = self.weight.detach().reshape(-1, self.in_channels, self.out_channels).float().to(dev)
+            if name == "any":
+                return w.contiguous(), scale, shift
+            return (*D.sparse_pack(name, w, scale, width), shift)
+        return self._packs.get(dev, (self, bn), (D.MATH, name, width, None if bn is None else id(bn)), build)
 
     # ------------------------------------------------------------------ forward
     def forward(self, input):

@@ -321,7 +321,7 @@ def test_encoder_raster_path_equals_appearance_order_path():
             outs[tag] = (dense.clone(), [(m.features.clone(), m.indices.clone(), list(m.spatial_shape)) for m in middle])
     finally:
         D.L0, D.R16_COUTS, D.L0_ROWS = saved
-        enc._packed_dev = None
+        enc.packs.clear()
     ref_dense, ref_mid = outs["off"]
     assert torch.isfinite(ref_dense).all() and float(ref_dense.abs().max()) > 0
     for tag in ("raster16", "raster16+32"):

@@ -31,7 +31,7 @@ if os.environ.get("BENCH_L0_MODES"):
 results, ref = {}, None
 for tag, l0, couts, rows in modes:
     D.L0, D.R16_COUTS, D.L0_ROWS = l0, couts, rows
-    enc._packed_dev = None
+    enc.packs.clear()
     times, names = [], []
     def timed(step, b, feats, residual, out, io=0):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
