@@ -76,8 +76,12 @@ class DeviceSweepLoader:
     keys the detector reads (voxelnet.py:84-97, mg_head.py:710-724): ``voxel_features``,
     ``coordinates``, ``num_points``, ``num_voxels``, ``shape``, ``anchors``, ``metadata``."""
 
-    def __init__(self, pool, voxel_cfg, anchors, batch_size=4, indices=None, device="cuda", with_points=False, view=None):
+    def __init__(self, pool, voxel_cfg, anchors, batch_size=4, indices=None, device="cuda", with_points=False, view=None,
+                 keep_points=False):
         self.with_points = bool(with_points)   # also yield the padded point slots (``voxels``) for PillarFeatureNet
+        # also yield the batch's merged points and their frame offsets (``points``, ``point_offsets``, as FileSweepLoader
+        # does): what models.WithEstimator reads
+        self.keep_points = bool(keep_points)
         # (flip_x, flip_y, rot, scale): every batch is voxelized from an augmented COPY of its points
         # (selector_ops.points_view_, CALD's second sweep); None launches nothing
         self.view = view
@@ -121,6 +125,8 @@ class DeviceSweepLoader:
             }
             if self.with_points:
                 ex["voxels"] = v["voxels"]
+            if self.keep_points:
+                ex["points"], ex["point_offsets"] = pts, off
             yield ex
 
 

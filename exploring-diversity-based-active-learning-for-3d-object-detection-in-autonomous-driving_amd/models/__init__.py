@@ -1,6 +1,6 @@
 from .registry import (BACKBONES, DETECTORS, ESTIMATORS, HEADS, LOSSES, NECKS, READERS,
                        ROI_EXTRACTORS, SHARED_HEADS)
-from .builder import build_backbone, build_detector, build_head, build_neck, build_reader
+from .builder import build_backbone, build_detector, build_estimator, build_head, build_neck, build_reader
 from .readers import PillarFeatureNet, VoxelFeatureExtractorV3
 from .backbones import FPNSpMiddleResNetFHD, PointPillarsScatter, SparseTensor
 from .necks import RPN
@@ -15,6 +15,7 @@ from .bevfusion_model import BEVFusion, BEVFusionCameraLidar
 from .bevfusion_camera_only import BEVFusionCameraOnly, GeneralizedResNet, LSSFPN, LSSTransform
 from .bev_seg_head import BEVGridTransform, BEVSegmentationHead
 from .voxel_layers import DynamicScatter, Voxelization, dynamic_scatter
+from .estimator import Estimator, WithEstimator
 
-__all__ = ["READERS", "BACKBONES", "NECKS", "HEADS", "DETECTORS", "build_detector",
+__all__ = ["READERS", "BACKBONES", "NECKS", "HEADS", "DETECTORS", "ESTIMATORS", "build_detector", "build_estimator",
            "build_reader", "build_backbone", "build_neck", "build_head", "build_box_coder"]

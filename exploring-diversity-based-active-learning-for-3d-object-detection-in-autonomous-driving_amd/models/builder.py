@@ -2,7 +2,7 @@
 from torch import nn
 
 from ..utils import build_from_cfg
-from .registry import BACKBONES, DETECTORS, HEADS, NECKS, READERS
+from .registry import BACKBONES, DETECTORS, ESTIMATORS, HEADS, NECKS, READERS
 
 
 def build(cfg, registry, default_args=None):
@@ -29,3 +29,7 @@ def build_head(cfg):
 
 def build_detector(cfg, train_cfg=None, test_cfg=None):
     return build(cfg, DETECTORS, dict(train_cfg=train_cfg, test_cfg=test_cfg))
+
+
+def build_estimator(cfg):
+    return build(cfg, ESTIMATORS)

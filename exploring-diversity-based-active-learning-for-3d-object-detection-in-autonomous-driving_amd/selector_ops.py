@@ -226,6 +226,65 @@ def match_boxes(boxes, scores, labels, counts, ref_boxes, ref_labels, ref_scores
     return out
 
 
+EST_MAX_BOXES, EST_MAX_CLASSES, EST_BAD_OFFSETS, EST_BAD_LABEL = 1024, 32, 1, 2      # AL3D_EST_* of include/al3d.h
+
+
+def estimator_status_check(status):
+    """Raise for the AL3D_EST_* bits of a status word that is on the host already."""
+    st = int(status)
+    if st & EST_BAD_OFFSETS:
+        raise lib.Al3dError("estimate_boxes: point_offsets is not ascending inside [0, number of points]")
+    if st & EST_BAD_LABEL:
+        raise lib.Al3dError("estimate_boxes: a detection's label lies outside [0, num_classes)")
+    if st:
+        raise lib.Al3dError(f"estimate_boxes: status {st}")
+
+
+def estimate_boxes(boxes, labels, counts, points, point_offsets, weights, num_classes, rot_col=6, out=None, check=True):
+    """The box-wise IoU estimator on the raw NMS buffers (``al3d_estimator_f32`` in include/al3d.h; reference
+    estimator.py:92-105,155-274).
+
+    ``boxes [B,nt,post,D]`` f32, ``labels [B,nt,post]`` i32, ``counts [B,nt]`` i32; ``points [P,F]`` f32 with the frames
+    back to back and ``point_offsets [B+1]`` i64; ``weights``: the folded, packed network (``models.estimator``).  Returns
+    ``dict(boxes, scores, labels, counts)`` -- the boxes that hold a point, compacted per (frame, task), scored with the
+    predicted IoU -- plus ``npts [B,nt,post]`` i32 and ``pooled [B,nt,post,128]`` f32 (views of the workspace, per INPUT
+    slot) and ``status`` (device i32).  ``out``: buffers to write instead of fresh zeroed ones.  ``check=True`` reads the
+    status word back (one small D2H) and raises ``Al3dError``; with ``check=False`` nothing synchronises and the caller
+    hands ``status`` to ``estimator_status_check`` when it next reads from the device."""
+    boxes = _dev(boxes, torch.float32, "boxes")
+    labels = _dev(labels, torch.int32, "labels")
+    counts = _dev(counts, torch.int32, "counts")
+    points = _dev(points, torch.float32, "points")
+    point_offsets = _dev(point_offsets, torch.int64, "point_offsets")
+    weights = _dev(weights, torch.float32, "weights")
+    if boxes.dim() != 4 or labels.shape != boxes.shape[:3] or counts.shape != boxes.shape[:2]:
+        raise lib.Al3dError("estimate_boxes: boxes [B,nt,post,D], labels [B,nt,post], counts [B,nt] expected")
+    B, nt, post, bd = boxes.shape
+    if points.dim() != 2 or point_offsets.shape != (B + 1,) or weights.dim() != 1:
+        raise lib.Al3dError("estimate_boxes: points [P,F], point_offsets [B+1], weights [n] expected")
+    dev = boxes.device
+    if out is None:
+        out = dict(boxes=torch.zeros_like(boxes), scores=torch.zeros((B, nt, post), dtype=torch.float32, device=dev),
+                   labels=torch.zeros_like(labels), counts=torch.zeros_like(counts))
+    ws_bytes = lib.load().al3d_estimator_workspace_bytes(B, nt, post)
+    ws = torch.empty((max(ws_bytes, 512),), dtype=torch.uint8, device=dev)
+    status = torch.empty((1,), dtype=torch.int32, device=dev)
+    lib.call("al3d_estimator_f32", _ptr(boxes), _ptr(labels), _ptr(counts), B, nt, post, bd, int(rot_col),
+             _ptr(points) if points.shape[0] else None, _ptr(point_offsets), points.shape[0], points.shape[1],
+             _ptr(weights), weights.numel(), int(num_classes), _ptr(out["boxes"]), _ptr(out["scores"]), _ptr(out["labels"]),
+             _ptr(out["counts"]), _ptr(ws), _ptr(status), _stream())
+    slots = B * nt * post
+    a0 = (-ws.data_ptr()) % 256                      # the entry aligns the workspace to 256 bytes itself
+    a1 = a0 + (slots * 4 + 255) // 256 * 256
+    res = dict(out)
+    res["npts"] = ws[a0:a0 + slots * 4].view(torch.int32).view(B, nt, post)
+    res["pooled"] = ws[a1:a1 + slots * 512].view(torch.float32).view(B, nt, post, 128)
+    res["status"] = status
+    if check:
+        estimator_status_check(status.item())
+    return res
+
+
 def points_view_(points, view):
     """In place on the xyz columns of ``points [P,F]``: ``view = (flip_x, flip_y, rot, scale)`` -- y negated if ``flip_x``,
     x negated if ``flip_y`` (det3d's naming), then the rotation about z, then the scaling (preprocess.py:787-854)."""

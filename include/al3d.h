@@ -1066,6 +1066,47 @@ int al3d_match_boxes_f32(const float* boxes, const float* scores, const int* lab
  * (preprocess.py:787-793). */
 int al3d_points_view_f32(float* points, int64_t P, int F, int flip_x, int flip_y, float rot, float scale, void* stream);
 
+/* ---------------------------------------------------------------- box-wise IoU estimator
+ * Replaces det3d/models/detectors/estimator.py:155-274 (extract_points_feature_gpu: the [points, boxes] membership mask
+ * built 20 boxes at a time :203-213 from box_torch_ops.py:388-407 and geometry.py:5-31, the per-box Python loop with the
+ * height filter :226, the local frame :240-242, the centerness :243-250 and the one-hot :256-257), :92-105 (estimate:
+ * iou_estimator, scatter_max, iou_head, sigmoid) and :71-75 (the predicted IoU becomes the score), for inference.
+ *
+ * Predictions in the layout of al3d_head_decode_nms / al3d_center_decode_nms_f32: boxes [B,nt,post,box_dim] f32, labels
+ * [B,nt,post] i32 (merged class id in [0, num_classes)), counts [B,nt] i32 (clamped to [0, post]).  Of a box columns 0..5
+ * (centre, w, l, h) and rot_col are read; the reference takes box[:7][-1], i.e. rot_col = 6.  Points: points [P,F] f32
+ * (F >= 3, xyz first), frames back to back, point_off [B+1] i64 ascending inside [0, P].
+ *
+ * Per frame and valid box: a point belongs to the box iff all four cross products against the edges of the footprint
+ * center_to_corner_box2d(xy, 2 (w, l), r) are > 0 (rotation_2d: clockwise for a positive angle) and |pz - z| <= h / 2.  Its
+ * 9 + num_classes features are the offset from the centre in the frame x' = dx cos r + dy sin r, y' = -dx sin r + dy cos r,
+ * z' = dz (batch_z_rotation_matrix_torch: the opposite sense; both are kept as the reference has them), w/2 +- x',
+ * l/2 +- y', h/2 +- z', and the one-hot of the label.  wts: the network with its BatchNorms folded in, packed as
+ * W1 [32][9+nc], b1 [32], W2 [64][32], b2, W3 [128][64], b3, H1 [128][256] (input-major), c1 [256], H2 [256][64]
+ * (input-major), c2 [64], H3 [64], c3 [1]; al3d_estimator_weight_elems(nc) floats (-1 for a bad nc).
+ *
+ * Outputs, in the same layout: the boxes of each (frame, task) that hold at least one point, order kept, compacted to the
+ * front of out_boxes / out_labels, out_scores = the predicted IoU, out_counts [B,nt] their number; slots behind the count
+ * are not written.  A frame in which no box survives gets zero counts (the reference's torch.stack([]) raises).
+ * workspace: al3d_estimator_workspace_bytes(B, nt, post) bytes (-1 for sizes the entry refuses); after the call its
+ * 256-byte-aligned start holds npts [B,nt,post] i32, the points of every slot, and from the next multiple of 256 bytes
+ * pooled [B,nt,post,128] f32, the max-pooled rows (zero where no point).  Every result is a max or an integer sum over the
+ * points, so it does not depend on scheduling: two calls give the same bits.
+ *
+ * Refused before any launch (AL3D_EINVAL): nt * post > AL3D_EST_MAX_BOXES, num_classes > AL3D_EST_MAX_CLASSES, a wts_elems
+ * that does not match.  *status (device int): an OR of the AL3D_EST_* bits found on the device; when it is not 0 neither
+ * the outputs nor npts / pooled have been written.  No host synchronisation inside. */
+#define AL3D_EST_MAX_BOXES 1024       /* nt * post: the slots of one frame */
+#define AL3D_EST_MAX_CLASSES 32
+#define AL3D_EST_BAD_OFFSETS 1        /* point_off is not ascending inside [0, P] */
+#define AL3D_EST_BAD_LABEL 2          /* a valid slot's label lies outside [0, num_classes) (F.one_hot raises) */
+int64_t al3d_estimator_workspace_bytes(int B, int nt, int post);
+int64_t al3d_estimator_weight_elems(int num_classes);
+int al3d_estimator_f32(const float* boxes, const int* labels, const int* counts, int B, int nt, int post, int box_dim,
+                       int rot_col, const float* points, const int64_t* point_off, int64_t P, int F, const float* wts,
+                       int64_t wts_elems, int num_classes, float* out_boxes, float* out_scores, int* out_labels,
+                       int* out_counts, void* workspace, int* status, void* stream);
+
 /* ---------------------------------------------------------------- runtime
  * A HIP stream restricted to n_cus compute units starting at first_cu (hipExtStreamCreateWithCUMask); the
  * reference has no analogue (its loader workers are host processes, det3d/datasets/loader/build_loader.py:23-59):

@@ -39,6 +39,9 @@ def parse_args():
     p.add_argument("--synthetic-scenes", type=int, default=0,
                    help="generate a synthetic pool of this many scenes (writes infos/log files)")
     p.add_argument("--batch", type=int, default=8)
+    p.add_argument("--estimator-checkpoint", default=None,
+                   help="weights of the config's `estimator` section (default: the config's estimator_load_from); with "
+                        "both, the detections are rescored by the predicted IoU before the selector reads them")
     args = p.parse_args()
     os.environ.setdefault("LOCAL_RANK", str(args.local_rank))
     return args
@@ -115,6 +118,17 @@ def main():
         else:
             synthetic.seeded_init_(model, seed=0)
         model = model.to(dev).eval()
+        # the box-wise IoU estimator (reference active_trainer.py:441-443): only with an `estimator` section AND weights
+        est_ckpt = args.estimator_checkpoint or cfg.get("estimator_load_from")
+        estimator = None
+        if cfg.get("estimator") is not None and est_ckpt:
+            from al3d.models import WithEstimator, build_estimator
+            estimator = build_estimator(cfg.estimator)
+            sd = torch.load(est_ckpt, map_location="cpu", weights_only=True)
+            sd = sd.get("state_dict", sd)
+            estimator.load_state_dict({k[7:] if k.startswith("module.") else k: v for k, v in sd.items()}, strict=True)
+            model = WithEstimator(model, estimator.to(dev).eval())
+            logger.info("estimator loaded from %s: detections are rescored by the predicted IoU", est_ckpt)
         infos = fileio.load(sel_cfg.infos_origin)
         n = len(infos)
         per = (n + world - 1) // world
@@ -148,7 +162,7 @@ def main():
         elif args.synthetic_scenes:
             pool = PoolFrames.from_synthetic(len(mine), dev, seed=1000 + rank)
             loader = DeviceSweepLoader(pool, cfg.voxel_generator, anchors, batch_size=args.batch, device=dev,
-                                       with_points=with_points)
+                                       with_points=with_points, keep_points=estimator is not None)
         else:
             # real files: streamed by the native reader pool one batch ahead of the detector (the reference's
             # 8 DataLoader workers, build_loader.py:23-59), never staged as a whole pool
