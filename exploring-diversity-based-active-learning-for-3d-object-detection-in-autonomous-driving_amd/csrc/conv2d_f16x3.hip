@@ -1,31 +1,5 @@
-// Dense 2-D convolution in fp32-class arithmetic with THREE f16 matrix-core products per MAC.
-//
-// f16 carries 11 significand bits, so two pieces hold 22-23 of an fp32 value's 24 (bf16 needs
-// three pieces and six products for the same, conv2d_bf16x6.hip).  What f16 lacks is exponent
-// range; the split is arranged to spend as little of it as possible:
-//
-//   activation x (any |x| < 65504):  xh = f16(x)                A0
-//                                    xl = f16((x - xh) * 2^11)  A1   (residual lifted by 2^11)
-//   weight w, pre-scaled once per layer by a power of two so that max|ws| <= 2^14:
-//                                    wh = f16(ws)               B0
-//                                    wl = f16(ws - wh)          B1
-//                                    wd = wh * 2^-11            B2   (derived in registers from the B0
-//                                         fragment with v_pk_mul_f16; exact: wh >= 2^-3 for every
-//                                         weight above 2^-17 max|w|, f16 subnormal rounding below)
-//   x*ws = A0*B0 + A0*B1 + A1*B2 + (dropped xl*wl term <= 2^-24 |x ws|)
-//
-// All three products go into ONE fp32 accumulator (v_mfma_f32_32x32x16_f16, products exact);
-// the weight scale 2^-s is folded into the per-channel BN scale on the host (exact).
-// Per-product relative error <= ~3 * 2^-24, i.e. the size of one fp32 rounding, for |x| >= 2^-14.
-// Below that xh is an f16 subnormal (v_cvt_f16_f32 and the gfx950 matrix core both keep them --
-// measured, tools/probe_f16x3.py) with absolute error 2^-25, of which the lifted residual recovers
-// eleven more bits: absolute representation error <= 2^-36 everywhere.  Measured against fp64
-// (max error as a fraction of sum|a*b|, lognormal activations of typical magnitude m):
-//      m = 1 .. 1e-5: 2.6e-7 .. 3.2e-7  (fp32-input MFMA kernel: 4.2e-7 .. 5.3e-7, bf16x6: 3.1e-7 .. 4.4e-7)
-//      m = 1e-6: 1.4e-6 (and short K=32 sums already at m = 1e-5) -- the envelope: tensors whose
-// typical magnitude is within [1e-4, 6e4].
-// An activation >= 65504 turns into inf/NaN in the output, never a plausible number -- the sweep
-// checks its embeddings for finiteness and names AL3D_MATH=bf16x6 (full fp32 range) as the way out.
+// Dense 2-D convolution in fp32-class arithmetic with THREE f16 matrix-core products per MAC: the f16x3 arithmetic of
+// al3d_f16x3.h (split, ranges, error bounds, measured envelope, product order).
 //
 // Same role, layouts and tiling as conv2d_bf16x6.hip: NHWC f32 activations in HBM, split while
 // they are staged; weights pre-split into [2][Cout][taps][Cin] f16.  Half the MFMAs, 4 instead
@@ -47,10 +21,6 @@
 #define F3_LDB 48          // bytes per LDS row: 16 f16 (32 B) + 16 B pad (conflict-free b128 reads)
 #define F3_TH 8
 #define F3_TW 16
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 // This file's A/B knobs, read from the environment once per process (the same bits under every setting)
 struct F3Knobs {
@@ -105,56 +75,13 @@ struct ConvF3Params {
     int rows_pitch = 0;
 };
 
-// 1-D grid -> (pixel tile, column block).  Blocks with equal blockIdx % 8 share an XCD and its L2,
-// so the column blocks of one pixel tile get ids that differ by 8: they run on the same XCD at
-// about the same time and the second one finds the tile's activations in L2 instead of HBM (the
-// 1x1 layers are bandwidth-bound: 42 flop per byte).  Grid = ceil(ntiles / 8) * 8 * nblocks.
-// xmap = 1 ("band", round 5): each XCD (blockIdx % 8) walks ONE contiguous band of pixel tiles in raster order, the column
-// blocks of a tile back to back -- so that the tiles resident on an XCD at any moment are spatial neighbours (the 3x3 kernels'
-// 6 x 34 halos overlap: rows shared with the tile above / below are L2 hits instead of second HBM reads) and the second column
-// block still finds its activations in L2.  xmap = 0 ("rr"): tiles dealt round-robin over the XCDs (rounds 1-4).
-__device__ __forceinline__ bool f3_tile_of_block(const ConvF3Params& p, int& tile, int& nblk)
-{
-    if (p.xmap) {
-        const int k = blockIdx.x & 7, t = blockIdx.x >> 3;
-        const int j = t / p.nblocks;
-        nblk = t - j * p.nblocks;
-        const int q8 = p.ntiles >> 3, r8 = p.ntiles & 7;
-        tile = k * q8 + (k < r8 ? k : r8) + j;
-        return j < q8 + (k < r8 ? 1 : 0);
-    }
-    const int id = blockIdx.x, span = 8 * p.nblocks;
-    const int grp = id / span, rem = id - grp * span;
-    nblk = rem >> 3;
-    tile = grp * 8 + (rem & 7);
-    return tile < p.ntiles;
-}
+// grid of f3_tile_of_block (al3d_f16x3.h); every kernel here passes p.xmap as its band flag
 static inline unsigned f3_grid(const ConvF3Params& p)
 {
     return (unsigned)(al3d_cdiv(p.ntiles, 8) * 8 * p.nblocks);
 }
 
-__device__ __forceinline__ void split_act(float x, _Float16& h, _Float16& l)
-{
-    h = (_Float16)x;                                  // subnormal below 2^-14 (kept: see the header)
-    l = (_Float16)__builtin_fmaf((float)h, -2048.0f, x * 2048.0f);   // == (x - h) * 2^11 exactly; one v_fma_mix
-}
-
-__device__ __forceinline__ void split_act4(const float4& v, f16x4& h, f16x4& l)
-{
-    const float e[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { _Float16 a, b; split_act(e[i], a, b); h[i] = a; l[i] = b; }
-}
-
-// wd fragment = wh fragment * 2^-11 (packed f16 multiplies; the compiler emits v_pk_mul_f16)
-__device__ __forceinline__ f16x8 lift_down(const f16x8& wh)
-{
-    return wh * (_Float16)0.00048828125f;
-}
-
 #define F3_IC(v) std::integral_constant<int, v>{}
-#define F3_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0)
 
 static int convf3_check(const ConvF3Params& p, const char* name)
 {
@@ -177,7 +104,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_f16x3_kernel(ConvF3Params p)
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave & 1, wn = wave >> 1;
     int tile, nblk;
-    if (!f3_tile_of_block(p, tile, nblk)) return;     // padding block of the last group (uniform)
+    if (!f3_tile_of_block(p.ntiles, p.nblocks, p.xmap, tile, nblk)) return;     // padding block of the last group (uniform)
     const int tx_ = tile % p.tiles_x; tile /= p.tiles_x;
     const int ty_ = tile % p.tiles_y; tile /= p.tiles_y;
     const int b = tile;
@@ -225,7 +152,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_f16x3_kernel(ConvF3Params p)
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             f16x4 h, l;
-            split_act4(ra[i], h, l);
+            f3_split4(ra[i], h, l);
             const int off = (ar + 64 * i) * F3_LDB + 8 * aq;
             *reinterpret_cast<f16x4*>(&As[buf][0][off]) = h;
             *reinterpret_cast<f16x4*>(&As[buf][1][off]) = l;
@@ -258,16 +185,12 @@ __global__ __launch_bounds__(256, 2) void conv2d_f16x3_kernel(ConvF3Params p)
                 a[pl][t] = *reinterpret_cast<const f16x8*>(&As[buf][pl][(wm * 64 + t * 32 + fr) * F3_LDB + 16 * fh]);
                 bb[pl][t] = *reinterpret_cast<const f16x8*>(&Bs[buf][pl][(wn * 64 + t * 32 + fr) * F3_LDB + 16 * fh]);
             }
-            bb[2][t] = lift_down(bb[0][t]);
+            bb[2][t] = f3_lift_down(bb[0][t]);
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                acc[i][j] = F3_MFMA(a[1][i], bb[2][j], acc[i][j]);      // xl * wh   (smallest first)
-                acc[i][j] = F3_MFMA(a[0][i], bb[1][j], acc[i][j]);      // xh * wl
-                acc[i][j] = F3_MFMA(a[0][i], bb[0][j], acc[i][j]);      // xh * wh
-            }
+            for (int j = 0; j < 2; ++j) f3_mac3(a[0][i], a[1][i], bb[0][j], bb[1][j], bb[2][j], acc[i][j]);
         if (step + 1 < nsteps) store_step(buf ^ 1);
         __syncthreads();
     }
@@ -283,7 +206,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_f16x3_kernel(ConvF3Params p)
         for (int i = 0; i < 2; ++i) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+                const int m = wm * 64 + i * 32 + f3_crow(r, fh);
                 const int y = ty_ * F3_TH + m / F3_TW, x = tx_ * F3_TW + m % F3_TW;
                 if (y >= MH || x >= MW) continue;
                 float v = acc[i][j][r] * sc + sh;
@@ -361,7 +284,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_halo_kernel(ConvF3Params
     const int wm = wave & 1, wn = wave >> 1;
     const int fr = lane & 31, fh = lane >> 5;
     int tile, nblk;
-    if (!f3_tile_of_block(p, tile, nblk)) return;     // padding block of the last group (uniform)
+    if (!f3_tile_of_block(p.ntiles, p.nblocks, p.xmap, tile, nblk)) return;     // padding block of the last group (uniform)
     const int tx_ = tile % p.tiles_x; tile /= p.tiles_x;
     const int ty_ = tile % p.tiles_y; tile /= p.tiles_y;
     const int b = tile;
@@ -392,7 +315,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_halo_kernel(ConvF3Params
             const int hp = piece >> 2, q = piece & 3;
             if (hp >= G3_HP) continue;
             f16x4 h, l;
-            split_act4(rh[k], h, l);
+            f3_split4(rh[k], h, l);
             const int off = hp * F3_LDB + 8 * q;
             *reinterpret_cast<f16x4*>(&Ah[buf][0][off]) = h;
             *reinterpret_cast<f16x4*>(&Ah[buf][1][off]) = l;
@@ -457,17 +380,18 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_halo_kernel(ConvF3Params
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int j = 0; j < 2; ++j)
-                acc[i][j] = F3_MFMA(fa[set][pa][i], fb[set][pb][j], acc[i][j]);
+                acc[i][j] = f3_mfma32(fa[set][pa][i], fb[set][pb][j], acc[i][j]);
     };
+    // (product-major over the four tiles, interleaved with the step's loads and stores: f3_mac3's order, spelled out)
     auto mfma_lifted = [&](int set) {                 // xl' * (wh * 2^-11)
         f16x8 wd[2];
 #pragma unroll
-        for (int j = 0; j < 2; ++j) wd[j] = lift_down(fb[set][0][j]);
+        for (int j = 0; j < 2; ++j) wd[j] = f3_lift_down(fb[set][0][j]);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int j = 0; j < 2; ++j)
-                acc[i][j] = F3_MFMA(fa[set][1][i], wd[j], acc[i][j]);
+                acc[i][j] = f3_mfma32(fa[set][1][i], wd[j], acc[i][j]);
     };
 
     // ---- prologue: halo(0), B(0), B(1) in LDS; B(2) in flight in register set 0
@@ -532,7 +456,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_halo_kernel(ConvF3Params
             const int y = ty_ * G3_TH + 2 * wm + i;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int x = tx_ * G3_TW + (r & 3) + 8 * (r >> 2) + 4 * fh;
+                const int x = tx_ * G3_TW + f3_crow(r, fh);
                 if (y >= p.OH || x >= p.OW) continue;
                 float v = acc[i][j][r] * sc + sh;
                 if (p.relu) v = v <= 0.f ? 0.f : v;                   // NaN propagates, like torch.relu
@@ -580,7 +504,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_frag_kernel(ConvF3Params
     const int row0 = SHAPE ? 0 : 2 * wm, ch0 = SHAPE ? wave * 32 : wn * 64;      // the wave's first image row / channel in the tile
     const int fr = lane & 31, fh = lane >> 5;
     int tile, nblk;
-    if (!f3_tile_of_block(p, tile, nblk)) return;     // padding block of the last group (uniform)
+    if (!f3_tile_of_block(p.ntiles, p.nblocks, p.xmap, tile, nblk)) return;     // padding block of the last group (uniform)
     const int tx_ = tile % p.tiles_x; tile /= p.tiles_x;
     const int ty_ = tile % p.tiles_y; tile /= p.tiles_y;
     const int b = tile;
@@ -642,7 +566,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_frag_kernel(ConvF3Params
             const int hp = piece >> 2, q = piece & 3;
             if (hp >= G3_HP) continue;
             f16x4 h, l;
-            split_act4(rh[(HALO_FAR ? 2 * half : 0) + k], h, l);
+            f3_split4(rh[(HALO_FAR ? 2 * half : 0) + k], h, l);
             const int off = hp * F3_LDB + 8 * q;
             *reinterpret_cast<f16x4*>(&Ah[buf][0][off]) = h;
             *reinterpret_cast<f16x4*>(&Ah[buf][1][off]) = l;
@@ -689,10 +613,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_frag_kernel(ConvF3Params
             fa[set][pl][t] = *reinterpret_cast<const f16x8*>(
                 &Ah[hbuf][pl][a_off + ((t + ky) * G3_HW + kx) * F3_LDB]);
     };
+    // the three products of f3_mac3 in its order, product-major over the tiles so that the step's other work goes between them
     auto mfma_step = [&](int set, auto ky_, const f16x8 (&fb)[2][NJ], auto&& between0, auto&& between1) {
         f16x8 wd[NJ];
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) wd[j] = lift_down(fb[0][j]);
+        for (int j = 0; j < NJ; ++j) wd[j] = f3_lift_down(fb[0][j]);
         if constexpr (SRC != 0) {
             // the same three products per accumulator in the same order; image row i at tap row ky reads halo row i + ky
             constexpr int ky = decltype(ky_)::value;
@@ -700,34 +625,34 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_frag_kernel(ConvF3Params
             for (int i = 0; i < NI; ++i)
                 if ((live >> (row0 + i + ky)) & 1)
 #pragma unroll
-                    for (int j = 0; j < NJ; ++j) acc[i][j] = F3_MFMA(fa[set][1][i], wd[j], acc[i][j]);
+                    for (int j = 0; j < NJ; ++j) acc[i][j] = f3_mfma32(fa[set][1][i], wd[j], acc[i][j]);
             between0();
 #pragma unroll
             for (int i = 0; i < NI; ++i)
                 if ((live >> (row0 + i + ky)) & 1)
 #pragma unroll
-                    for (int j = 0; j < NJ; ++j) acc[i][j] = F3_MFMA(fa[set][0][i], fb[1][j], acc[i][j]);
+                    for (int j = 0; j < NJ; ++j) acc[i][j] = f3_mfma32(fa[set][0][i], fb[1][j], acc[i][j]);
 #pragma unroll
             for (int i = 0; i < NI; ++i)
                 if ((live >> (row0 + i + ky)) & 1)
 #pragma unroll
-                    for (int j = 0; j < NJ; ++j) acc[i][j] = F3_MFMA(fa[set][0][i], fb[0][j], acc[i][j]);
+                    for (int j = 0; j < NJ; ++j) acc[i][j] = f3_mfma32(fa[set][0][i], fb[0][j], acc[i][j]);
             between1();
             return;
         }
 #pragma unroll
         for (int i = 0; i < NI; ++i)
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) acc[i][j] = F3_MFMA(fa[set][1][i], wd[j], acc[i][j]);       // xl' * wd
+            for (int j = 0; j < NJ; ++j) acc[i][j] = f3_mfma32(fa[set][1][i], wd[j], acc[i][j]);       // xl' * wd
         between0();
 #pragma unroll
         for (int i = 0; i < NI; ++i)
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) acc[i][j] = F3_MFMA(fa[set][0][i], fb[1][j], acc[i][j]);    // xh * wl
+            for (int j = 0; j < NJ; ++j) acc[i][j] = f3_mfma32(fa[set][0][i], fb[1][j], acc[i][j]);    // xh * wl
 #pragma unroll
         for (int i = 0; i < NI; ++i)
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) acc[i][j] = F3_MFMA(fa[set][0][i], fb[0][j], acc[i][j]);    // xh * wh
+            for (int j = 0; j < NJ; ++j) acc[i][j] = f3_mfma32(fa[set][0][i], fb[0][j], acc[i][j]);    // xh * wh
         between1();
     };
 
@@ -802,7 +727,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_frag_kernel(ConvF3Params
                 for (int r = 0; r < 16; ++r) {
                     float v = acc[i][j][r] * sc + sh;
                     if (p.relu) v = v <= 0.f ? 0.f : v;
-                    scr[((r & 3) + 8 * (r >> 2) + 4 * fh) * SP + j * 32 + fr] = v;
+                    scr[(f3_crow(r, fh)) * SP + j * 32 + fr] = v;
                 }
             }
             __builtin_amdgcn_s_waitcnt(0xc07f);
@@ -841,7 +766,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_frag_kernel(ConvF3Params
             const int y = ty_ * G3_TH + row0 + i;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int x = tx_ * G3_TW + (r & 3) + 8 * (r >> 2) + 4 * fh;
+                const int x = tx_ * G3_TW + f3_crow(r, fh);
                 if (y >= p.OH || x >= p.OW) continue;
                 float v = acc[i][j][r] * sc + sh;
                 if (p.relu) v = v <= 0.f ? 0.f : v;                   // NaN propagates, like torch.relu
@@ -865,7 +790,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_frag_kernel(ConvF3Params
 // accumulator, but 32 input channels deep per instruction instead of 16: NOT bit-identical to the kernels above
 // (same error class; tests compare at fp32 tolerance).
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define F3_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0)
 #define G16_HBUF 9984                  // one (chunk, plane) halo buffer: 204 pixels x 48 B, padded to a multiple of 256
 
 __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_frag16_kernel(ConvF3Params p)
@@ -876,7 +800,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_frag16_kernel(ConvF3Para
     const int wm = wave & 1, wn = wave >> 1;
     const int lr = lane & 15, lq = lane >> 4;
     int tile, nblk;
-    if (!f3_tile_of_block(p, tile, nblk)) return;     // padding block of the last group (uniform)
+    if (!f3_tile_of_block(p.ntiles, p.nblocks, p.xmap, tile, nblk)) return;     // padding block of the last group (uniform)
     const int tx_ = tile % p.tiles_x; tile /= p.tiles_x;
     const int ty_ = tile % p.tiles_y; tile /= p.tiles_y;
     const int b = tile;
@@ -908,7 +832,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_frag16_kernel(ConvF3Para
             const int c = piece >= 816 ? 1 : 0, rem = piece - 816 * c;
             const int hp = rem >> 2, q = rem & 3;
             f16x4 h, l;
-            split_act4(rh[k], h, l);
+            f3_split4(rh[k], h, l);
             const int off = hp * F3_LDB + 8 * q;
             *reinterpret_cast<f16x4*>(&Ah[buf][c][0][off]) = h;
             *reinterpret_cast<f16x4*>(&Ah[buf][c][1][off]) = l;
@@ -951,16 +875,17 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_frag16_kernel(ConvF3Para
         for (int mt = 0; mt < 4; ++mt)
             fa[set][pl][mt] = *reinterpret_cast<const f16x8*>(base + (((mt >> 1) + ky) * G3_HW + 16 * (mt & 1) + kx) * F3_LDB);
     };
+    // the three products of f3_mac3 in its order, product-major over the four row tiles of a column tile
     auto mfma_step = [&](int set, int snext, auto&& between0, auto&& between1) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const f16x8 wd = lift_down(fb[0][j]);
+            const f16x8 wd = f3_lift_down(fb[0][j]);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) acc[i][j] = F3_MFMA16(fa[set][1][i], wd, acc[i][j]);          // xl' * wd
+            for (int i = 0; i < 4; ++i) acc[i][j] = f3_mfma16(fa[set][1][i], wd, acc[i][j]);          // xl' * wd
 #pragma unroll
-            for (int i = 0; i < 4; ++i) acc[i][j] = F3_MFMA16(fa[set][0][i], fb[1][j], acc[i][j]);    // xh * wl
+            for (int i = 0; i < 4; ++i) acc[i][j] = f3_mfma16(fa[set][0][i], fb[1][j], acc[i][j]);    // xh * wl
 #pragma unroll
-            for (int i = 0; i < 4; ++i) acc[i][j] = F3_MFMA16(fa[set][0][i], fb[0][j], acc[i][j]);    // xh * wh
+            for (int i = 0; i < 4; ++i) acc[i][j] = f3_mfma16(fa[set][0][i], fb[0][j], acc[i][j]);    // xh * wh
             load_b1(j, snext);                        // tile j of the next step into the registers just consumed
             if (j == 0) between0();
             if (j == 1) between1();
@@ -1040,7 +965,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_f16x3_bstream_kernel(ConvF3Para
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave & 1, wn = wave >> 1;
     int tile, nblk;
-    if (!f3_tile_of_block(p, tile, nblk)) return;     // padding block of the last group (uniform)
+    if (!f3_tile_of_block(p.ntiles, p.nblocks, p.xmap, tile, nblk)) return;     // padding block of the last group (uniform)
     const int tx_ = tile % p.tiles_x; tile /= p.tiles_x;
     const int ty_ = tile % p.tiles_y; tile /= p.tiles_y;
     const int b = tile;
@@ -1081,7 +1006,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_f16x3_bstream_kernel(ConvF3Para
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             f16x4 h, l;
-            split_act4(ra[i], h, l);
+            f3_split4(ra[i], h, l);
             const int off = (ar + 64 * i) * F3_LDB + 8 * aq;
             *reinterpret_cast<f16x4*>(&As[buf][0][off]) = h;
             *reinterpret_cast<f16x4*>(&As[buf][1][off]) = l;
@@ -1129,15 +1054,11 @@ __global__ __launch_bounds__(256, 2) void conv2d_f16x3_bstream_kernel(ConvF3Para
             for (int pl = 0; pl < 2; ++pl)
                 a[pl][t] = *reinterpret_cast<const f16x8*>(&As[buf][pl][a_off + t * 32 * F3_LDB]);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) wd[j] = lift_down(fb[0][j]);
+        for (int j = 0; j < 2; ++j) wd[j] = f3_lift_down(fb[0][j]);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                acc[i][j] = F3_MFMA(a[1][i], wd[j], acc[i][j]);          // xl' * wd   (smallest first)
-                acc[i][j] = F3_MFMA(a[0][i], fb[1][j], acc[i][j]);       // xh * wl
-                acc[i][j] = F3_MFMA(a[0][i], fb[0][j], acc[i][j]);       // xh * wh
-            }
+            for (int j = 0; j < 2; ++j) f3_mac3(a[0][i], a[1][i], fb[0][j], fb[1][j], wd[j], acc[i][j]);
     };
     // step s: B(s+2) requested, A(s+1) requested, MFMAs of step s, A(s+1) split + stored, barrier
     auto step = [&](auto k_, int s) {
@@ -1174,7 +1095,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_f16x3_bstream_kernel(ConvF3Para
         for (int i = 0; i < 2; ++i) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+                const int m = wm * 64 + i * 32 + f3_crow(r, fh);
                 const int y = ty_ * F3_TH + m / F3_TW, x = tx_ * F3_TW + m % F3_TW;
                 if (y >= MH || x >= MW) continue;
                 float v = acc[i][j][r] * sc + sh;
@@ -1562,41 +1483,21 @@ extern "C" int al3d_deconv2x2_nhwc_f16x3_gap(const float* in, const void* wgt_f1
 // wave and step, into a ring of NS stages that runs NS-1 steps ahead; counted `s_waitcnt vmcnt` + ONE raw
 // `s_barrier` per step publish a stage.  The activation split (xh, xl') happens on the fragment, in registers,
 // after the ds_read -- 2 x more VALU than splitting once per workgroup, but off the critical path of the loads.
-// Bank conflicts are handled on the SOURCE side of the DMA (the LDS side is lane-linear by construction): lane
-// (row r, chunk s) fetches chunk s ^ f(r), the swizzle of the sparse LDS-DMA kernel (spconv_glds.hip).
-// LDS reads are inline asm with their own lgkmcnt wait: hipcc cannot see that a DMA writes LDS and would
-// otherwise drain vmcnt(0) before every read it cannot disambiguate.
+// The stage layout, the source-side swizzle, the fragment offsets and reads, and the pipelined loop of the default
+// kernel are al3d_f16x3.h's (f3_ring_gemm, shared with the token GEMM of tokens.hip); this file keeps the pixel / tap
+// address generation and the epilogues.
 // Same tiles, same grid, same product order as conv2d_f16x3_kernel: bit-identical results, same GAP partials.
-typedef float dg_f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void dg_lds_void;
-typedef const __attribute__((address_space(1))) void dg_gbl_void;
 __device__ __attribute__((aligned(256))) float g_dma_zero[64];     // stays zero: source of out-of-image pixels
-
-#define DG_STAGE 16384      // bytes per stage: A 8 KB + B 8 KB
-#define DG_BOFF 8192
-
-template <int N> __device__ __forceinline__ void dg_wait_vm()
-{
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ int dg_swz(int r) { return (r & 1) | (((r >> 3) & 1) << 1); }
-
-__device__ __forceinline__ void dg_split8(const dg_f32x4& lo, const dg_f32x4& hi, f16x8& ph, f16x8& pl)
-{
-    const float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { _Float16 a, b; split_act(v[e], a, b); ph[e] = a; pl[e] = b; }
-}
 
 template <int MODE, int NS>
 __global__ __launch_bounds__(256, NS <= 3 ? 3 : 2) void conv2d_f16x3_dma_kernel(ConvF3Params p)
 {
-    __shared__ __attribute__((aligned(1024))) unsigned char smem[NS * DG_STAGE];
+    __shared__ __attribute__((aligned(1024))) unsigned char smem[NS * F3_RING_STAGE];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave & 1, wn = wave >> 1;
     int tile, nblk;
-    if (!f3_tile_of_block(p, tile, nblk)) return;     // padding block of the last group (uniform)
+    if (!f3_tile_of_block(p.ntiles, p.nblocks, p.xmap, tile, nblk)) return;     // padding block of the last group (uniform)
     const int tx_ = tile % p.tiles_x; tile /= p.tiles_x;
     const int ty_ = tile % p.tiles_y; tile /= p.tiles_y;
     const int b = tile;
@@ -1607,7 +1508,7 @@ __global__ __launch_bounds__(256, NS <= 3 ? 3 : 2) void conv2d_f16x3_dma_kernel(
     const int wtaps = MODE == 0 ? taps : 4;
     const int kchunks = p.Cin / F3_BK;
     const int total = taps * kchunks;
-    const unsigned smem_base = (unsigned)(size_t)(dg_lds_void*)smem;
+    const unsigned smem_base = (unsigned)(size_t)(lds_void*)smem;
 
     // ---- DMA side.  Wave w fetches M-tile w (pixels 32w .. 32w+31 of the 8 x 16 tile) and the 2 KB quarter w of the
     // weight tile.  Lane (jg, sg) of piece i fetches chunk sg ^ f(r) of row r = 2 jg + i.
@@ -1618,14 +1519,14 @@ __global__ __launch_bounds__(256, NS <= 3 ? 3 : 2) void conv2d_f16x3_dma_kernel(
         const int r = 2 * jg + i, m = 32 * wave + r;
         py[i] = ty_ * F3_TH + m / F3_TW;
         px[i] = tx_ * F3_TW + m % F3_TW;
-        cg[i] = (sg ^ dg_swz(r)) * 4;
+        cg[i] = (sg ^ f3_ring_swz(r)) * 4;
     }
     const char* wsrc = reinterpret_cast<const char*>(p.wgt) +
                        ((int64_t)nblk * wtaps + tap0) * kchunks * 8192 + wave * 2048 + lane * 16;
     int ltap = 0, lchunk = 0;                          // cursor of the next stage to request
     auto issue = [&](int stage) {
         const int ky = MODE == 0 ? ltap / p.ksize : 0, kx = MODE == 0 ? ltap - ky * p.ksize : 0;
-        const unsigned dst = __builtin_amdgcn_readfirstlane(smem_base + stage * DG_STAGE + wave * 2048);
+        const unsigned dst = __builtin_amdgcn_readfirstlane(smem_base + stage * F3_RING_STAGE + wave * 2048);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             int iy, ix;
@@ -1635,12 +1536,12 @@ __global__ __launch_bounds__(256, NS <= 3 ? 3 : 2) void conv2d_f16x3_dma_kernel(
             // 32-bit element index (the entry checks B*H*W*Cin < 2^31): keeps the select a pair of v_cndmask, no branch
             const unsigned idx = (unsigned)(((b * p.H + iy) * p.W + ix) * p.Cin + lchunk * F3_BK + cg[i]);
             const float* src = ok ? p.in + idx : g_dma_zero + cg[i];
-            __builtin_amdgcn_global_load_lds((dg_gbl_void*)src, (dg_lds_void*)(size_t)(dst + i * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gbl_void*)src, (lds_void*)(size_t)(dst + i * 1024), 16, 0, 0);
         }
         const char* ws = wsrc + ((int64_t)ltap * kchunks + lchunk) * 8192;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
-            __builtin_amdgcn_global_load_lds((dg_gbl_void*)(ws + i * 1024), (dg_lds_void*)(size_t)(dst + DG_BOFF + i * 1024),
+            __builtin_amdgcn_global_load_lds((gbl_void*)(ws + i * 1024), (lds_void*)(size_t)(dst + F3_RING_BOFF + i * 1024),
                                              16, 0, 0);
         // steps past the end re-fetch the last one (into a free stage): the DMA count per step stays 4
         if (ltap * kchunks + lchunk + 1 < total) { if (++lchunk == kchunks) { lchunk = 0; ++ltap; } }
@@ -1654,51 +1555,31 @@ __global__ __launch_bounds__(256, NS <= 3 ? 3 : 2) void conv2d_f16x3_dma_kernel(
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-    // ---- fragment side: lane (fr, fh) reads chunks 2 fh, 2 fh + 1 of pixel row fr of M-tiles 2 wm, 2 wm + 1 and
-    // chunk fh of weight rows wn * 64 + {0, 32} + fr of both planes
     const int fr = lane & 31, fh = lane >> 5;
-    const unsigned offA0 = (unsigned)(wm * 4096 + (fr & 1) * 1024 + (fr >> 1) * 64 + (((2 * fh) ^ dg_swz(fr)) * 16));
-    const unsigned offA1 = (unsigned)(wm * 4096 + (fr & 1) * 1024 + (fr >> 1) * 64 + (((2 * fh + 1) ^ dg_swz(fr)) * 16));
-    const unsigned offB = (unsigned)(DG_BOFF + (wn * 64 + fr) * 32 + ((fh ^ ((fr >> 3) & 1)) * 16));
+    const F3RingOffs off = f3_ring_offsets(wm, wn, fr, fh);            // fragment side
 
 #pragma unroll
     for (int s = 0; s < NS - 1; ++s) issue(s);
     int stage = 0, fill = NS - 1;
     for (int s = 0; s < total; ++s) {
-        dg_wait_vm<4 * (NS - 2)>();                    // this wave's share of stage s has landed ...
+        f3_wait_vm<4 * (NS - 2)>();                    // this wave's share of stage s has landed ...
         __builtin_amdgcn_s_barrier();                  // ... everyone's has, and stage s-1 is free
         issue(fill);
-        const unsigned sb = smem_base + stage * DG_STAGE;
-        dg_f32x4 a0l, a0h, a1l, a1h;
-        f16x8 wh0, wl0, wh1, wl1;
-        asm volatile("ds_read_b128 %0, %8\n\t"
-                     "ds_read_b128 %1, %9\n\t"
-                     "ds_read_b128 %2, %8 offset:2048\n\t"
-                     "ds_read_b128 %3, %9 offset:2048\n\t"
-                     "ds_read_b128 %4, %10\n\t"
-                     "ds_read_b128 %5, %10 offset:4096\n\t"
-                     "ds_read_b128 %6, %10 offset:1024\n\t"
-                     "ds_read_b128 %7, %10 offset:5120\n\t"
-                     "s_waitcnt lgkmcnt(0)"
-                     : "=&v"(a0l), "=&v"(a0h), "=&v"(a1l), "=&v"(a1h), "=&v"(wh0), "=&v"(wl0), "=&v"(wh1), "=&v"(wl1)
-                     : "v"(sb + offA0), "v"(sb + offA1), "v"(sb + offB) : "memory");
+        f32x4 a0l, a0h, a1l, a1h;
+        f16x8 wh[2], wl[2];
+        f3_ring_read(a0l, a0h, a1l, a1h, wh[0], wl[0], wh[1], wl[1], smem_base + stage * F3_RING_STAGE, off);
         f16x8 ah[2], al[2];
-        dg_split8(a0l, a0h, ah[0], al[0]);
-        dg_split8(a1l, a1h, ah[1], al[1]);
-        const f16x8 wd0 = lift_down(wh0), wd1 = lift_down(wh1);
+        f3_split8(a0l, a0h, ah[0], al[0]);
+        f3_split8(a1l, a1h, ah[1], al[1]);
+        const f16x8 wd[2] = {f3_lift_down(wh[0]), f3_lift_down(wh[1])};
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            acc[i][0] = F3_MFMA(al[i], wd0, acc[i][0]);                  // xl' * wd   (smallest first)
-            acc[i][0] = F3_MFMA(ah[i], wl0, acc[i][0]);                  // xh * wl
-            acc[i][0] = F3_MFMA(ah[i], wh0, acc[i][0]);                  // xh * wh
-            acc[i][1] = F3_MFMA(al[i], wd1, acc[i][1]);
-            acc[i][1] = F3_MFMA(ah[i], wl1, acc[i][1]);
-            acc[i][1] = F3_MFMA(ah[i], wh1, acc[i][1]);
-        }
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) f3_mac3(ah[i], al[i], wh[j], wl[j], wd[j], acc[i][j]);
         stage = stage + 1 == NS ? 0 : stage + 1;
         fill = fill + 1 == NS ? 0 : fill + 1;
     }
-    dg_wait_vm<0>();                                   // the tail's dummy requests must not outlive the workgroup's LDS
+    f3_wait_vm<0>();                                   // the tail's dummy requests must not outlive the workgroup's LDS
 
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -1711,7 +1592,7 @@ __global__ __launch_bounds__(256, NS <= 3 ? 3 : 2) void conv2d_f16x3_dma_kernel(
         for (int i = 0; i < 2; ++i) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+                const int m = wm * 64 + i * 32 + f3_crow(r, fh);
                 const int y = ty_ * F3_TH + m / F3_TW, x = tx_ * F3_TW + m % F3_TW;
                 if (y >= MH || x >= MW) continue;
                 float v = acc[i][j][r] * sc + sh;
@@ -1732,26 +1613,17 @@ __global__ __launch_bounds__(256, NS <= 3 ? 3 : 2) void conv2d_f16x3_dma_kernel(
     }
 }
 
-// Software-pipelined form of the kernel above (the default): the fragments of step s+1 are read while the
-// MFMAs of step s run, from ONE asm block that interleaves the eight ds_reads with the twelve MFMAs and ends in
-// the lgkmcnt wait -- hipcc never sees a register that is still in flight.  Two operand sets alternate (the loop
-// is unrolled by two), so the split of step s+1 writes registers no queued MFMA reads.  All NS stage buffers are
-// in flight: a stage's buffer is refilled as soon as every wave holds its fragments in registers.
-// The four accumulator chains are interleaved inside the block (dependent MFMAs are four instructions apart);
-// each accumulator still receives xl'*wd, xh*wl, xh*wh in that order per step: the same bits.
-struct DgOps {
-    f16x8 ah[2], al[2], wh[2], wl[2], wd[2];
-};
-
+// Software-pipelined form of the kernel above (the default): the loop is f3_ring_gemm (al3d_f16x3.h), all NS stages in
+// flight; each accumulator still receives xl'*wd, xh*wl, xh*wh in that order per step: the same bits.
 template <int MODE, int NS, int IO = 0>
 __global__ __launch_bounds__(256, 2) void conv2d_f16x3_dma2_kernel(ConvF3Params p)
 {
-    __shared__ __attribute__((aligned(1024))) unsigned char smem[NS * DG_STAGE];
+    __shared__ __attribute__((aligned(1024))) unsigned char smem[NS * F3_RING_STAGE];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave & 1, wn = wave >> 1;
     int tile, nblk;
-    if (!f3_tile_of_block(p, tile, nblk)) return;     // padding block of the last group (uniform)
+    if (!f3_tile_of_block(p.ntiles, p.nblocks, p.xmap, tile, nblk)) return;     // padding block of the last group (uniform)
     const int tx_ = tile % p.tiles_x; tile /= p.tiles_x;
     const int ty_ = tile % p.tiles_y; tile /= p.tiles_y;
     const int b = tile;
@@ -1762,7 +1634,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_f16x3_dma2_kernel(ConvF3Params 
     const int wtaps = MODE == 0 ? taps : 4;
     const int kchunks = p.Cin / F3_BK;
     const int total = taps * kchunks;
-    const unsigned smem_base = (unsigned)(size_t)(dg_lds_void*)smem;
+    const unsigned smem_base = (unsigned)(size_t)(lds_void*)smem;
 
     const int jg = lane >> 2, sg = lane & 3;
     int py[2], px[2], cg[2];
@@ -1771,7 +1643,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_f16x3_dma2_kernel(ConvF3Params 
         const int r = 2 * jg + i, m = 32 * wave + r;
         py[i] = ty_ * F3_TH + m / F3_TW;
         px[i] = tx_ * F3_TW + m % F3_TW;
-        cg[i] = (sg ^ dg_swz(r)) * 4;
+        cg[i] = (sg ^ f3_ring_swz(r)) * 4;
     }
     const char* wsrc = reinterpret_cast<const char*>(p.wgt) +
                        ((int64_t)nblk * wtaps + tap0) * kchunks * 8192 + wave * 2048 + lane * 16;
@@ -1795,109 +1667,26 @@ __global__ __launch_bounds__(256, 2) void conv2d_f16x3_dma2_kernel(ConvF3Params 
                 ainc[i] = ok ? 4u * F3_BK : 0u;
             }
         }
-        const unsigned dst = __builtin_amdgcn_readfirstlane(smem_base + stage * DG_STAGE + wave * 2048);
+        const unsigned dst = __builtin_amdgcn_readfirstlane(smem_base + stage * F3_RING_STAGE + wave * 2048);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
-            __builtin_amdgcn_global_load_lds((dg_gbl_void*)(abase[i] + (size_t)lchunk * ainc[i]),
-                                             (dg_lds_void*)(size_t)(dst + i * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gbl_void*)(abase[i] + (size_t)lchunk * ainc[i]),
+                                             (lds_void*)(size_t)(dst + i * 1024), 16, 0, 0);
         const char* ws = wsrc + ((int64_t)ltap * kchunks + lchunk) * 8192;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
-            __builtin_amdgcn_global_load_lds((dg_gbl_void*)(ws + i * 1024), (dg_lds_void*)(size_t)(dst + DG_BOFF + i * 1024),
+            __builtin_amdgcn_global_load_lds((gbl_void*)(ws + i * 1024), (lds_void*)(size_t)(dst + F3_RING_BOFF + i * 1024),
                                              16, 0, 0);
         // steps past the end re-fetch the last one (into a free stage): the DMA count per step stays 4
         if (ltap * kchunks + lchunk + 1 < total) { if (++lchunk == kchunks) { lchunk = 0; ++ltap; } }
     };
 
+#pragma unroll
+    for (int s = 0; s < NS; ++s) issue(s);             // fill the ring
     f32x16 c00, c01, c10, c11;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { c00[r] = 0.f; c01[r] = 0.f; c10[r] = 0.f; c11[r] = 0.f; }
-
+    // row formats are compile-time: no branch in the loop.  Pair pixels in: the 32 bytes of a fragment ARE (xh[8], xl'[8])
+    f3_ring_gemm<NS, (IO & SP_IO_IN_PAIR) != 0, f3_split>(smem_base, total, wm, wn, lane, issue, c00, c01, c10, c11);
     const int fr = lane & 31, fh = lane >> 5;
-    const unsigned offA0 = (unsigned)(wm * 4096 + (fr & 1) * 1024 + (fr >> 1) * 64 + (((2 * fh) ^ dg_swz(fr)) * 16));
-    const unsigned offA1 = (unsigned)(wm * 4096 + (fr & 1) * 1024 + (fr >> 1) * 64 + (((2 * fh + 1) ^ dg_swz(fr)) * 16));
-    const unsigned offB = (unsigned)(DG_BOFF + (wn * 64 + fr) * 32 + ((fh ^ ((fr >> 3) & 1)) * 16));
-
-    DgOps A, B;
-    constexpr bool in_pair = (IO & SP_IO_IN_PAIR) != 0;                      // row formats are compile-time: no branch in the loop
-    auto finish = [&](DgOps& o, const dg_f32x4& r0l, const dg_f32x4& r0h, const dg_f32x4& r1l, const dg_f32x4& r1h) {
-        if constexpr (in_pair) {                         // pair pixels: the 32 bytes of a fragment ARE (xh[8], xl'[8])
-            o.ah[0] = __builtin_bit_cast(f16x8, r0l); o.al[0] = __builtin_bit_cast(f16x8, r0h);
-            o.ah[1] = __builtin_bit_cast(f16x8, r1l); o.al[1] = __builtin_bit_cast(f16x8, r1h);
-        } else {
-            dg_split8(r0l, r0h, o.ah[0], o.al[0]);
-            dg_split8(r1l, r1h, o.ah[1], o.al[1]);
-        }
-        o.wd[0] = lift_down(o.wh[0]);
-        o.wd[1] = lift_down(o.wh[1]);
-    };
-
-#pragma unroll
-    for (int s = 0; s < NS; ++s) issue(s);
-    {
-        dg_wait_vm<4 * (NS - 1)>();                    // stage 0
-        __builtin_amdgcn_s_barrier();
-        dg_f32x4 r0l, r0h, r1l, r1h;
-        asm volatile("ds_read_b128 %0, %8\n\t"
-                     "ds_read_b128 %1, %9\n\t"
-                     "ds_read_b128 %2, %8 offset:2048\n\t"
-                     "ds_read_b128 %3, %9 offset:2048\n\t"
-                     "ds_read_b128 %4, %10\n\t"
-                     "ds_read_b128 %5, %10 offset:4096\n\t"
-                     "ds_read_b128 %6, %10 offset:1024\n\t"
-                     "ds_read_b128 %7, %10 offset:5120\n\t"
-                     "s_waitcnt lgkmcnt(0)"
-                     : "=&v"(r0l), "=&v"(r0h), "=&v"(r1l), "=&v"(r1h), "=&v"(A.wh[0]), "=&v"(A.wl[0]), "=&v"(A.wh[1]),
-                       "=&v"(A.wl[1])
-                     : "v"(smem_base + offA0), "v"(smem_base + offA1), "v"(smem_base + offB) : "memory");
-        finish(A, r0l, r0h, r1l, r1h);
-    }
-    int nstage = 1 % NS, fill = 0;
-    // one step: MFMAs on `cur`, fragments of the next stage -> `nxt`
-    auto step = [&](DgOps& cur, DgOps& nxt) {
-        dg_wait_vm<4 * (NS - 2)>();                    // this wave's share of the next stage has landed ...
-        __builtin_amdgcn_s_barrier();                  // ... everyone's has; every wave holds the current stage in registers
-        issue(fill);                                   // -> the current stage's buffer
-        const unsigned sb = smem_base + nstage * DG_STAGE;
-        dg_f32x4 r0l, r0h, r1l, r1h;
-        asm volatile("s_nop 1\n\t"
-                     "ds_read_b128 %0, %22\n\t"
-                     "ds_read_b128 %1, %23\n\t"
-                     "v_mfma_f32_32x32x16_f16 %8, %12, %16, %8\n\t"
-                     "v_mfma_f32_32x32x16_f16 %9, %12, %19, %9\n\t"
-                     "ds_read_b128 %2, %22 offset:2048\n\t"
-                     "ds_read_b128 %3, %23 offset:2048\n\t"
-                     "v_mfma_f32_32x32x16_f16 %10, %14, %16, %10\n\t"
-                     "v_mfma_f32_32x32x16_f16 %11, %14, %19, %11\n\t"
-                     "ds_read_b128 %4, %24\n\t"
-                     "ds_read_b128 %5, %24 offset:4096\n\t"
-                     "v_mfma_f32_32x32x16_f16 %8, %13, %17, %8\n\t"
-                     "v_mfma_f32_32x32x16_f16 %9, %13, %20, %9\n\t"
-                     "ds_read_b128 %6, %24 offset:1024\n\t"
-                     "ds_read_b128 %7, %24 offset:5120\n\t"
-                     "v_mfma_f32_32x32x16_f16 %10, %15, %17, %10\n\t"
-                     "v_mfma_f32_32x32x16_f16 %11, %15, %20, %11\n\t"
-                     "v_mfma_f32_32x32x16_f16 %8, %13, %18, %8\n\t"
-                     "v_mfma_f32_32x32x16_f16 %9, %13, %21, %9\n\t"
-                     "v_mfma_f32_32x32x16_f16 %10, %15, %18, %10\n\t"
-                     "v_mfma_f32_32x32x16_f16 %11, %15, %21, %11\n\t"
-                     "s_waitcnt lgkmcnt(0)"
-                     : "=&v"(r0l), "=&v"(r0h), "=&v"(r1l), "=&v"(r1h), "=&v"(nxt.wh[0]), "=&v"(nxt.wl[0]), "=&v"(nxt.wh[1]),
-                       "=&v"(nxt.wl[1]), "+v"(c00), "+v"(c01), "+v"(c10), "+v"(c11)
-                     : "v"(cur.al[0]), "v"(cur.ah[0]), "v"(cur.al[1]), "v"(cur.ah[1]),                    // 12..15
-                       "v"(cur.wd[0]), "v"(cur.wl[0]), "v"(cur.wh[0]), "v"(cur.wd[1]), "v"(cur.wl[1]), "v"(cur.wh[1]),   // 16..21
-                       "v"(sb + offA0), "v"(sb + offA1), "v"(sb + offB)                                   // 22..24
-                     : "memory");
-        finish(nxt, r0l, r0h, r1l, r1h);
-        nstage = nstage + 1 == NS ? 0 : nstage + 1;
-        fill = fill + 1 == NS ? 0 : fill + 1;
-    };
-    for (int s = 0; s < total; s += 2) {
-        step(A, B);
-        if (s + 1 < total) step(B, A);
-    }
-    dg_wait_vm<0>();                                   // the tail's dummy requests must not outlive the workgroup's LDS
-    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");  // the last MFMAs' results before the VALU reads them
 
     const f32x16* accp[2][2] = {{&c00, &c01}, {&c10, &c11}};
     if constexpr ((IO & 4) == 0) {
@@ -1920,7 +1709,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_f16x3_dma2_kernel(ConvF3Params 
                 const f32x16& acc = *accp[i][j];
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int ml = (r & 3) + 8 * (r >> 2) + 4 * fh;
+                    const int ml = f3_crow(r, fh);
                     const int m = wm * 64 + i * 32 + ml;
                     const int y = ty_ * F3_TH + m / F3_TW, x = tx_ * F3_TW + m % F3_TW;
                     float v = acc[r] * sc + sh;
@@ -1992,7 +1781,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_f16x3_dma2_kernel(ConvF3Params 
             const f32x16& acc = *accp[i][j];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+                const int m = wm * 64 + i * 32 + f3_crow(r, fh);
                 const int y = ty_ * F3_TH + m / F3_TW, x = tx_ * F3_TW + m % F3_TW;
                 if (y >= MH || x >= MW) continue;
                 float v = acc[r] * sc + sh;

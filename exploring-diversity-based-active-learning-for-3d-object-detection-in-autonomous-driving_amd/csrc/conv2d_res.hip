@@ -1,7 +1,7 @@
 // Kernels of the camera-only BEV decoder (GeneralizedResNet + LSSFPN behind the plain LSS view transform).
 //
 //   conv3x3_res_f16x3_kernel   3x3 / s1 / p1 convolution + affine + residual + ReLU: conv2 + bn2 + shortcut + ReLU of a
-//                              ResNet BasicBlock as one launch, f16x3 arithmetic (conv2d_f16x3.hip's header)
+//                              ResNet BasicBlock as one launch, f16x3 arithmetic (al3d_f16x3.h)
 //   add_relu_kernel            relu(x + res): the same residual step behind a convolution of the other arithmetics
 //   upsample_bilinear_ac_kernel  bilinear resize, align_corners = True (LSSFPN's tail)
 //
@@ -20,13 +20,10 @@
 // the order of conv2d_f16x3_kernel / conv2d_f16x3_dma_kernel.  The epilogue is (acc * scale + shift) + res, then ReLU,
 // each operation rounded to f32 on its own (the file is built without contraction).
 #include "al3d_common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+#include "al3d_f16x3.h"
 
 #define R3_TH 4
 #define R3_TW 8
-#define R3_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0)
 
 struct ConvResParams {
     const float* in;        // [B, H, W, Cin] f32
@@ -40,18 +37,6 @@ struct ConvResParams {
 };
 
 __device__ __attribute__((aligned(32))) float g_res_zero[8];       // stays zero: source of out-of-image pixels
-
-// as conv2d_f16x3.hip's split_act: xh = f16(x), xl' = f16((x - xh) * 2^11)
-__device__ __forceinline__ void r3_split8(const float4& lo, const float4& hi, f16x8& ph, f16x8& pl)
-{
-    const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const _Float16 h = (_Float16)v[e];
-        ph[e] = h;
-        pl[e] = (_Float16)__builtin_fmaf((float)h, -2048.0f, v[e] * 2048.0f);
-    }
-}
 
 template <int NB>
 __global__ __launch_bounds__(256) void conv3x3_res_f16x3_kernel(ConvResParams p)
@@ -113,14 +98,9 @@ __global__ __launch_bounds__(256) void conv3x3_res_f16x3_kernel(ConvResParams p)
     for (int s = 0; s < total; ++s) {
         if (s + 1 < total) request(a_nxt, wh_nxt, wl_nxt);
         f16x8 ah, al;
-        r3_split8(a_cur[0], a_cur[1], ah, al);
+        f3_split8(a_cur[0], a_cur[1], ah, al);
 #pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            const f16x8 wd = wh_cur[j] * (_Float16)0.00048828125f;         // wh * 2^-11 (exact; conv2d_f16x3.hip)
-            acc[j] = R3_MFMA(al, wd, acc[j]);                               // xl' * wd   (smallest first)
-            acc[j] = R3_MFMA(ah, wl_cur[j], acc[j]);                        // xh * wl
-            acc[j] = R3_MFMA(ah, wh_cur[j], acc[j]);                        // xh * wh
-        }
+        for (int j = 0; j < NB; ++j) f3_mac3(ah, al, wh_cur[j], wl_cur[j], f3_lift_down(wh_cur[j]), acc[j]);
         a_cur[0] = a_nxt[0]; a_cur[1] = a_nxt[1];
 #pragma unroll
         for (int j = 0; j < NB; ++j) { wh_cur[j] = wh_nxt[j]; wl_cur[j] = wl_nxt[j]; }
@@ -134,7 +114,7 @@ __global__ __launch_bounds__(256) void conv3x3_res_f16x3_kernel(ConvResParams p)
         const float sh = p.shift ? p.shift[n] : 0.0f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int m = (r & 3) + 8 * (r >> 2) + 4 * fh;
+            const int m = f3_crow(r, fh);
             const int y = ty_ * R3_TH + (m >> 3), x = tx_ * R3_TW + (m & 7);
             if (y >= p.H || x >= p.W) continue;
             const int64_t pix = ((int64_t)b * p.H + y) * p.W + x;

@@ -1,4 +1,4 @@
-// 3x3 / stride 1 / pad 1 convolution as Winograd F(2x2, 3x3) in f16x3 arithmetic (conv2d_f16x3.hip): 16 multiplies per
+// 3x3 / stride 1 / pad 1 convolution as Winograd F(2x2, 3x3) in f16x3 arithmetic (al3d_f16x3.h): 16 multiplies per
 // 2 x 2 output tile and (input, output) channel pair instead of 36, i.e. 2.25 x fewer matrix-core products on the
 // eleven stride-1 3x3 layers of the SECOND neck (det3d/models/necks/rpn.py:66-113 -- 58 of its 67.6 GFLOP per frame).
 //
@@ -27,11 +27,6 @@
 #include "sp_rows.h"
 #include <type_traits>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
-#define WN_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0)
 #define WN_IC(v) std::integral_constant<int, v>{}
 #define WN_T 16                         // output tile edge
 #define WN_HW (WN_T + 2)                // halo edge
@@ -39,10 +34,6 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 #define WN_STAGE 24576                  // bytes per halo stage: 24 DMA instructions of 16 pixels x 64 B (324 pixels used)
 #define WN_NS 3
 #define WN_XP 36                        // floats per (row a, j, tile) line of the output exchange: 32 channels + pad
-
-typedef float wn_f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void wn_lds_void;
-typedef const __attribute__((address_space(1))) void wn_gbl_void;
 
 struct WinoParams {
     const float* in;        // [B, H, W, Cin] f32
@@ -56,22 +47,6 @@ struct WinoParams {
 
 __device__ __attribute__((aligned(64))) float g_wn_zero[16];
 
-__device__ __forceinline__ void wn_split(float x, _Float16& h, _Float16& l)
-{
-    h = (_Float16)x;
-    l = (_Float16)__builtin_fmaf((float)h, -2048.0f, x * 2048.0f);
-}
-
-// same XCD-aware (pixel tile, channel block) order as conv2d_f16x3.hip
-__device__ __forceinline__ bool wn_tile_of_block(const WinoParams& p, int& tile, int& nblk)
-{
-    const int id = blockIdx.x, span = 8 * p.nblocks;
-    const int grp = id / span, rem = id - grp * span;
-    nblk = rem >> 3;
-    tile = grp * 8 + (rem & 7);
-    return tile < p.ntiles;
-}
-
 // The halo's 16-byte chunk q of pixel (row, col) sits at position q ^ ((col >> 2) & 3) of the pixel's 64 bytes (applied
 // on the source side of the DMA): the eight tiles of a tile row then read eight different bank groups.
 __device__ __forceinline__ int wn_swz(int col) { return (col >> 2) & 3; }
@@ -84,14 +59,14 @@ __global__ __launch_bounds__(256, 1) void conv3x3_f16x3_wino_kernel(WinoParams p
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 31, fh = lane >> 5;
     int tile, nblk;
-    if (!wn_tile_of_block(p, tile, nblk)) return;
+    if (!f3_tile_of_block(p.ntiles, p.nblocks, false, tile, nblk)) return;
     const int tx_ = tile % p.tiles_x; tile /= p.tiles_x;
     const int ty_ = tile % p.tiles_y; tile /= p.tiles_y;
     const int b = tile;
     const int n0 = nblk * 64;
     const int y0 = ty_ * WN_T - 1, x0 = tx_ * WN_T - 1;
     const int nchunks = p.Cin >> 4;
-    const unsigned smem_base = (unsigned)(size_t)(wn_lds_void*)smem;
+    const unsigned smem_base = (unsigned)(size_t)(lds_void*)smem;
 
     // ---- halo by LDS-DMA: instruction k of wave w covers halo pixels 16 (6 w + k) .. + 15; lane (px = l >> 2, pos = l & 3)
     // fetches chunk pos ^ swz(col).  Addresses depend on the chunk only through a constant stride.
@@ -112,7 +87,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_f16x3_wino_kernel(WinoParams p
         const unsigned dst = __builtin_amdgcn_readfirstlane(smem_base + (chunk % WN_NS) * WN_STAGE + wave * 6144);
 #pragma unroll
         for (int k = 0; k < 6; ++k)
-            __builtin_amdgcn_global_load_lds((wn_gbl_void*)(hsrc[k] + (size_t)cc * hinc[k]), (wn_lds_void*)(size_t)(dst + k * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gbl_void*)(hsrc[k] + (size_t)cc * hinc[k]), (lds_void*)(size_t)(dst + k * 1024), 16, 0, 0);
     };
 
     // ---- this wave's weight stream: positions 4 w .. 4 w + 3 (transformed row a = w), both 32-channel tiles of the block.
@@ -177,7 +152,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_f16x3_wino_kernel(WinoParams p
 
     // The patch rows of a tile are read and transformed in two halves (the fragment's two 16-byte pieces = channels
     // 8 h .. 8 h + 3 and 8 h + 4 .. 8 h + 7): eight 16-byte reads and 32 live registers at a time instead of sixteen / 64.
-    wn_f32x4 d[2][4];                                 // [row r1 / r2][pixel c]
+    f32x4 d[2][4];                                 // [row r1 / r2][pixel c]
     auto patch_read = [&](unsigned sb, int e) {       // sb = stage base + tile offset (0 / 9216)
         const unsigned s1 = sb + rdelta;
         asm volatile("ds_read_b128 %0, %8\n\tds_read_b128 %1, %9\n\tds_read_b128 %2, %10\n\tds_read_b128 %3, %11\n\t"
@@ -204,10 +179,10 @@ __global__ __launch_bounds__(256, 1) void conv3x3_f16x3_wino_kernel(WinoParams p
         for (int i = 0; i < 4; ++i) {
             const float v0 = t[0][i] - t[2][i], v1 = t[1][i] + t[2][i], v2 = t[2][i] - t[1][i], v3 = t[1][i] - t[3][i];
             _Float16 hh, ll;
-            wn_split(v0, hh, ll); ah[0][4 * e + i] = hh; al[0][4 * e + i] = ll;
-            wn_split(v1, hh, ll); ah[1][4 * e + i] = hh; al[1][4 * e + i] = ll;
-            wn_split(v2, hh, ll); ah[2][4 * e + i] = hh; al[2][4 * e + i] = ll;
-            wn_split(v3, hh, ll); ah[3][4 * e + i] = hh; al[3][4 * e + i] = ll;
+            f3_split(v0, hh, ll); ah[0][4 * e + i] = hh; al[0][4 * e + i] = ll;
+            f3_split(v1, hh, ll); ah[1][4 * e + i] = hh; al[1][4 * e + i] = ll;
+            f3_split(v2, hh, ll); ah[2][4 * e + i] = hh; al[2][4 * e + i] = ll;
+            f3_split(v3, hh, ll); ah[3][4 * e + i] = hh; al[3][4 * e + i] = ll;
         }
     };
     auto make_a = [&](unsigned sb, f16x8 (&ah)[4], f16x8 (&al)[4]) {     // a whole tile's fragments (two halves)
@@ -221,7 +196,8 @@ __global__ __launch_bounds__(256, 1) void conv3x3_f16x3_wino_kernel(WinoParams p
         if constexpr (ABL != 3) { patch_read(sb, 1); patch_wait(); }
         transform(ah, al, 1);
     };
-    // the 24 products of one (chunk, m tile); after_pos(c) runs when position c's six are issued
+    // the 24 products of one (chunk, m tile), per position in f3_mac3's order (product-major over the two column tiles);
+    // after_pos(c) runs when position c's six are issued
     auto products = [&](auto m_, const f16x8 (&ah)[4], const f16x8 (&al)[4], auto&& after_pos) {
         constexpr int m = decltype(m_)::value;
 #pragma unroll
@@ -229,16 +205,16 @@ __global__ __launch_bounds__(256, 1) void conv3x3_f16x3_wino_kernel(WinoParams p
             if (m == 0) wait_b_pos(c, fb[c]);
             f16x8 wd[2];
 #pragma unroll
-            for (int j = 0; j < 2; ++j) wd[j] = fb[c][0][j] * (_Float16)0.00048828125f;
+            for (int j = 0; j < 2; ++j) wd[j] = f3_lift_down(fb[c][0][j]);
             if constexpr (ABL == 1) {                    // dev ablation: no products (operands kept alive)
                 asm volatile("" :: "v"(al[c]), "v"(ah[c]), "v"(wd[0]), "v"(wd[1]), "v"(fb[c][1][0]), "v"(fb[c][1][1]), "v"(fb[c][0][0]), "v"(fb[c][0][1]));
             } else {
 #pragma unroll
-            for (int j = 0; j < 2; ++j) acc[c][m][j] = WN_MFMA(al[c], wd[j], acc[c][m][j]);
+            for (int j = 0; j < 2; ++j) acc[c][m][j] = f3_mfma32(al[c], wd[j], acc[c][m][j]);
 #pragma unroll
-            for (int j = 0; j < 2; ++j) acc[c][m][j] = WN_MFMA(ah[c], fb[c][1][j], acc[c][m][j]);
+            for (int j = 0; j < 2; ++j) acc[c][m][j] = f3_mfma32(ah[c], fb[c][1][j], acc[c][m][j]);
 #pragma unroll
-            for (int j = 0; j < 2; ++j) acc[c][m][j] = WN_MFMA(ah[c], fb[c][0][j], acc[c][m][j]);
+            for (int j = 0; j < 2; ++j) acc[c][m][j] = f3_mfma32(ah[c], fb[c][0][j], acc[c][m][j]);
             }
             after_pos(c);
         }
@@ -294,7 +270,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_f16x3_wino_kernel(WinoParams p
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int tl = 32 * i + (r & 3) + 8 * (r >> 2) + 4 * fh;
+                const int tl = 32 * i + f3_crow(r, fh);
                 const float m0 = acc[0][i][j_n][r], m1 = acc[1][i][j_n][r], m2 = acc[2][i][j_n][r], m3 = acc[3][i][j_n][r];
                 X[((wave * 2 + 0) * 64 + tl) * WN_XP + fr] = (m0 + m1) + m2;
                 X[((wave * 2 + 1) * 64 + tl) * WN_XP + fr] = (m1 - m2) - m3;

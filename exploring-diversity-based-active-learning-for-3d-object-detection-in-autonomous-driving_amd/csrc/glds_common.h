@@ -1,21 +1,14 @@
 // The single header of the f16x3 sparse-convolution kernels (spconv_wave.hip, spconv_glds.hip, spconv_rng.hip,
-// spconv_blk.hip, spconv_l0.hip).  Device side: native vector types for inline-asm operands, the f16x3 split and lift, the
+// spconv_blk.hip, spconv_l0.hip).  Device side (the arithmetic itself is al3d_f16x3.h's): the
 // pipelined unit (the three products of a unit in their one summation order), raw LDS reads fused with their waits,
-// counted vmcnt waits, LDS-DMA piece loops, the XCD placement.  Host side: the argument checks and the launch of every entry point.
+// LDS-DMA piece loops, the XCD placement.  Host side: the argument checks and the launch of every entry point.
 #pragma once
 #include "al3d_common.h"
 #include "sp_rows.h"
 #include <stdlib.h>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 gl_f16x2 __attribute__((ext_vector_type(2)));
-typedef float gl_f32x2 __attribute__((ext_vector_type(2)));
-typedef float gl_f32x4 __attribute__((ext_vector_type(4)));     // native vectors: inline-asm register operands
-typedef int gl_i32x4 __attribute__((ext_vector_type(4)));
+typedef int gl_i32x4 __attribute__((ext_vector_type(4)));       // native vectors: inline-asm register operands
 typedef int gl_i32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
 
 static __device__ __attribute__((aligned(256))) float g_glds_zero[128];     // stays zero: source of masked gathers
 static __device__ __attribute__((aligned(256))) int g_glds_neg1[64] = {      // "no neighbour": index source of items past the end
@@ -40,23 +33,10 @@ __device__ __forceinline__ int gl_xcd_slot()
     return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
 }
 
-// ---- the f16x3 arithmetic (see conv2d_f16x3.hip): x = xh + xl' * 2^-11 with xh = f16(x), xl' = f16((x - xh) * 2^11)
-// (sp_split8, sp_rows.h); x * w = xl' * (wh * 2^-11) + xh * wl + xh * wh, three f16 MFMAs into one fp32 accumulator.
-__device__ __forceinline__ void gl_split8_f16(const gl_f32x4& lo, const gl_f32x4& hi, f16x8& ph, f16x8& pl)
-{
-    const float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    uint4 h, l;
-    sp_split8(v, h, l);
-    ph = __builtin_bit_cast(f16x8, h);
-    pl = __builtin_bit_cast(f16x8, l);
-}
-__device__ __forceinline__ f16x8 gl_lift_down(const f16x8& wh)        // wh * 2^-11 (packed multiplies)
-{
-    return wh * (_Float16)0.00048828125f;
-}
-// The three products of a unit are issued SMALLEST FIRST -- al * wd (wd = gl_lift_down(wh)), ah * wl, ah * wh -- into
-// one fp32 accumulator, units in tap, channel-unit order: every structure keeps this order (gl_read_next_mfma below and
-// the kernels' own MFMA triples), which is why they all give the same bits.
+// ---- the f16x3 arithmetic is al3d_f16x3.h's (through sp_rows.h): the pair-wise split f3_split8p, f3_lift_down, and the
+// three products of a unit SMALLEST FIRST -- al * wd, ah * wl, ah * wh (f3_mac3) -- into one fp32 accumulator, units in
+// tap, channel-unit order: every structure keeps this order (gl_read_next_mfma below and the kernels' own triples),
+// which is why they all give the same bits.
 __device__ __forceinline__ f32x16 gl_zero()                           // a zeroed accumulator tile
 {
     f32x16 z;
@@ -77,7 +57,7 @@ __device__ __forceinline__ void gl_lds_read_idx(gl_i32x2& d, unsigned addr)
     asm volatile("ds_read_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(d) : "v"(addr) : "memory");
 }
 // A fragment only (the B fragments of this (tap, chunk) are already in registers)
-__device__ __forceinline__ void gl_lds_read_a(gl_f32x4& lo, gl_f32x4& hi, unsigned a0, unsigned a1)
+__device__ __forceinline__ void gl_lds_read_a(f32x4& lo, f32x4& hi, unsigned a0, unsigned a1)
 {
     asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %3\n\ts_waitcnt lgkmcnt(0)"
                  : "=&v"(lo), "=&v"(hi) : "v"(a0), "v"(a1) : "memory");
@@ -85,7 +65,7 @@ __device__ __forceinline__ void gl_lds_read_a(gl_f32x4& lo, gl_f32x4& hi, unsign
 // A fragment + the B fragments (wh, wl planes) of TN 32-column tiles; OFF = byte offset of the unit in the slab,
 // PL = byte distance of the two planes, 32 rows of a plane = 1 KiB
 template <int TN, int OFF, int PL>
-__device__ __forceinline__ void gl_lds_read_ab(gl_f32x4& lo, gl_f32x4& hi, f16x8 (&wh)[TN], f16x8 (&wl)[TN], unsigned a0,
+__device__ __forceinline__ void gl_lds_read_ab(f32x4& lo, f32x4& hi, f16x8 (&wh)[TN], f16x8 (&wl)[TN], unsigned a0,
                                                unsigned a1, unsigned b)
 {
     static_assert(TN == 1 || TN == 2 || TN == 4, "tile counts of the supported channel pairs");
@@ -111,10 +91,6 @@ __device__ __forceinline__ void gl_lds_read_ab(gl_f32x4& lo, gl_f32x4& hi, f16x8
                      : "v"(a0), "v"(a1), "v"(b), "n"(OFF), "n"(OFF + PL), "n"(OFF + 1024), "n"(OFF + PL + 1024),
                        "n"(OFF + 2048), "n"(OFF + PL + 2048), "n"(OFF + 3072), "n"(OFF + PL + 3072) : "memory");
 }
-template <int N> __device__ __forceinline__ void gl_wait_vm()
-{
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 // N consecutive 1-KiB LDS-DMA pieces (64 lanes x 16 bytes): src is this lane's address in the first piece, dst uniform
 template <int N> __device__ __forceinline__ void gl_dma_pieces(const unsigned char* src, unsigned dst)
 {
@@ -125,11 +101,11 @@ template <int N> __device__ __forceinline__ void gl_dma_pieces(const unsigned ch
 }
 
 // One pipelined unit: the ds_reads of the NEXT unit's A / B fragments interleaved with the MFMAs of the current unit
-// (al * wd, ah * wl, ah * wh per tile; wd lifted by the caller), closed by the lgkmcnt wait -- one asm block, so no
+// (al * wd, ah * wl, ah * wh per tile: the order of f3_mac3; wd lifted by the caller), closed by the lgkmcnt wait -- one asm block, so no
 // register is visible to hipcc while it is in flight.  (`s_nop 1`: the operands come from VALU instructions right
 // before the block -- 2 wait states to an MFMA read.)
 template <int TN, int OFF, int PL>
-__device__ __forceinline__ void gl_read_next_mfma(gl_f32x4& nlo, gl_f32x4& nhi, f16x8 (&nwh)[TN], f16x8 (&nwl)[TN],
+__device__ __forceinline__ void gl_read_next_mfma(f32x4& nlo, f32x4& nhi, f16x8 (&nwh)[TN], f16x8 (&nwl)[TN],
                                                   f32x16 (&acc)[TN], const f16x8& al, const f16x8& ah,
                                                   const f16x8 (&wd)[TN], const f16x8 (&wl)[TN], const f16x8 (&wh)[TN],
                                                   unsigned a0, unsigned a1, unsigned b)

@@ -2,7 +2,7 @@
 //
 // "f32" rows: [n][C] float.  "pair" rows: the SAME 4 C bytes per row, but every group of 8 channels is stored as
 // the two f16 planes the f16x3 arithmetic multiplies with -- 16 bytes xh[8] = f16(x), then 16 bytes
-// xl'[8] = f16((x - xh) * 2^11) (conv2d_f16x3.hip's split).  A consumer's A fragment (8 channels of a row = 32
+// xl'[8] = f16((x - xh) * 2^11) (al3d_f16x3.h: sp_split8 / sp_unsplit8).  A consumer's A fragment (8 channels of a row = 32
 // bytes per lane) is then its MFMA operand pair as loaded: the split -- about two thirds of the VALU work of a
 // gathered (row, tap) unit, repeated for each of the ~16 taps that reference a row -- happens ONCE, in the
 // producer's epilogue.  Products are unchanged (the kernels never multiplied anything but xh and xl'), so a layer
@@ -14,40 +14,11 @@
 // residual is pair rows.
 #pragma once
 #include "al3d_common.h"
+#include "al3d_f16x3.h"
 
 #define SP_IO_IN_PAIR 1
 #define SP_IO_OUT_PAIR 2
 #define SP_IO_RES_PAIR 4
-
-typedef _Float16 sp_f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 sp_f16x2 __attribute__((ext_vector_type(2)));
-typedef float sp_f32x2 __attribute__((ext_vector_type(2)));
-
-// 8 floats -> (xh[8], xl'[8]) as two 16-byte words
-__device__ __forceinline__ void sp_split8(const float (&v)[8], uint4& hi, uint4& lo)
-{
-    unsigned h[4], l[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const sp_f32x2 x = {v[2 * e], v[2 * e + 1]};
-        const sp_f16x2 xh = __builtin_convertvector(x, sp_f16x2);
-        // (x - xh) * 2^11 == fma(xh, -2^11, x * 2^11) exactly (power-of-two scalings, exact residual)
-        const sp_f32x2 r = {__builtin_fmaf((float)xh[0], -2048.0f, x[0] * 2048.0f),
-                            __builtin_fmaf((float)xh[1], -2048.0f, x[1] * 2048.0f)};
-        h[e] = __builtin_bit_cast(unsigned, xh);
-        l[e] = __builtin_bit_cast(unsigned, __builtin_convertvector(r, sp_f16x2));
-    }
-    hi = make_uint4(h[0], h[1], h[2], h[3]);
-    lo = make_uint4(l[0], l[1], l[2], l[3]);
-}
-
-// (xh[8], xl'[8]) -> xh + xl' * 2^-11
-__device__ __forceinline__ void sp_unsplit8(const uint4& hi, const uint4& lo, float (&v)[8])
-{
-    const sp_f16x8 h = __builtin_bit_cast(sp_f16x8, hi), l = __builtin_bit_cast(sp_f16x8, lo);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = __builtin_fmaf((float)l[e], 0.00048828125f, (float)h[e]);
-}
 
 // Epilogue of one 32-row x 32-column C tile that a wave has transposed into `scr` (row pitch EP_PITCH floats):
 // BN scale / shift, residual, ReLU, store -- in either row format.  j = column tile, wrow0 = first row of the wave.

@@ -276,11 +276,11 @@ __global__ __launch_bounds__(64 * (R / 32 + 1)) void sp_conv_blk_kernel(const fl
     if (!consumer) {
         // ================= producer wave: NB - 1 slabs ahead of the consumers
         for (int s = 0; s < NSLAB; ++s) {
-            gl_wait_vm<(NB - 2) * C::SLAB_PIECES>();                         // slab s has landed
+            f3_wait_vm<(NB - 2) * C::SLAB_PIECES>();                         // slab s has landed
             if (!(abl & 1) || s == 0) __builtin_amdgcn_s_barrier();          // ... and slab s-1's buffer is free
             issue_slab(s + NB - 1);
         }
-        gl_wait_vm<0>();
+        f3_wait_vm<0>();
         __builtin_amdgcn_s_barrier();                                        // the consumers' hand-over to their epilogue
         return;
     }
@@ -330,10 +330,8 @@ __global__ __launch_bounds__(64 * (R / 32 + 1)) void sp_conv_blk_kernel(const fl
     auto mfma3 = [&](const f16x8& ah, const f16x8& al, const f16x8 (&wh)[TN], const f16x8 (&wl)[TN]) {
 #pragma unroll
         for (int jn = 0; jn < TN; ++jn) {
-            const f16x8 wd = gl_lift_down(wh[jn]);
-            acc[jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, wd, acc[jn], 0, 0, 0);              // smallest first: the order of glds_common.h
-            acc[jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wl[jn], acc[jn], 0, 0, 0);
-            acc[jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wh[jn], acc[jn], 0, 0, 0);
+            const f16x8 wd = f3_lift_down(wh[jn]);
+            f3_mac3(ah, al, wh[jn], wl[jn], wd, acc[jn]);
         }
     };
 
@@ -373,7 +371,7 @@ __global__ __launch_bounds__(64 * (R / 32 + 1)) void sp_conv_blk_kernel(const fl
                 const int kg = SU >= KG ? u % KG : kgb + u;
                 if (!((live >> t) & 1u)) return;
                 if (pertap && kg == 0) gather_tap(k0 + t, rowa[t], sw[t], ok[t]);
-                gl_f32x4 vh, vl;
+                f32x4 vh, vl;
                 f16x8 wh[TN], wl[TN];
                 gl_lds_read_ab<TN, u * UNIT_BYTES, NROWS * 32>(vh, vl, wh, wl, a_addr(t, kg, 0), a_addr(t, kg, 1), bslab);
                 mfma3(__builtin_bit_cast(f16x8, vh), __builtin_bit_cast(f16x8, vl), wh, wl);
@@ -382,7 +380,7 @@ __global__ __launch_bounds__(64 * (R / 32 + 1)) void sp_conv_blk_kernel(const fl
         } else if constexpr (PIPE) {
             // all SU units of the slab, unit u + 1's fragments read while unit u's products run (a tap without a
             // neighbour in this tile reads the zero row: +0 products)
-            gl_f32x4 vh[2], vl[2];
+            f32x4 vh[2], vl[2];
             f16x8 wh[2][TN], wl[2][TN];
             gl_lds_read_ab<TN, 0, NROWS * 32>(vh[0], vl[0], wh[0], wl[0], a_addr(0, kgb, 0), a_addr(0, kgb, 1), bslab);
             gl_static_for<SU>([&](auto UU) {
@@ -394,7 +392,7 @@ __global__ __launch_bounds__(64 * (R / 32 + 1)) void sp_conv_blk_kernel(const fl
                     const int kgn = SU >= KG ? (u + 1) % KG : kgb + u + 1;
                     f16x8 wd[TN];
 #pragma unroll
-                    for (int jn = 0; jn < TN; ++jn) wd[jn] = gl_lift_down(wh[cur][jn]);
+                    for (int jn = 0; jn < TN; ++jn) wd[jn] = f3_lift_down(wh[cur][jn]);
                     gl_read_next_mfma<TN, (u + 1) * UNIT_BYTES, NROWS * 32>(vh[nxt], vl[nxt], wh[nxt], wl[nxt], acc, al, ah, wd,
                                                                              wl[cur], wh[cur], a_addr(tn, kgn, 0),
                                                                              a_addr(tn, kgn, 1), bslab);

@@ -148,12 +148,12 @@ __global__ __launch_bounds__(64 * (NW + 1)) void sp_conv_glds_kernel(const float
             fill = fill + 1 == NB ? 0 : fill + 1;
         }
         for (int s = 0; s < nslabs; ++s) {
-            gl_wait_vm<(NB - 2) * C::SLAB_PIECES>();                         // slab s has landed
+            f3_wait_vm<(NB - 2) * C::SLAB_PIECES>();                         // slab s has landed
             __builtin_amdgcn_s_barrier();                                    // ... and slab s-1's buffer is free
             issue_slab(fill);
             fill = fill + 1 == NB ? 0 : fill + 1;
         }
-        gl_wait_vm<0>();
+        f3_wait_vm<0>();
         return;
     }
 
@@ -255,7 +255,7 @@ __global__ __launch_bounds__(64 * (NW + 1)) void sp_conv_glds_kernel(const float
 #pragma unroll
     for (int t = 0; t < P - 1; ++t) {
         issue_x(t + 1);
-        gl_wait_vm<1>();                                                     // X(t) (conservative: also G(t-1))
+        f3_wait_vm<1>();                                                     // X(t) (conservative: also G(t-1))
         issue_g(t, t);
     }
 
@@ -271,9 +271,9 @@ __global__ __launch_bounds__(64 * (NW + 1)) void sp_conv_glds_kernel(const float
             const int wgstep = it >> 9;
             if (wgstep >= step_end) break;                                   // belongs to a later slab
             issue_x(j + P);
-            if constexpr (ABL != 4) gl_wait_vm<NP + 1>();                    // X(j+P-1) has landed
+            if constexpr (ABL != 4) f3_wait_vm<NP + 1>();                    // X(j+P-1) has landed
             issue_g(j + P - 1, pslot);
-            if constexpr (ABL != 4) gl_wait_vm<(P - 1) * (NP + 1)>();        // G(j) has landed
+            if constexpr (ABL != 4) f3_wait_vm<(P - 1) * (NP + 1)>();        // G(j) has landed
             const unsigned sA = a_base + slot * SLOT_BYTES;
             const unsigned bB = bslab + (wgstep - sl * SPS) * (UA * UNIT_BYTES);
             const bool newb = !C::BHOLD || wgstep != last_step;               // wave-uniform
@@ -284,7 +284,7 @@ __global__ __launch_bounds__(64 * (NW + 1)) void sp_conv_glds_kernel(const float
                 if (rr != r) return;                                         // wave-uniform: one copy of the body per tile
                 gl_static_for<UA>([&](auto U) {
                     constexpr int ua = decltype(U)::value;
-                    gl_f32x4 lo, hi;
+                    f32x4 lo, hi;
                     if (newb)
                         gl_lds_read_ab<TN, ua * UNIT_BYTES, NROWS * C::WPITCH>(lo, hi, wh[ua], wl[ua], sA + offA[ua][0],
                                                                                sA + offA[ua][1], bB);
@@ -295,14 +295,12 @@ __global__ __launch_bounds__(64 * (NW + 1)) void sp_conv_glds_kernel(const float
                         ah = __builtin_bit_cast(f16x8, lo);
                         al = __builtin_bit_cast(f16x8, hi);
                     } else {
-                        gl_split8_f16(lo, hi, ah, al);
+                        f3_split8p(lo, hi, ah, al);
                     }
 #pragma unroll
                     for (int jn = 0; jn < TN; ++jn) {
-                        const f16x8 wd = gl_lift_down(wh[ua][jn]);
-                        acc[r][jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, wd, acc[r][jn], 0, 0, 0);     // smallest first: the order of glds_common.h
-                        acc[r][jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wl[ua][jn], acc[r][jn], 0, 0, 0);
-                        acc[r][jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wh[ua][jn], acc[r][jn], 0, 0, 0);
+                        const f16x8 wd = f3_lift_down(wh[ua][jn]);
+                        f3_mac3(ah, al, wh[ua][jn], wl[ua][jn], wd, acc[r][jn]);
                     }
                 });
             });
@@ -311,7 +309,7 @@ __global__ __launch_bounds__(64 * (NW + 1)) void sp_conv_glds_kernel(const float
             ++j;
         }
     }
-    gl_wait_vm<0>();                                                         // the tail's dummy gathers
+    f3_wait_vm<0>();                                                         // the tail's dummy gathers
 
     // ---- epilogue (see sp_conv_wave2_kernel): transpose each 32 x 32 C tile through the wave's own LDS
     // (its gather slots: wave-private, no barrier) and move float4s over the contiguous 32-row block

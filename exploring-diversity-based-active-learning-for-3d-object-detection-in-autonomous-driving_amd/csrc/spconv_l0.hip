@@ -497,7 +497,7 @@ extern "C" int al3d_sp_pack_r16_f16x3(const void* planes_f16x2, int cout, void* 
 // =====================================================================================================
 // one tap's fragments (the per-row fallback)
 template <int PLB>
-__device__ __forceinline__ void r16_read_tap(gl_f32x4& alo, gl_f32x4& ahi, f16x8& wh, f16x8& wl, unsigned a0, unsigned a1,
+__device__ __forceinline__ void r16_read_tap(f32x4& alo, f32x4& ahi, f16x8& wh, f16x8& wl, unsigned a0, unsigned a1,
                                              unsigned wb)
 {
     asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %5\n\tds_read_b128 %2, %6\n\tds_read_b128 %3, %6 offset:%7\n\t"
@@ -517,11 +517,11 @@ __device__ __forceinline__ void r16_scr_write8(unsigned addr, float v0, float v1
                     "n"(1 * RB), "n"(2 * RB), "n"(3 * RB), "n"(8 * RB), "n"(9 * RB), "n"(10 * RB), "n"(11 * RB)
                  : "memory");
 }
-__device__ __forceinline__ void r16_lds_read16(gl_f32x4& d, unsigned addr)
+__device__ __forceinline__ void r16_lds_read16(f32x4& d, unsigned addr)
 {
     asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(d) : "v"(addr) : "memory");
 }
-__device__ __forceinline__ void r16_lds_read16x2(gl_f32x4& d0, gl_f32x4& d1, unsigned a0, unsigned a1)
+__device__ __forceinline__ void r16_lds_read16x2(f32x4& d0, f32x4& d1, unsigned a0, unsigned a1)
 {
     asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %3\n\ts_waitcnt lgkmcnt(0)" : "=&v"(d0), "=&v"(d1) : "v"(a0), "v"(a1) : "memory");
 }
@@ -561,7 +561,7 @@ __device__ __forceinline__ void r16_lds_write16(unsigned addr, const gl_i32x4& v
     asm volatile("ds_write_b128 %0, %1" :: "v"(addr), "v"(v) : "memory");
 }
 // A fragments of three taps (all lanes) / B fragments of three taps (the caller masks the lanes of columns >= COUT)
-__device__ __forceinline__ void r16_read_a3(gl_f32x4 (&alo)[3], gl_f32x4 (&ahi)[3], const unsigned (&a0)[3], const unsigned (&a1)[3])
+__device__ __forceinline__ void r16_read_a3(f32x4 (&alo)[3], f32x4 (&ahi)[3], const unsigned (&a0)[3], const unsigned (&a1)[3])
 {
     asm volatile("ds_read_b128 %0, %6\n\tds_read_b128 %1, %7\n\tds_read_b128 %2, %8\n\tds_read_b128 %3, %9\n\t"
                  "ds_read_b128 %4, %10\n\tds_read_b128 %5, %11\n\ts_waitcnt lgkmcnt(0)"
@@ -680,18 +680,16 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 ? 3 : 1)) void sp_conv_r16_kernel
         }
     };
 
-    auto mac = [&](const gl_f32x4& vlo, const gl_f32x4& vhi, const f16x8& wh, const f16x8& wl) __attribute__((always_inline)) {
+    auto mac = [&](const f32x4& vlo, const f32x4& vhi, const f16x8& wh, const f16x8& wl) __attribute__((always_inline)) {
         f16x8 ah, al;
         if (io & SP_IO_IN_PAIR) {
             ah = __builtin_bit_cast(f16x8, vlo);
             al = __builtin_bit_cast(f16x8, vhi);
         } else {
-            gl_split8_f16(vlo, vhi, ah, al);
+            f3_split8p(vlo, vhi, ah, al);
         }
-        const f16x8 wd = gl_lift_down(wh);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, wd, acc, 0, 0, 0);       // smallest first: the order of glds_common.h
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wl, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wh, acc, 0, 0, 0);
+        const f16x8 wd = f3_lift_down(wh);
+        f3_mac3(ah, al, wh, wl, wd, acc);
     };
 
     constexpr int EPV = COUT == 16 ? 8 : 16;
@@ -708,12 +706,12 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 ? 3 : 1)) void sp_conv_r16_kernel
             for (int i = 0; i < (32 * Q4) / 64; ++i) {
                 const int idx = lane + 64 * i;
                 const int rl = idx / Q4, c4 = (idx % Q4) * 4;                 // c4 == ec
-                gl_f32x4 v;
+                f32x4 v;
                 r16_lds_read16(v, scr_base + (rl * EP_PITCH + c4) * 4);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float o = v[e] * sc[e] + sh[e];
-                    if constexpr (RES) o += __builtin_bit_cast(gl_f32x4, rr[s][i < 2 ? i : 0])[e];
+                    if constexpr (RES) o += __builtin_bit_cast(f32x4, rr[s][i < 2 ? i : 0])[e];
                     if (relu) o = o <= 0.f ? 0.f : o;                           // NaN propagates, like torch.relu
                     eo[4 * i + e] = o;
                 }
@@ -723,7 +721,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 ? 3 : 1)) void sp_conv_r16_kernel
             for (int i = 0; i < (32 * Q8) / 64; ++i) {
                 const int grp = lane + 64 * i;
                 const int rl = grp / Q8, c8 = (grp % Q8) * 8;                 // c8 == ec
-                gl_f32x4 a, b;
+                f32x4 a, b;
                 r16_lds_read16x2(a, b, scr_base + (rl * EP_PITCH + c8) * 4, scr_base + (rl * EP_PITCH + c8 + 4) * 4);
                 float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
 #pragma unroll
@@ -735,7 +733,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 ? 3 : 1)) void sp_conv_r16_kernel
                     if (io & SP_IO_RES_PAIR) {
                         sp_unsplit8(__builtin_bit_cast(uint4, rr[s][0]), __builtin_bit_cast(uint4, rr[s][1]), r);
                     } else {
-                        const gl_f32x4 ra = __builtin_bit_cast(gl_f32x4, rr[s][0]), rb = __builtin_bit_cast(gl_f32x4, rr[s][1]);
+                        const f32x4 ra = __builtin_bit_cast(f32x4, rr[s][0]), rb = __builtin_bit_cast(f32x4, rr[s][1]);
                         r[0] = ra[0]; r[1] = ra[1]; r[2] = ra[2]; r[3] = ra[3]; r[4] = rb[0]; r[5] = rb[1]; r[6] = rb[2]; r[7] = rb[3];
                     }
 #pragma unroll
@@ -748,7 +746,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 ? 3 : 1)) void sp_conv_r16_kernel
                 if (io & SP_IO_OUT_PAIR) {
                     uint4 hi, lo;
                     sp_split8(v, hi, lo);
-                    const gl_f32x4 fh4 = __builtin_bit_cast(gl_f32x4, hi), fl4 = __builtin_bit_cast(gl_f32x4, lo);
+                    const f32x4 fh4 = __builtin_bit_cast(f32x4, hi), fl4 = __builtin_bit_cast(f32x4, lo);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { eo[8 * i + e] = fh4[e]; eo[8 * i + 4 + e] = fl4[e]; }
                 } else {
@@ -807,12 +805,12 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 ? 3 : 1)) void sp_conv_r16_kernel
 #pragma unroll
             for (int kx = 0; kx < 3; ++kx) {
                 if (!((tm >> kx & 1u) && !(abl & 4))) continue;                 // wave-uniform
-                gl_f32x4 vlo, vhi;
+                f32x4 vlo, vhi;
                 if (!(abl & 8)) {
                     if (fr < COUT) r16_read_b1<PLB>(bwh, bwl, wb + kx * TAPB);   // columns >= COUT are never stored
                     gl_lds_read_a(vlo, vhi, a0[kx], a1[kx]);                    // ... and this wait covers both
                 } else {
-                    vlo = vhi = gl_f32x4{0.f, 0.f, 0.f, 0.f};
+                    vlo = vhi = f32x4{0.f, 0.f, 0.f, 0.f};
                 }
                 mac(vlo, vhi, bwh, bwl);
             }
@@ -834,7 +832,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 ? 3 : 1)) void sp_conv_r16_kernel
                 const unsigned f = (unsigned)(fr >> 2) & 3u;
                 const unsigned a0 = ok ? sA + (unsigned)fr * 64u + (((2u * fh) ^ f) << 4) : zero_base;
                 const unsigned a1 = ok ? a0 ^ 16u : zero_base + 16u;
-                gl_f32x4 vlo, vhi;
+                f32x4 vlo, vhi;
                 f16x8 bh, bl;
                 r16_read_tap<PLB>(vlo, vhi, bh, bl, a0, a1, wb + kx * TAPB);
                 if (tm >> kx & 1u) mac(vlo, vhi, bh, bl);

@@ -125,11 +125,11 @@ __global__ __launch_bounds__(64 * (NW + 1)) void sp_conv_rng_kernel(const float*
         };
         issue_slab(0);
         for (int s = 0; s < nsteps; ++s) {
-            gl_wait_vm<0>();                                                 // slab s has landed
+            f3_wait_vm<0>();                                                 // slab s has landed
             __builtin_amdgcn_s_barrier();                                    // ... and slab s-1's buffer is free
             issue_slab((s + 1) & 1);
         }
-        gl_wait_vm<0>();
+        f3_wait_vm<0>();
         return;
     }
 
@@ -227,7 +227,7 @@ __global__ __launch_bounds__(64 * (NW + 1)) void sp_conv_rng_kernel(const float*
 #else
         if (len <= CAP) {
 #endif
-            gl_wait_vm<C::WAITN>();                                          // X(t), G(t) have landed (see the order above)
+            f3_wait_vm<C::WAITN>();                                          // X(t), G(t) have landed (see the order above)
             int id[3];
             rg_lds_read_idx3(id[0], id[1], id[2], xa);
             // fragment addresses of the six units (kx, ua) of the item
@@ -245,7 +245,7 @@ __global__ __launch_bounds__(64 * (NW + 1)) void sp_conv_rng_kernel(const float*
                 }
             }
             // software pipeline over the units: unit u+1's fragments are read while unit u's MFMAs run
-            gl_f32x4 vlo[2], vhi[2];
+            f32x4 vlo[2], vhi[2];
             f16x8 wh[2][TN], wl[2][TN];
             gl_lds_read_ab<TN, 0, NROWS * 32>(vlo[0], vhi[0], wh[0], wl[0], ua0[0], ua1[0], bslab);
             gl_static_for<3 * UA>([&](auto U) {
@@ -256,19 +256,19 @@ __global__ __launch_bounds__(64 * (NW + 1)) void sp_conv_rng_kernel(const float*
                     ah = __builtin_bit_cast(f16x8, vlo[cur]);
                     al = __builtin_bit_cast(f16x8, vhi[cur]);
                 } else {
-                    gl_split8_f16(vlo[cur], vhi[cur], ah, al);
+                    f3_split8p(vlo[cur], vhi[cur], ah, al);
                 }
 #pragma unroll
-                for (int jn = 0; jn < TN; ++jn) wd[jn] = gl_lift_down(wh[cur][jn]);
+                for (int jn = 0; jn < TN; ++jn) wd[jn] = f3_lift_down(wh[cur][jn]);
                 if constexpr (u + 1 < 3 * UA) {
                     gl_read_next_mfma<TN, (u + 1) * UNIT_BYTES, NROWS * 32>(vlo[nxt], vhi[nxt], wh[nxt], wl[nxt], acc, al, ah, wd,
                                                                            wl[cur], wh[cur], ua0[u + 1], ua1[u + 1], bslab);
                 } else {
 #pragma unroll
                     for (int jn = 0; jn < TN; ++jn) {
-                        acc[jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, wd[jn], acc[jn], 0, 0, 0);     // smallest first: the order of glds_common.h
-                        acc[jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wl[cur][jn], acc[jn], 0, 0, 0);
-                        acc[jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wh[cur][jn], acc[jn], 0, 0, 0);
+                        acc[jn] = f3_mfma32(al, wd[jn], acc[jn]);     // smallest first: the order of f3_mac3, spelled out (calling
+                        acc[jn] = f3_mfma32(ah, wl[cur][jn], acc[jn]);  // it changes the 64-channel instantiation's machine code)
+                        acc[jn] = f3_mfma32(ah, wh[cur][jn], acc[jn]);
                     }
                 }
             });
@@ -276,7 +276,7 @@ __global__ __launch_bounds__(64 * (NW + 1)) void sp_conv_rng_kernel(const float*
             // irregular group: per-row gather of each tap into rows 0..31 of the slot (drains the queue)
             gl_static_for<3>([&](auto KX) {
                 constexpr int kx = decltype(KX)::value;
-                gl_wait_vm<0>();
+                f3_wait_vm<0>();
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     int idr;
@@ -287,7 +287,7 @@ __global__ __launch_bounds__(64 * (NW + 1)) void sp_conv_rng_kernel(const float*
                     __builtin_amdgcn_global_load_lds((gbl_void*)src, (lds_void*)(size_t)__builtin_amdgcn_readfirstlane(sA + i * 1024),
                                                      16, 0, 0);
                 }
-                gl_wait_vm<0>();
+                f3_wait_vm<0>();
                 int idf;
                 rg_lds_read_idx1(idf, xa + kx * 128);
                 const bool ok = idf >= 0;
@@ -295,7 +295,7 @@ __global__ __launch_bounds__(64 * (NW + 1)) void sp_conv_rng_kernel(const float*
                 const unsigned x = ok ? (unsigned)((2 * fh) ^ ((fr >> 1) & 7)) : 0u;
                 gl_static_for<UA>([&](auto U) {
                     constexpr int ua = decltype(U)::value;
-                    gl_f32x4 vlo, vhi;
+                    f32x4 vlo, vhi;
                     f16x8 wh[TN], wl[TN];
                     gl_lds_read_ab<TN, (kx * UA + ua) * UNIT_BYTES, NROWS * 32>(vlo, vhi, wh, wl, rowa + ((x ^ (4 * ua)) << 4),
                                                                                 rowa + ((x ^ (4 * ua + 1)) << 4), bslab);
@@ -304,14 +304,14 @@ __global__ __launch_bounds__(64 * (NW + 1)) void sp_conv_rng_kernel(const float*
                         ah = __builtin_bit_cast(f16x8, vlo);
                         al = __builtin_bit_cast(f16x8, vhi);
                     } else {
-                        gl_split8_f16(vlo, vhi, ah, al);
+                        f3_split8p(vlo, vhi, ah, al);
                     }
 #pragma unroll
                     for (int jn = 0; jn < TN; ++jn) {
-                        const f16x8 wd = gl_lift_down(wh[jn]);
-                        acc[jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, wd, acc[jn], 0, 0, 0);
-                        acc[jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wl[jn], acc[jn], 0, 0, 0);
-                        acc[jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wh[jn], acc[jn], 0, 0, 0);
+                        const f16x8 wd = f3_lift_down(wh[jn]);
+                        acc[jn] = f3_mfma32(al, wd, acc[jn]);
+                        acc[jn] = f3_mfma32(ah, wl[jn], acc[jn]);
+                        acc[jn] = f3_mfma32(ah, wh[jn], acc[jn]);
                     }
                 });
             });
@@ -322,7 +322,7 @@ __global__ __launch_bounds__(64 * (NW + 1)) void sp_conv_rng_kernel(const float*
         slot = slot + 1 == P ? 0 : slot + 1;
         xe ^= 1;
     }
-    gl_wait_vm<0>();                                                         // the tail's dummy requests
+    f3_wait_vm<0>();                                                         // the tail's dummy requests
 
     // ---- epilogue (as sp_conv_glds_kernel): transpose each 32 x 32 C tile through the wave's own LDS
     float* scr = reinterpret_cast<float*>(smem + C::W_BYTES + wave * C::A_WAVE_BYTES);

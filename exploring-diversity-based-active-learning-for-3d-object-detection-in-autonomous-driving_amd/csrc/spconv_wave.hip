@@ -208,20 +208,8 @@ __global__ __launch_bounds__(256) void sp_conv_wave_kernel(const float* __restri
 __device__ __attribute__((aligned(256))) float g_sw_zero[128];   // stays zero: target of masked gathers
 __device__ int g_sw_neg1 = -1;                                    // "no neighbour" for masked index loads
 
-// ---- f16x3 arithmetic: the split, the lift and the order of a unit's three products are glds_common.h's; here on the
-// operand types of this kernel's plain loads (float4 fragments, uint4 weight pieces)
-__device__ __forceinline__ void sw_split8_f16(const float4& lo, const float4& hi, f16x8& ph, f16x8& pl)
-{
-    const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    uint4 h, l;
-    sp_split8(v, h, l);
-    ph = __builtin_bit_cast(f16x8, h);
-    pl = __builtin_bit_cast(f16x8, l);
-}
-__device__ __forceinline__ uint4 sw_lift_down(const uint4& wh)       // 8 f16 * 2^-11 (packed multiplies)
-{
-    return __builtin_bit_cast(uint4, gl_lift_down(__builtin_bit_cast(f16x8, wh)));
-}
+// ---- f16x3 arithmetic: the split, the lift and the order of a unit's three products are al3d_f16x3.h's, on the operand
+// types of this kernel's plain loads (float4 fragments, uint4 weight pieces)
 
 template <int CIN, int COUT, int NW, int UPS, int P, int NPL>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 8))) void sp_conv_wave2_kernel(const float* __restrict__ fin,
@@ -339,7 +327,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 8)))
         const int uu = (piece >> 1) / (NROWS * NPL);
         *reinterpret_cast<uint4*>(&Ws[buf][uu * UNIT_BYTES + (pl * NROWS + n) * SW_PITCH + 16 * half]) = v;
         if (NPL == 2 && pl == 0)                        // f16x3: third LDS plane = wh * 2^-11, derived once per slab
-            *reinterpret_cast<uint4*>(&Ws[buf][uu * UNIT_BYTES + (2 * NROWS + n) * SW_PITCH + 16 * half]) = sw_lift_down(v);
+            *reinterpret_cast<uint4*>(&Ws[buf][uu * UNIT_BYTES + (2 * NROWS + n) * SW_PITCH + 16 * half]) = f3_lift_down(v);
     };
     auto store_slab = [&](int buf) {
         store_piece(buf, 0, rw0);
@@ -405,7 +393,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 8)))
                             ah = __builtin_bit_cast(f16x8, dlo[slot]);
                             al = __builtin_bit_cast(f16x8, dhi[slot]);
                         } else {
-                            sw_split8_f16(dlo[slot], dhi[slot], ah, al);
+                            f3_split8p(dlo[slot], dhi[slot], ah, al);
                         }
 #pragma unroll
                         for (int j = 0; j < TN; ++j) {
@@ -414,9 +402,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 8)))
                             const f16x8 wh = *reinterpret_cast<const f16x8*>(live ? ub + (0 * NROWS + n) * SW_PITCH + 16 * fh : zrow);
                             const f16x8 wl = *reinterpret_cast<const f16x8*>(live ? ub + (1 * NROWS + n) * SW_PITCH + 16 * fh : zrow);
                             const f16x8 wd = *reinterpret_cast<const f16x8*>(live ? ub + (2 * NROWS + n) * SW_PITCH + 16 * fh : zrow);
-                            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, wd, acc[j], 0, 0, 0);     // smallest first: the order of glds_common.h
-                            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wl, acc[j], 0, 0, 0);
-                            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wh, acc[j], 0, 0, 0);
+                            acc[j] = f3_mfma32(al, wd, acc[j]);     // smallest first: the order of f3_mac3, spelled out (calling it
+                            acc[j] = f3_mfma32(ah, wl, acc[j]);     // changes the 128-column instantiations' machine code)
+                            acc[j] = f3_mfma32(ah, wh, acc[j]);
                         }
                         // hipcc otherwise emits read -> lgkmcnt(0) -> MFMA three times per tile through ONE
                         // register quad, exposing the LDS latency 3*TN times per unit: ask for all B

@@ -127,7 +127,7 @@ __device__ __forceinline__ float tk_window_softmax(f32x16 (&sm)[2], int query, i
 // belongs to the reads (separate asm statements could be scheduled apart from their uses)
 __device__ __forceinline__ void tk_staged_row8(unsigned arr, int row, int s, int h, float (&v)[8])
 {
-    tk_f32x4 lo, hi;
+    f32x4 lo, hi;
     asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %3\n\ts_waitcnt lgkmcnt(0)"
                  : "=&v"(lo), "=&v"(hi)
                  : "v"(arr + tk_arow_off(row, 4 * s + 2 * h)), "v"(arr + tk_arow_off(row, 4 * s + 2 * h + 1))
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(128, Arith::kWavesPerSimd) void tok_window_attentio
     const int c = lane & 31, h = lane >> 5;
     const int ld = 3 * p.C;
     const float* base = p.qkv + (int64_t)win * TK_NT * ld + head * 32;
-    const unsigned stg_base = (unsigned)(size_t)(tk_lds_void*)stg;
+    const unsigned stg_base = (unsigned)(size_t)(lds_void*)stg;
     const TkWinPos w = tk_win_pos(win, p.nwy, p.nwx);
     // the rows first (their latency is the longest: per row group ONE source row address serves the k, q and v pieces), then
     // the position-bias table and the region codes in its shadow -- with the table load in front every item began by
@@ -187,7 +187,7 @@ __global__ __launch_bounds__(128, Arith::kWavesPerSimd) void tok_window_attentio
             for (int arr = 0; arr < 3; ++arr) {
                 const int aoff = live ? (arr == 0 ? p.C : arr == 1 ? 0 : 2 * p.C) : 0;
                 const unsigned dst = __builtin_amdgcn_readfirstlane(stg_base + arr * TK_ABYTES + it * 1024);
-                __builtin_amdgcn_global_load_lds((tk_gbl_void*)(rp + aoff), (tk_lds_void*)(size_t)dst, 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((gbl_void*)(rp + aoff), (lds_void*)(size_t)dst, 16, 0, 0);
             }
         }
     }
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(128, Arith::kWavesPerSimd) void tok_window_attentio
     tk_region_codes(w, p.nwy, p.nwx, p.shift, rycode, rxcode);
 #pragma unroll
     for (int k = 0; k < 2; ++k) { const int t = threadIdx.x + 128 * k; if (t < 176) tbl[t] = tv[k]; }
-    tk_wait_vm<0>();
+    f3_wait_vm<0>();
     __syncthreads();                                   // both waves' shares of k, q and v have landed
     __builtin_amdgcn_s_waitcnt(0xc07f);
     __builtin_amdgcn_wave_barrier();

@@ -1,21 +1,13 @@
 // Pieces shared by the token kernels of both arithmetics (tokens.hip: f16x3, tokens_bf16x6.hip: bf16x6) that do not
-// depend on the operand format: vector typedefs, the zero row, the erf / GELU of the GEMM epilogues, the parameter blocks
+// depend on the operand format: the zero row, the erf / GELU of the GEMM epilogues, the parameter blocks
 // and staged-row layout of the 7 x 7 window kernel, the head-dim-16 attention's parameter block and chunk combine kernel.
-// The attention kernels themselves, with the window geometry and softmax, are in tok_attention.h.
+// The attention kernels themselves, with the window geometry and softmax, are in tok_attention.h.  The vector and
+// address-space typedefs and the counted wait are al3d_f16x3.h's (they carry no arithmetic).
 #pragma once
 #include "al3d_common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float tk_f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void tk_lds_void;
-typedef const __attribute__((address_space(1))) void tk_gbl_void;
+#include "al3d_f16x3.h"
 
 static __device__ __attribute__((aligned(256))) float g_tok_zero[64];     // stays zero: source of rows beyond a matrix / window
-
-template <int N> __device__ __forceinline__ void tk_wait_vm()
-{
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // erf to fp32 rounding level, branch-free: the two minimax pieces of N. Juffa's single-precision erf (x + x P(x^2) below
 // 475/512, 1 - exp(Q(|x|)) above; each < 1 ulp with an exact exp) are both evaluated and one is selected -- the library erff

@@ -10,9 +10,9 @@
 //                                window partition + padding for LN1; the 2x2 neighbourhood for patch merging) and
 //                                written as "pair rows" (sp_rows.h): the f16 split (xh, xl') the f16x3 products
 //                                multiply with, done once per activation instead of once per consuming tile
-//   tok_linear_f16x3_kernel      [M, K] x [N, K]^T in fp32-class f16x3 arithmetic (conv2d_f16x3.hip: three f16
+//   tok_linear_f16x3_kernel      [M, K] x [N, K]^T in fp32-class f16x3 arithmetic (al3d_f16x3.h: three f16
 //                                products per MAC into one fp32 accumulator), both operands by LDS-DMA through a
-//                                3-stage ring exactly as conv2d_f16x3_dma2_kernel, rows addressed directly;
+//                                3-stage ring shared with conv2d_f16x3_dma2_kernel (f3_ring_gemm), rows addressed directly;
 //                                epilogue: bias, exact (erf) GELU, residual, row SCATTER (window order -> token
 //                                order, padding rows dropped), f32 or pair rows out
 //   tok_window_attention_kernel<TkF16x3>  (tok_attention.h, shared with tokens_bf16x6.hip; TkF16x3 below is this
@@ -36,37 +36,10 @@
 #include "tok_attention.h"
 #include <type_traits>
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+#define TK_NS 3             // stages of the token GEMM's ring (f3_ring_gemm, al3d_f16x3.h)
 
-#define TK_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0)
-#define TK_STAGE 16384      // bytes per ring stage: A 8 KB (128 rows x 16 channels f32 / pair) + B 8 KB
-#define TK_BOFF 8192
-#define TK_NS 3
-
-__device__ __forceinline__ int tk_swz(int r) { return (r & 1) | (((r >> 3) & 1) << 1); }
-
-__device__ __forceinline__ void tk_split(float x, _Float16& h, _Float16& l)
-{
-    // x is pinned to ONE rounded fp32 value first: with the producer's arithmetic visible (x = a * b), the compiler may
-    // otherwise feed the residual below from the unrounded product while h rounds the rounded one -- at an f16 tie the
-    // two then disagree by a whole f16 ulp (seen in the fused MLP: GELU output 0.27600098, low part with the wrong sign)
-    asm volatile("" : "+v"(x));
-    h = (_Float16)x;
-    float hf = (float)h;
-    asm volatile("" : "+v"(hf));                                     // the residual is taken against THIS h
-    l = (_Float16)__builtin_fmaf(hf, -2048.0f, x * 2048.0f);         // (x - h) * 2^11 exactly
-}
-__device__ __forceinline__ void tk_split8(const float (&v)[8], f16x8& ph, f16x8& pl)
-{
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { _Float16 a, b; tk_split(v[e], a, b); ph[e] = a; pl[e] = b; }
-}
-__device__ __forceinline__ void tk_split8v(const tk_f32x4& lo, const tk_f32x4& hi, f16x8& ph, f16x8& pl)
-{
-    const float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    tk_split8(v, ph, pl);
-}
-__device__ __forceinline__ f16x8 tk_lift_down(const f16x8& wh) { return wh * (_Float16)0.00048828125f; }
+// Every split of an activation in this file is al3d_f16x3.h's PINNED form: the values split here were computed in the same
+// kernel, with their producer's arithmetic in the compiler's view.
 
 // ------------------------------------------------------------------ LayerNorm over gathered rows
 struct TokLnParams {
@@ -230,34 +203,21 @@ struct TokGemmParams {
     int ntiles, nblocks;
 };
 
-// same XCD-aware (row tile, column block) order as conv2d_f16x3.hip's f3_tile_of_block
-__device__ __forceinline__ bool tk_tile_of_block(const TokGemmParams& p, int& tile, int& nblk)
-{
-    const int id = blockIdx.x, span = 8 * p.nblocks;
-    const int grp = id / span, rem = id - grp * span;
-    nblk = rem >> 3;
-    tile = grp * 8 + (rem & 7);
-    return tile < p.ntiles;
-}
-
-struct TkOps {
-    f16x8 ah[2], al[2], wh[2], wl[2], wd[2];
-};
-
 // IO bit 0: A rows are pair rows; bit 1: write pair rows.  Tile 128 rows x 128 columns x 16 channels per step,
-// four waves of 64 x 64; ring, fragment offsets, asm block and product order of conv2d_f16x3_dma2_kernel.
+// four waves of 64 x 64: the ring GEMM of conv2d_f16x3_dma2_kernel (f3_ring_gemm, al3d_f16x3.h) on matrix rows; same
+// XCD-aware (row tile, column block) order, dealt round-robin.
 template <int IO>
 __global__ __launch_bounds__(256, 2) void tok_linear_f16x3_kernel(TokGemmParams p)
 {
-    __shared__ __attribute__((aligned(1024))) unsigned char smem[TK_NS * TK_STAGE];
+    __shared__ __attribute__((aligned(1024))) unsigned char smem[TK_NS * F3_RING_STAGE];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave & 1, wn = wave >> 1;
     int tile, nblk;
-    if (!tk_tile_of_block(p, tile, nblk)) return;      // padding block of the last group (uniform)
+    if (!f3_tile_of_block(p.ntiles, p.nblocks, false, tile, nblk)) return;      // padding block of the last group (uniform)
     const int m0 = tile * 128, n0 = nblk * 128;
     const int total = p.K >> 4;
-    const unsigned smem_base = (unsigned)(size_t)(tk_lds_void*)smem;
+    const unsigned smem_base = (unsigned)(size_t)(lds_void*)smem;
 
     // DMA side: wave w fetches rows 32 w .. 32 w + 31 and quarter w of the weight tile; lane (jg, sg) of piece i
     // fetches 16-byte chunk sg ^ f(r) of row r = 2 jg + i (source-side swizzle: the LDS side of a DMA is lane-linear)
@@ -267,7 +227,7 @@ __global__ __launch_bounds__(256, 2) void tok_linear_f16x3_kernel(TokGemmParams 
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int r = 2 * jg + i, m = m0 + 32 * wave + r;
-        const int cg = (sg ^ tk_swz(r)) * 4;
+        const int cg = (sg ^ f3_ring_swz(r)) * 4;
         const bool ok = m < p.M;
         abase[i] = reinterpret_cast<const char*>(ok ? p.a + (int64_t)m * p.K + cg : g_tok_zero + cg);
         ainc[i] = ok ? 64u : 0u;
@@ -275,107 +235,24 @@ __global__ __launch_bounds__(256, 2) void tok_linear_f16x3_kernel(TokGemmParams 
     const char* wsrc = reinterpret_cast<const char*>(p.wgt) + (int64_t)nblk * total * 8192 + wave * 2048 + lane * 16;
     int lchunk = 0;
     auto issue = [&](int stage) {
-        const unsigned dst = __builtin_amdgcn_readfirstlane(smem_base + stage * TK_STAGE + wave * 2048);
+        const unsigned dst = __builtin_amdgcn_readfirstlane(smem_base + stage * F3_RING_STAGE + wave * 2048);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
-            __builtin_amdgcn_global_load_lds((tk_gbl_void*)(abase[i] + (size_t)lchunk * ainc[i]),
-                                             (tk_lds_void*)(size_t)(dst + i * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gbl_void*)(abase[i] + (size_t)lchunk * ainc[i]),
+                                             (lds_void*)(size_t)(dst + i * 1024), 16, 0, 0);
         const char* ws = wsrc + (int64_t)lchunk * 8192;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
-            __builtin_amdgcn_global_load_lds((tk_gbl_void*)(ws + i * 1024), (tk_lds_void*)(size_t)(dst + TK_BOFF + i * 1024),
+            __builtin_amdgcn_global_load_lds((gbl_void*)(ws + i * 1024), (lds_void*)(size_t)(dst + F3_RING_BOFF + i * 1024),
                                              16, 0, 0);
         if (lchunk + 1 < total) ++lchunk;              // steps past the end re-fetch the last one: 4 DMAs per step, always
     };
 
+#pragma unroll
+    for (int s = 0; s < TK_NS; ++s) issue(s);          // fill the ring
     f32x16 c00, c01, c10, c11;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { c00[r] = 0.f; c01[r] = 0.f; c10[r] = 0.f; c11[r] = 0.f; }
-
+    f3_ring_gemm<TK_NS, (IO & 1) != 0, f3_split_pinned>(smem_base, total, wm, wn, lane, issue, c00, c01, c10, c11);
     const int fr = lane & 31, fh = lane >> 5;
-    const unsigned offA0 = (unsigned)(wm * 4096 + (fr & 1) * 1024 + (fr >> 1) * 64 + (((2 * fh) ^ tk_swz(fr)) * 16));
-    const unsigned offA1 = (unsigned)(wm * 4096 + (fr & 1) * 1024 + (fr >> 1) * 64 + (((2 * fh + 1) ^ tk_swz(fr)) * 16));
-    const unsigned offB = (unsigned)(TK_BOFF + (wn * 64 + fr) * 32 + ((fh ^ ((fr >> 3) & 1)) * 16));
-
-    TkOps A, B;
-    constexpr bool in_pair = (IO & 1) != 0;
-    auto finish = [&](TkOps& o, const tk_f32x4& r0l, const tk_f32x4& r0h, const tk_f32x4& r1l, const tk_f32x4& r1h) {
-        if constexpr (in_pair) {                         // the 32 bytes of a fragment ARE (xh[8], xl'[8])
-            o.ah[0] = __builtin_bit_cast(f16x8, r0l); o.al[0] = __builtin_bit_cast(f16x8, r0h);
-            o.ah[1] = __builtin_bit_cast(f16x8, r1l); o.al[1] = __builtin_bit_cast(f16x8, r1h);
-        } else {
-            tk_split8v(r0l, r0h, o.ah[0], o.al[0]);
-            tk_split8v(r1l, r1h, o.ah[1], o.al[1]);
-        }
-        o.wd[0] = tk_lift_down(o.wh[0]);
-        o.wd[1] = tk_lift_down(o.wh[1]);
-    };
-
-#pragma unroll
-    for (int s = 0; s < TK_NS; ++s) issue(s);
-    {
-        tk_wait_vm<4 * (TK_NS - 1)>();                 // stage 0
-        __builtin_amdgcn_s_barrier();
-        tk_f32x4 r0l, r0h, r1l, r1h;
-        asm volatile("ds_read_b128 %0, %8\n\t"
-                     "ds_read_b128 %1, %9\n\t"
-                     "ds_read_b128 %2, %8 offset:2048\n\t"
-                     "ds_read_b128 %3, %9 offset:2048\n\t"
-                     "ds_read_b128 %4, %10\n\t"
-                     "ds_read_b128 %5, %10 offset:4096\n\t"
-                     "ds_read_b128 %6, %10 offset:1024\n\t"
-                     "ds_read_b128 %7, %10 offset:5120\n\t"
-                     "s_waitcnt lgkmcnt(0)"
-                     : "=&v"(r0l), "=&v"(r0h), "=&v"(r1l), "=&v"(r1h), "=&v"(A.wh[0]), "=&v"(A.wl[0]), "=&v"(A.wh[1]),
-                       "=&v"(A.wl[1])
-                     : "v"(smem_base + offA0), "v"(smem_base + offA1), "v"(smem_base + offB) : "memory");
-        finish(A, r0l, r0h, r1l, r1h);
-    }
-    int nstage = 1 % TK_NS, fill = 0;
-    auto step = [&](TkOps& cur, TkOps& nxt) {
-        tk_wait_vm<4 * (TK_NS - 2)>();                 // this wave's share of the next stage has landed ...
-        __builtin_amdgcn_s_barrier();                  // ... everyone's has; every wave holds the current stage in registers
-        issue(fill);                                   // -> the current stage's buffer
-        const unsigned sb = smem_base + nstage * TK_STAGE;
-        tk_f32x4 r0l, r0h, r1l, r1h;
-        asm volatile("s_nop 1\n\t"
-                     "ds_read_b128 %0, %22\n\t"
-                     "ds_read_b128 %1, %23\n\t"
-                     "v_mfma_f32_32x32x16_f16 %8, %12, %16, %8\n\t"
-                     "v_mfma_f32_32x32x16_f16 %9, %12, %19, %9\n\t"
-                     "ds_read_b128 %2, %22 offset:2048\n\t"
-                     "ds_read_b128 %3, %23 offset:2048\n\t"
-                     "v_mfma_f32_32x32x16_f16 %10, %14, %16, %10\n\t"
-                     "v_mfma_f32_32x32x16_f16 %11, %14, %19, %11\n\t"
-                     "ds_read_b128 %4, %24\n\t"
-                     "ds_read_b128 %5, %24 offset:4096\n\t"
-                     "v_mfma_f32_32x32x16_f16 %8, %13, %17, %8\n\t"
-                     "v_mfma_f32_32x32x16_f16 %9, %13, %20, %9\n\t"
-                     "ds_read_b128 %6, %24 offset:1024\n\t"
-                     "ds_read_b128 %7, %24 offset:5120\n\t"
-                     "v_mfma_f32_32x32x16_f16 %10, %15, %17, %10\n\t"
-                     "v_mfma_f32_32x32x16_f16 %11, %15, %20, %11\n\t"
-                     "v_mfma_f32_32x32x16_f16 %8, %13, %18, %8\n\t"
-                     "v_mfma_f32_32x32x16_f16 %9, %13, %21, %9\n\t"
-                     "v_mfma_f32_32x32x16_f16 %10, %15, %18, %10\n\t"
-                     "v_mfma_f32_32x32x16_f16 %11, %15, %21, %11\n\t"
-                     "s_waitcnt lgkmcnt(0)"
-                     : "=&v"(r0l), "=&v"(r0h), "=&v"(r1l), "=&v"(r1h), "=&v"(nxt.wh[0]), "=&v"(nxt.wl[0]), "=&v"(nxt.wh[1]),
-                       "=&v"(nxt.wl[1]), "+v"(c00), "+v"(c01), "+v"(c10), "+v"(c11)
-                     : "v"(cur.al[0]), "v"(cur.ah[0]), "v"(cur.al[1]), "v"(cur.ah[1]),                    // 12..15
-                       "v"(cur.wd[0]), "v"(cur.wl[0]), "v"(cur.wh[0]), "v"(cur.wd[1]), "v"(cur.wl[1]), "v"(cur.wh[1]),   // 16..21
-                       "v"(sb + offA0), "v"(sb + offA1), "v"(sb + offB)                                   // 22..24
-                     : "memory");
-        finish(nxt, r0l, r0h, r1l, r1h);
-        nstage = nstage + 1 == TK_NS ? 0 : nstage + 1;
-        fill = fill + 1 == TK_NS ? 0 : fill + 1;
-    };
-    for (int s = 0; s < total; s += 2) {
-        step(A, B);
-        if (s + 1 < total) step(B, A);
-    }
-    tk_wait_vm<0>();                                   // the tail's dummy requests must not outlive the workgroup's LDS
-    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");  // the last MFMAs' results before the VALU reads them
 
     // epilogue: scale / bias / GELU in the C layout, then each 32-row x 64-column half of the wave's tile goes
     // through a wave-private LDS scratch (the ring, free after the barrier) so that a lane holds consecutive channels
@@ -395,7 +272,7 @@ __global__ __launch_bounds__(256, 2) void tok_linear_f16x3_kernel(TokGemmParams 
             const f32x16& acc = *accp[i][j];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int ml = (r & 3) + 8 * (r >> 2) + 4 * fh;
+                const int ml = f3_crow(r, fh);
                 float v = acc[r] * sc + sh;
                 if (p.act == 1) v = tk_gelu(v);
                 else if (p.act == 2) v = v <= 0.f ? 0.f : v;         // NaN propagates, like torch.relu
@@ -516,14 +393,14 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? 2 : 1)) void tok_mlp_f16x3_kern
     float* scr = gs + 3 * C + (threadIdx.x >> 6) * (32 * 33);           // per wave: 32 tokens x 33
     const int tid = threadIdx.x, lane = tid & 63, fr = lane & 31, fh = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned ring_base = (unsigned)(size_t)(tk_lds_void*)ring;
+    const unsigned ring_base = (unsigned)(size_t)(lds_void*)ring;
 
     auto issue = [&](int t) {                                           // hidden tile t -> ring stage t % NS
         const char* src = reinterpret_cast<const char*>(p.image) + (int64_t)t * TILE + wave * 1024 + lane * 16;
         const unsigned dst = __builtin_amdgcn_readfirstlane(ring_base + (t % NS) * TILE + wave * 1024);
 #pragma unroll
         for (int r = 0; r < RPT; ++r)
-            __builtin_amdgcn_global_load_lds((tk_gbl_void*)(src + r * DMA_ROUND), (tk_lds_void*)(size_t)(dst + r * DMA_ROUND), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gbl_void*)(src + r * DMA_ROUND), (lds_void*)(size_t)(dst + r * DMA_ROUND), 16, 0, 0);
     };
     for (int i = tid; i < 32 * p.NT; i += NTHR) b1s[i] = p.bias1[i];
     for (int i = tid; i < C; i += NTHR) { gs[i] = p.gamma[i]; gs[C + i] = p.beta[i]; gs[2 * C + i] = p.bias2[i]; }
@@ -562,7 +439,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? 2 : 1)) void tok_mlp_f16x3_kern
             const int ch = kc * 16 + fh * 8 + e;
             v[e] = (xv[kc][e] - mean) * rstd * gs[ch] + gs[C + ch];
         }
-        tk_split8(v, xh[kc], xl[kc]);
+        f3_split8<f3_split_pinned>(v, xh[kc], xl[kc]);
     }
 
     f32x16 acc[U];
@@ -577,7 +454,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? 2 : 1)) void tok_mlp_f16x3_kern
     for (int t = 0; t < p.NT; ++t) {
         // tiles t .. t + NS - 2 are in flight (fewer at the end): this wave's share of tile t has landed when at most the
         // younger tiles' requests remain
-        if (t + NS - 2 < p.NT) tk_wait_vm<(NS - 2) * RPT>(); else tk_wait_vm<0>();
+        if (t + NS - 2 < p.NT) f3_wait_vm<(NS - 2) * RPT>(); else f3_wait_vm<0>();
         __syncthreads();                                   // ... everyone's has, and nobody reads tile t - 1 any more
         if (t + NS - 1 < p.NT) issue(t + NS - 1);
         const unsigned char* st = ring + (t % NS) * TILE + lane * 16;
@@ -588,10 +465,8 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? 2 : 1)) void tok_mlp_f16x3_kern
         for (int kc = 0; kc < KC; ++kc) {
             const f16x8 wh = *reinterpret_cast<const f16x8*>(st + (kc * 2) * 1024);
             const f16x8 wl = *reinterpret_cast<const f16x8*>(st + (kc * 2 + 1) * 1024);
-            const f16x8 wd = tk_lift_down(wh);
-            h = TK_MFMA(wd, xl[kc], h);
-            h = TK_MFMA(wl, xh[kc], h);
-            h = TK_MFMA(wh, xh[kc], h);
+            const f16x8 wd = f3_lift_down(wh);
+            f3_mac3<false>(xh[kc], xl[kc], wh, wl, wd, h);
         }
         // bias + GELU + split: registers 8 q .. 8 q + 7 are B-operand chunk q (hidden unit (e&3) + 8 (e>>2) + 4 fh + 16 q)
         f16x8 hh[2], hl[2];
@@ -605,7 +480,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? 2 : 1)) void tok_mlp_f16x3_kern
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[4 * g + e] = tk_gelu(h[8 * q + 4 * g + e] * p.scale1 + bb[e]);
             }
-            tk_split8(v, hh[q], hl[q]);
+            f3_split8<f3_split_pinned>(v, hh[q], hl[q]);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u)
@@ -613,10 +488,8 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? 2 : 1)) void tok_mlp_f16x3_kern
             for (int q = 0; q < 2; ++q) {
                 const f16x8 wh = *reinterpret_cast<const f16x8*>(st + W2OFF + ((u * 2 + q) * 2) * 1024);
                 const f16x8 wl = *reinterpret_cast<const f16x8*>(st + W2OFF + ((u * 2 + q) * 2 + 1) * 1024);
-                const f16x8 wd = tk_lift_down(wh);
-                acc[u] = TK_MFMA(wd, hl[q], acc[u]);
-                acc[u] = TK_MFMA(wl, hh[q], acc[u]);
-                acc[u] = TK_MFMA(wh, hh[q], acc[u]);
+                const f16x8 wd = f3_lift_down(wh);
+                f3_mac3<false>(hh[q], hl[q], wh, wl, wd, acc[u]);
             }
     }
 
@@ -626,7 +499,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? 2 : 1)) void tok_mlp_f16x3_kern
     for (int u = 0; u < U; ++u) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int cl = (r & 3) + 8 * (r >> 2) + 4 * fh;             // channel inside the tile; token = fr
+            const int cl = f3_crow(r, fh);                              // channel inside the tile; token = fr
             scr[fr * 33 + cl] = acc[u][r] * p.scale2 + gs[2 * C + 32 * u + cl];
         }
         __builtin_amdgcn_s_waitcnt(0xc07f);
@@ -668,7 +541,7 @@ __global__ __launch_bounds__(768, 3) void tok_mlp16_f16x3_kernel(TokMlpParams p)
     float* gs = b1s + 32 * p.NT;                                        // gamma [C] | beta [C] | bias2 [C]
     const int tid = threadIdx.x, lane = tid & 63, lr = lane & 15, lq = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned ring_base = (unsigned)(size_t)(tk_lds_void*)ring;
+    const unsigned ring_base = (unsigned)(size_t)(lds_void*)ring;
     const int nstage = 2 * p.NT;
 
     auto issue = [&](int st) {                                          // stage st (clamped) -> ring slot st % NS
@@ -677,7 +550,7 @@ __global__ __launch_bounds__(768, 3) void tok_mlp16_f16x3_kernel(TokMlpParams p)
         const unsigned dst = __builtin_amdgcn_readfirstlane(ring_base + (st % NS) * HALF + wave * 1024);
 #pragma unroll
         for (int r = 0; r < DPW; ++r)
-            __builtin_amdgcn_global_load_lds((tk_gbl_void*)(src + r * (NW * 1024)), (tk_lds_void*)(size_t)(dst + r * (NW * 1024)), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gbl_void*)(src + r * (NW * 1024)), (lds_void*)(size_t)(dst + r * (NW * 1024)), 16, 0, 0);
     };
 #pragma unroll
     for (int st = 0; st < NS - 1; ++st) issue(st);                     // the ring fills while the rows are loaded and normalised
@@ -729,13 +602,13 @@ __global__ __launch_bounds__(768, 3) void tok_mlp16_f16x3_kernel(TokMlpParams p)
             const int ch = 32 * ks + 8 * lq + e;
             v[e] = (v[e] - mean) * rstd * gs[ch] + gs[C + ch];
         }
-        tk_split8(v, xh[ks], xl[ks]);
+        f3_split8<f3_split_pinned>(v, xh[ks], xl[ks]);
     }
 
     __builtin_amdgcn_sched_barrier(0);                       // the accumulators start to live only here (the prologue spilled)
-    tk_f32x4 acc[U];
+    f32x4 acc[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) acc[u] = tk_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int u = 0; u < U; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     // the x loads above have been consumed (and with them, in order, the ring's first stages): from here on only the DMA
     // requests of the loop are in flight (DPW per stage and wave)
@@ -746,14 +619,14 @@ __global__ __launch_bounds__(768, 3) void tok_mlp16_f16x3_kernel(TokMlpParams p)
         // correction product wh xl' goes to its own accumulator and is scaled once (2^-11) instead of scaling every wh.
         // (Measured and not kept: a third of the waves one step behind the others, so that the GELU phases of a SIMD's
         // three waves do not coincide -- 0.78 against 0.65 ms.)
-        tk_wait_vm<(NS - 2) * DPW>();                        // this wave's share of stage 2 g has landed ...
+        f3_wait_vm<(NS - 2) * DPW>();                        // this wave's share of stage 2 g has landed ...
         __syncthreads();                                     // ... everyone's has, and nobody reads stage 2 g - 1 any more
         issue(2 * g + NS - 1);
         {
             const unsigned char* st = ring + ((2 * g) % NS) * HALF + lane * 16;
-            tk_f32x4 h[2], hc[2];
+            f32x4 h[2], hc[2];
 #pragma unroll
-            for (int j = 0; j < 2; ++j) { h[j] = tk_f32x4{0.f, 0.f, 0.f, 0.f}; hc[j] = h[j]; }
+            for (int j = 0; j < 2; ++j) { h[j] = f32x4{0.f, 0.f, 0.f, 0.f}; hc[j] = h[j]; }
             f16x8 wh[2], wl[2];
             wh[0] = *reinterpret_cast<const f16x8*>(st);
             wl[0] = *reinterpret_cast<const f16x8*>(st + 1024);
@@ -764,9 +637,9 @@ __global__ __launch_bounds__(768, 3) void tok_mlp16_f16x3_kernel(TokMlpParams p)
                     wl[(i + 1) & 1] = *reinterpret_cast<const f16x8*>(st + ((i + 1) * 2 + 1) * 1024);
                 }
                 const int j = i / KS, ks = i % KS;
-                hc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[i & 1], xl[ks], hc[j], 0, 0, 0);
-                h[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[i & 1], xh[ks], h[j], 0, 0, 0);
-                h[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[i & 1], xh[ks], h[j], 0, 0, 0);
+                hc[j] = f3_mfma16(wh[i & 1], xl[ks], hc[j]);
+                h[j] = f3_mfma16(wl[i & 1], xh[ks], h[j]);
+                h[j] = f3_mfma16(wh[i & 1], xh[ks], h[j]);
             }
             float v[8];
 #pragma unroll
@@ -774,12 +647,12 @@ __global__ __launch_bounds__(768, 3) void tok_mlp16_f16x3_kernel(TokMlpParams p)
                 const float4 b4 = *reinterpret_cast<const float4*>(b1s + 32 * g + 16 * j + 4 * lq);
                 const float bb[4] = {b4.x, b4.y, b4.z, b4.w};
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[4 * j + e] = tk_gelu((h[j][e] + hc[j][e] * 0.00048828125f) * p.scale1 + bb[e]);
+                for (int e = 0; e < 4; ++e) v[4 * j + e] = tk_gelu((h[j][e] + hc[j][e] * F3_UNLIFT) * p.scale1 + bb[e]);
             }
-            tk_split8(v, hh, hl);
+            f3_split8<f3_split_pinned>(v, hh, hl);
         }
         // ---- second half: out^T += W2[:, group g] H^T
-        tk_wait_vm<(NS - 2) * DPW>();
+        f3_wait_vm<(NS - 2) * DPW>();
         __syncthreads();
         issue(2 * g + NS);
         {
@@ -793,14 +666,12 @@ __global__ __launch_bounds__(768, 3) void tok_mlp16_f16x3_kernel(TokMlpParams p)
                     wh[(u + 1) & 1] = *reinterpret_cast<const f16x8*>(st + ((u + 1) * 2) * 1024);
                     wl[(u + 1) & 1] = *reinterpret_cast<const f16x8*>(st + ((u + 1) * 2 + 1) * 1024);
                 }
-                const f16x8 wd = tk_lift_down(wh[u & 1]);
-                acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wd, hl, acc[u], 0, 0, 0);
-                acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[u & 1], hh, acc[u], 0, 0, 0);
-                acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[u & 1], hh, acc[u], 0, 0, 0);
+                const f16x8 wd = f3_lift_down(wh[u & 1]);
+                f3_mac3<false>(hh, hl, wh[u & 1], wl[u & 1], wd, acc[u]);
             }
         }
     }
-    tk_wait_vm<0>();                                         // the tail's dummy requests must not outlive the workgroup's LDS
+    f3_wait_vm<0>();                                         // the tail's dummy requests must not outlive the workgroup's LDS
 
     // ---- out^T tiles are row pieces already: channels 16 u + 4 lq .. + 3 of token lr
     if (live) {
@@ -866,33 +737,22 @@ extern "C" int al3d_tok_mlp_f16x3(float* x, int64_t T, int C, int hidden, const 
 
 // ------------------------------------------------------------------ window attention and head-dim-16 attention (tok_attention.h)
 
-// the f16x3 split of 8 values with the packed conversions of sp_split8 (3 instructions per element instead of 5); the
-// inputs are pinned first (see tk_split: the high part and the residual must see the same rounded fp32 value)
-__device__ __forceinline__ void tk_split8p(float (&v)[8], f16x8& ph, f16x8& pl)
-{
-#pragma unroll
-    for (int e = 0; e < 8; ++e) asm volatile("" : "+v"(v[e]));
-    uint4 hi, lo;
-    sp_split8(v, hi, lo);
-    ph = __builtin_bit_cast(f16x8, hi);
-    pl = __builtin_bit_cast(f16x8, lo);
-}
-
 // The arithmetic of the attention kernels (tok_attention.h): every operand is an activation, split (xh, xl' = residual
-// x 2^11); a product is  xh yh  +  2^-11 (xh yl' + xl' yh)  with the two brackets in separate accumulators.
+// x 2^11); a product is  xh yh  +  2^-11 (xh yl' + xl' yh)  with the two brackets in separate accumulators.  The split
+// (pair-wise, pinned) and the constants are al3d_f16x3.h's.
 struct TkF16x3 {
     struct Frag { f16x8 h, l; };
     struct Acc { f32x16 m, c; };                         // main, 2^-11 correction
     static constexpr int kWavesPerSimd = 3;              // <= 168 registers
     static constexpr bool kPairRows = true;
-    static __device__ __forceinline__ void split8(float (&v)[8], Frag& o) { tk_split8p(v, o.h, o.l); }
+    static __device__ __forceinline__ void split8(float (&v)[8], Frag& o) { f3_split8p_pinned(v, o.h, o.l); }
     static __device__ __forceinline__ void mac(const Frag& a, const Frag& b, Acc& acc)
     {
-        acc.c = TK_MFMA(a.l, b.h, acc.c);
-        acc.c = TK_MFMA(a.h, b.l, acc.c);
-        acc.m = TK_MFMA(a.h, b.h, acc.m);
+        acc.c = f3_mfma32(a.l, b.h, acc.c);
+        acc.c = f3_mfma32(a.h, b.l, acc.c);
+        acc.m = f3_mfma32(a.h, b.h, acc.m);
     }
-    static __device__ __forceinline__ float value(const Acc& a, int r) { return a.m[r] + a.c[r] * 0.00048828125f; }
+    static __device__ __forceinline__ float value(const Acc& a, int r) { return a.m[r] + a.c[r] * F3_UNLIFT; }
     static __device__ __forceinline__ void rescale(Acc& a, float f)
     {
 #pragma unroll
@@ -903,7 +763,7 @@ struct TkF16x3 {
     {
         _Float16 hh[4], ll[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) tk_split(y[e], hh[e], ll[e]);
+        for (int e = 0; e < 4; ++e) f3_split_pinned(y[e], hh[e], ll[e]);
         typedef _Float16 h4 __attribute__((ext_vector_type(4)));
         const h4 vh4 = {hh[0], hh[1], hh[2], hh[3]}, vl4 = {ll[0], ll[1], ll[2], ll[3]};
         char* o = reinterpret_cast<char*>(dst);
@@ -1132,21 +992,14 @@ __global__ __launch_bounds__(C * 4 * WPB, 3) void tok_attn_block_f16x3_kernel(To
 #pragma unroll
             for (int kc = 0; kc < KC; ++kc) {
                 const f16x8 wh = rwh[kc % AB_D2], wl = rwl[kc % AB_D2];
-                const f16x8 wd = tk_lift_down(wh);
+                const f16x8 wd = f3_lift_down(wh);
                 if (kc + 1 < KC) {
                     xfrag(0, kc + 1, fx[(kc + 1) & 1][0], fx[(kc + 1) & 1][1]);
                     xfrag(1, kc + 1, fx[(kc + 1) & 1][2], fx[(kc + 1) & 1][3]);
                 }
                 const f16x8 xh0 = fx[kc & 1][0], xl0 = fx[kc & 1][1], xh1 = fx[kc & 1][2], xl1 = fx[kc & 1][3];
-                if constexpr (WA) {
-                    a0 = TK_MFMA(wd, xl0, a0); a1 = TK_MFMA(wd, xl1, a1);
-                    a0 = TK_MFMA(wl, xh0, a0); a1 = TK_MFMA(wl, xh1, a1);
-                    a0 = TK_MFMA(wh, xh0, a0); a1 = TK_MFMA(wh, xh1, a1);
-                } else {
-                    a0 = TK_MFMA(xl0, wd, a0); a1 = TK_MFMA(xl1, wd, a1);
-                    a0 = TK_MFMA(xh0, wl, a0); a1 = TK_MFMA(xh1, wl, a1);
-                    a0 = TK_MFMA(xh0, wh, a0); a1 = TK_MFMA(xh1, wh, a1);
-                }
+                f3_mac3<!WA>(xh0, xl0, wh, wl, wd, a0);
+                f3_mac3<!WA>(xh1, xl1, wh, wl, wd, a1);
                 issue(kc + AB_D2);
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -1166,7 +1019,7 @@ __global__ __launch_bounds__(C * 4 * WPB, 3) void tok_attn_block_f16x3_kernel(To
 #pragma unroll
                 for (int e = 0; e < 8; ++e) vv[e] = a[8 * s + e] * p.scale_qkv + (role == 0 ? bk[8 * s + e] : bv);
                 f16x8 oh, ol;
-                tk_split8p(vv, oh, ol);
+                f3_split8p_pinned(vv, oh, ol);
                 *reinterpret_cast<f16x8*>(dstb + ((t * 2 + s) * 2) * 1024) = oh;
                 *reinterpret_cast<f16x8*>(dstb + ((t * 2 + s) * 2 + 1) * 1024) = ol;
             }
@@ -1182,11 +1035,9 @@ __global__ __launch_bounds__(C * 4 * WPB, 3) void tok_attn_block_f16x3_kernel(To
         for (int kc = 0; kc < KC; ++kc) {
             const int g = KC + kc;
             const f16x8 wh = rwh[g % AB_D2], wl = rwl[g % AB_D2];
-            const f16x8 wd = tk_lift_down(wh);
+            const f16x8 wd = f3_lift_down(wh);
             if (kc + 1 < KC) xfrag(role, kc + 1, fx[(kc + 1) & 1][0], fx[(kc + 1) & 1][1]);
-            aq = TK_MFMA(wd, fx[kc & 1][1], aq);
-            aq = TK_MFMA(wl, fx[kc & 1][0], aq);
-            aq = TK_MFMA(wh, fx[kc & 1][0], aq);
+            f3_mac3<false>(fx[kc & 1][0], fx[kc & 1][1], wh, wl, wd, aq);
             if (g + AB_D2 < 2 * KC) issue(g + AB_D2);          // the projection's fragments are requested after the attention
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -1197,7 +1048,7 @@ __global__ __launch_bounds__(C * 4 * WPB, 3) void tok_attn_block_f16x3_kernel(To
             float vv[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) vv[e] = (aq[8 * s + e] * p.scale_qkv + bq[8 * s + e]) * p.scale;
-            tk_split8p(vv, qh[s], ql[s]);
+            f3_split8p_pinned(vv, qh[s], ql[s]);
         }
     }
     __syncthreads();                                         // K and V are in LDS; the normalised rows are dead
@@ -1216,16 +1067,16 @@ __global__ __launch_bounds__(C * 4 * WPB, 3) void tok_attn_block_f16x3_kernel(To
             for (int s = 0; s < 2; ++s) {
                 const f16x8 kh = *reinterpret_cast<const f16x8*>(kf + ((i * 2 + s) * 2) * 1024);
                 const f16x8 kl = *reinterpret_cast<const f16x8*>(kf + ((i * 2 + s) * 2 + 1) * 1024);
-                sc[i] = TK_MFMA(kl, qh[s], sc[i]);
-                sc[i] = TK_MFMA(kh, ql[s], sc[i]);
-                sm[i] = TK_MFMA(kh, qh[s], sm[i]);
+                sc[i] = f3_mfma32(kl, qh[s], sc[i]);
+                sc[i] = f3_mfma32(kh, ql[s], sc[i]);
+                sm[i] = f3_mfma32(kh, qh[s], sm[i]);
             }
         // logits -> probabilities in sm[i]: relative position bias from the table, shifted-window regions as a bit mask per
         // query (tok_attention.h)
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) sm[i][r] += sc[i][r] * 0.00048828125f;
+            for (int r = 0; r < 16; ++r) sm[i][r] += sc[i][r] * F3_UNLIFT;
         const float inv = tk_window_softmax(sm, query, fh, tbl, masked, rycode, rxcode);
         f32x16 om, oc;
         zero16(om); zero16(oc);
@@ -1240,17 +1091,17 @@ __global__ __launch_bounds__(C * 4 * WPB, 3) void tok_attn_block_f16x3_kernel(To
 #pragma unroll
                 for (int e = 0; e < 8; ++e) pv[e] = sm[i][8 * s + e];
                 f16x8 ph, pl;
-                tk_split8p(pv, ph, pl);
-                oc = TK_MFMA(vl, ph, oc);
-                oc = TK_MFMA(vh, pl, oc);
-                om = TK_MFMA(vh, ph, om);
+                f3_split8p_pinned(pv, ph, pl);
+                oc = f3_mfma32(vl, ph, oc);
+                oc = f3_mfma32(vh, pl, oc);
+                om = f3_mfma32(vh, ph, om);
             }
         unsigned char* orow = xn + query * PITCH + (4 * hd) * 32;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             _Float16 hh[4], ll[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) tk_split((om[4 * g + e] + oc[4 * g + e] * 0.00048828125f) * inv, hh[e], ll[e]);
+            for (int e = 0; e < 4; ++e) f3_split_pinned((om[4 * g + e] + oc[4 * g + e] * F3_UNLIFT) * inv, hh[e], ll[e]);
             typedef _Float16 h4 __attribute__((ext_vector_type(4)));
             const h4 vh4 = {hh[0], hh[1], hh[2], hh[3]}, vl4 = {ll[0], ll[1], ll[2], ll[3]};
             *reinterpret_cast<uint2*>(orow + g * 32 + 8 * fh) = __builtin_bit_cast(uint2, vh4);
@@ -1278,11 +1129,9 @@ __global__ __launch_bounds__(C * 4 * WPB, 3) void tok_attn_block_f16x3_kernel(To
         for (int kc = 0; kc < KC; ++kc) {
             const int g = 2 * KC + kc;
             const f16x8 wh = rwh[g % AB_D2], wl = rwl[g % AB_D2];
-            const f16x8 wd = tk_lift_down(wh);
+            const f16x8 wd = f3_lift_down(wh);
             if (kc + 1 < KC) xfrag(role, kc + 1, fx[(kc + 1) & 1][0], fx[(kc + 1) & 1][1]);
-            a = TK_MFMA(wd, fx[kc & 1][1], a);
-            a = TK_MFMA(wl, fx[kc & 1][0], a);
-            a = TK_MFMA(wh, fx[kc & 1][0], a);
+            f3_mac3<false>(fx[kc & 1][0], fx[kc & 1][1], wh, wl, wd, a);
             issue(g + AB_D2);
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -1398,7 +1247,7 @@ __global__ __launch_bounds__(256, 2) void tok_patch_embed_f16x3_kernel(TokPatchE
                 const float4 q = *reinterpret_cast<const float4*>(p.img + (((int64_t)b * p.H + (ok ? y : 0)) * p.W + 4 * tx) * 3 + off);
                 v[4 * hlf] = ok ? q.x : 0.f; v[4 * hlf + 1] = ok ? q.y : 0.f; v[4 * hlf + 2] = ok ? q.z : 0.f; v[4 * hlf + 3] = ok ? q.w : 0.f;
             }
-            tk_split8p(v, ph[s], pl[s]);
+            f3_split8p_pinned(v, ph[s], pl[s]);
         }
         f32x16 acc[3];
 #pragma unroll
@@ -1409,9 +1258,7 @@ __global__ __launch_bounds__(256, 2) void tok_patch_embed_f16x3_kernel(TokPatchE
             for (int s = 0; s < 3; ++s) {
                 const f16x8 wh = *reinterpret_cast<const f16x8*>(wf + ((u * 3 + s) * 2) * 1024);
                 const f16x8 wl = *reinterpret_cast<const f16x8*>(wf + ((u * 3 + s) * 2 + 1) * 1024);
-                acc[u] = TK_MFMA(tk_lift_down(wh), pl[s], acc[u]);
-                acc[u] = TK_MFMA(wl, ph[s], acc[u]);
-                acc[u] = TK_MFMA(wh, ph[s], acc[u]);
+                f3_mac3<false>(ph[s], pl[s], wh, wl, f3_lift_down(wh), acc[u]);
             }
         }
         // channel of register r of tile u: 32 u + (r & 3) + 8 (r >> 2) + 4 fh; the other 48 channels of the token sit in lane ^ 32
@@ -1450,7 +1297,7 @@ __global__ __launch_bounds__(256, 2) void tok_patch_embed_f16x3_kernel(TokPatchE
 #pragma unroll
         for (int u = 0; u < 3; ++u) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) scr[fr * 33 + (r & 3) + 8 * (r >> 2) + 4 * fh] = y[u][r];
+            for (int r = 0; r < 16; ++r) scr[fr * 33 + f3_crow(r, fh)] = y[u][r];
             __builtin_amdgcn_s_waitcnt(0xc07f);
             __builtin_amdgcn_wave_barrier();
 #pragma unroll

@@ -16,7 +16,7 @@
 #include "al3d_bf16x6.h"
 #include "tok_attention.h"
 
-// The shared split of a value PINNED to one rounded fp32 value first (tokens.hip's tk_split: with the producer's
+// The shared split of a value PINNED to one rounded fp32 value first (al3d_f16x3.h's f3_split_pinned: with the producer's
 // arithmetic visible the high piece and the residual must see the same value).
 __device__ __forceinline__ void tb_split(float x, __bf16& a, __bf16& b, __bf16& c)
 {

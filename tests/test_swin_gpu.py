@@ -674,3 +674,26 @@ def test_token_gemm_f32_rows_in_pair_rows_out(M, K, N):
     assert torch.equal(pair.view(torch.int32), D.rows_convert(got, True).view(torch.int32))
     back = D.rows_convert(pair, False)
     assert bool(((back - got).abs() <= 2.0 ** -21 * got.abs() + 2.0 ** -35).all())
+
+
+@pytest.mark.parametrize("K", [16, 48, 64, 80])
+def test_token_gemm_equals_the_1x1_dma_conv_bit_for_bit(K):
+    """tok_linear_f16x3_kernel and conv2d_f16x3_dma2_kernel run one ring GEMM (csrc/al3d_f16x3.h, f3_ring_gemm): on the same
+    rows, the same weight image (pack_dma_f16x3, taps = 1), scale and bias, the token GEMM and the 1x1 convolution over the
+    rows seen as a [1, M / 16, 16, K] map give the same bits.  M = 144: two row tiles, the second ragged; N = 136: two
+    column blocks, the second ragged; K = one step, exactly the ring's three stages, an even count above the ring, and an
+    odd count (the loop ends on step(A, B) alone)."""
+    from al3d import detector_ops as D
+    from al3d import token_ops as T
+    M, N = 144, 136
+    g = torch.Generator().manual_seed(1000 + K)
+    a = (torch.randn(M, K, generator=g) * torch.exp(torch.randn(M, K, generator=g))).to(DEV)
+    w = (torch.randn(N, K, generator=g) / K ** 0.5).to(DEV)
+    s = (0.5 + torch.rand(N, generator=g)).to(DEV)
+    b = (torch.randn(N, generator=g) * 0.1).to(DEV)
+    pk = T.PackedLinear(w, b, scale=s)
+    image, sc = pk.packed("f16x3")
+    tok = T.linear(a, pk)
+    conv = D.conv2d_nhwc(a.view(1, M // 16, 16, K), D.F16x3Packed("dma", image, N, 1, K), sc, b, 1, 1, 0, False)
+    assert tok.shape == (M, N) and conv.shape == (1, M // 16, 16, N)
+    assert torch.equal(tok.view(torch.int32), conv.view(M, N).view(torch.int32))

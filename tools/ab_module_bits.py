@@ -152,8 +152,40 @@ def sections():
             return dict(features=out.features, indices=out.indices)
         return run, {}
 
+    def swin_t():
+        """Swin-T on a map that needs padding (patch embedding, the fused attention block and MLP at embed 96 and 192, the
+        token GEMMs of the wider stages), and the token GEMM with pair rows in and out, which no module asks for."""
+        from al3d import detector_ops as D, token_ops as T
+        from al3d.models.swin import SwinTransformer
+        swin = synthetic.seed_modules_(SwinTransformer(embed_dims=96, depths=[2, 2, 6, 2], num_heads=[3, 6, 12, 24], window_size=7,
+                                                       mlp_ratio=4, qkv_bias=True, patch_norm=True, out_indices=[1, 2, 3]), 23)
+        swin = swin.to(DEV).eval()
+        img = randn(2, 96, 160, 3, seed=21)
+        a, pk = randn(300, 192, seed=22), T.PackedLinear(randn(136, 192, seed=24, scale=192 ** -0.5), randn(136, seed=25))
+
+        def run():
+            out = {f"level{i}": o for i, o in enumerate(swin(img))}
+            if D.MATH == "f16x3":
+                out["linear_pair_pair"] = T.linear(D.rows_convert(a, True), pk, a_pair=True, act="gelu", out_pair=True)
+            return out
+        return run, {}
+
+    def opt_in_dense():
+        """The f16x3 dense kernels no default dispatch reaches: the fused residual 3x3 (AL3D_RES=fused) and Winograd."""
+        from al3d import detector_ops as D
+        if D.MATH != "f16x3":
+            return (lambda: {}), {}
+        x, res = randn(2, 21, 37, 64, seed=26), randn(2, 21, 37, 128, seed=27)
+        w, bs, bt = randn(128, 9, 64, seed=28, scale=1.0 / 24), randn(128, seed=29).abs() + 0.5, randn(128, seed=30)
+        wr, sr = D.pack_res3x3(w, bs)
+        ww, sw = D.pack_wino_f16x3(w, bs)
+        return (lambda: dict(res3x3=D.conv3x3_res_nhwc(x, wr, sr, bt, res),
+                             wino=D.conv2d_nhwc(x, ww, sw, bt, 3, 1, 1, True),
+                             wino_pair=D.conv2d_nhwc(x, ww, sw, bt, 3, 1, 1, True, io=D.IO_OUT_PAIR))), {}
+
     return dict(rpn_head=rpn_head, encoder=encoder, decoder=decoder, view_transform=view_transform, center_head=center_head,
-                transfusion_convs=transfusion_convs, seg_head=seg_head, pillar_reader=pillar_reader, spconv_net=spconv_net)
+                transfusion_convs=transfusion_convs, seg_head=seg_head, pillar_reader=pillar_reader, spconv_net=spconv_net,
+                swin_t=swin_t, opt_in_dense=opt_in_dense)
 
 
 def record(out_path):

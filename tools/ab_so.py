@@ -8,7 +8,8 @@ the tree (not under gpurun_out/, which does not travel), then on the box:
     python tools/ab_so.py ab_tmp/lib_a.so ab_tmp/lib_b.so -- python tools/bench_splayers.py 32 al3d_sp_conv_wave2_bf16x6
 
 Each library is copied over csrc/libal3d_hip.so in turn (a, b, a, b) and the command is run as a
-child process; the last lines of its output are printed next to the variant name.
+child process; the last lines of its output are printed next to the variant name.  The first child that
+fails ends the run (exit status = the child's).
 """
 import os
 import shutil
@@ -36,9 +37,13 @@ def main():
                 print(f"== {os.path.basename(lib)} (round {rnd + 1}, rc {out.returncode})")
                 for l in tail:
                     print("   " + l[:300])
+                if out.returncode != 0:                 # a child that failed (or faulted the GPU): start nothing more
+                    print(out.stderr[-2000:])
+                    return out.returncode
+        return 0
     finally:
         shutil.move(keep, target)
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())
