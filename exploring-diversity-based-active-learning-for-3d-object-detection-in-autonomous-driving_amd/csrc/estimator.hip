@@ -22,8 +22,8 @@
 //                     head (128 -> 256 -> 64 -> 1, sigmoid), four boxes per wave pass so a weight is loaded once for four.
 //
 // Built with -ffp-contract=off: the geometry's products and sums round separately, as torch's elementwise ops do.  The
-// point network accumulates its dot products in double on the vector ALUs (f32 weights and activations, explicit fma),
-// the head in f32 with explicit fmaf.  Independent of AL3D_MATH.
+// point network and the head accumulate their dot products in double on the vector ALUs (f32 weights and activations,
+// explicit fma, one rounding per dot product); the sigmoid is taken in double and rounded once.  Independent of AL3D_MATH.
 #include "al3d_common.h"
 
 #define EST_PPL 8                        // points per lane
@@ -353,44 +353,46 @@ __global__ __launch_bounds__(64 * EST_WAVES) void est_head_kernel(
             s_x[wave][g][lane + 64] = __uint_as_float(row[lane + 64]);
         }
         __threadfence_block();
-        float acc[4][EST_GROUP];
+        // in double, as the point network: sequential f32 fmaf chains of 128 and 256 terms left the score one f32 ulp
+        // from the correctly rounded one on some boxes (4.9e-8 from float64 where a float32 torch evaluation is at 1.1e-8)
+        double acc[4][EST_GROUP];
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int g = 0; g < EST_GROUP; ++g) acc[i][g] = C1[lane + 64 * i];
+            for (int g = 0; g < EST_GROUP; ++g) acc[i][g] = (double)C1[lane + 64 * i];
         for (int k = 0; k < EST_C3; ++k) {
-            float w[4];
+            double w[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) w[i] = H1[k * EST_H1 + lane + 64 * i];
+            for (int i = 0; i < 4; ++i) w[i] = (double)H1[k * EST_H1 + lane + 64 * i];
 #pragma unroll
             for (int g = 0; g < EST_GROUP; ++g) {
-                const float x = s_x[wave][g][k];
+                const double x = (double)s_x[wave][g][k];
 #pragma unroll
-                for (int i = 0; i < 4; ++i) acc[i][g] = fmaf(x, w[i], acc[i][g]);
+                for (int i = 0; i < 4; ++i) acc[i][g] = fma(x, w[i], acc[i][g]);
             }
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int g = 0; g < EST_GROUP; ++g) s_h[wave][g][lane + 64 * i] = acc[i][g] > 0.f ? acc[i][g] : 0.f;
+            for (int g = 0; g < EST_GROUP; ++g) s_h[wave][g][lane + 64 * i] = acc[i][g] > 0. ? (float)acc[i][g] : 0.f;
         __threadfence_block();
-        float a2[EST_GROUP];
+        double a2[EST_GROUP];
 #pragma unroll
-        for (int g = 0; g < EST_GROUP; ++g) a2[g] = C2[lane];
+        for (int g = 0; g < EST_GROUP; ++g) a2[g] = (double)C2[lane];
         for (int k = 0; k < EST_H1; ++k) {
-            const float w = H2[k * EST_H2 + lane];
+            const double w = (double)H2[k * EST_H2 + lane];
 #pragma unroll
-            for (int g = 0; g < EST_GROUP; ++g) a2[g] = fmaf(s_h[wave][g][k], w, a2[g]);
+            for (int g = 0; g < EST_GROUP; ++g) a2[g] = fma((double)s_h[wave][g][k], w, a2[g]);
         }
-        const float w3 = H3[lane];
+        const double w3 = (double)H3[lane];
 #pragma unroll
         for (int g = 0; g < EST_GROUP; ++g) {
-            float v = (a2[g] > 0.f ? a2[g] : 0.f) * w3;
+            double v = (a2[g] > 0. ? (double)(float)a2[g] : 0.) * w3;
             for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
             if (g < ng) {
                 const int src = s_list[g0 + g], dst = g0 + g;
                 if (lane == 0) {
-                    out_scores[base + dst] = 1.0f / (1.0f + expf(-(v + C3[0])));
+                    out_scores[base + dst] = (float)(1.0 / (1.0 + exp(-(v + (double)C3[0]))));
                     out_labels[base + dst] = labels[base + src];
                 }
                 if (lane < box_dim) out_boxes[(base + dst) * box_dim + lane] = boxes[(base + src) * box_dim + lane];
