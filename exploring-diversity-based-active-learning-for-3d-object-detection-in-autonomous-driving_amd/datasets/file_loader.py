@@ -229,6 +229,8 @@ class FileSweepLoader:
         }
         if self.with_points:
             ex["voxels"] = v["voxels"]
+        if "point2voxel" in v:              # dynamic voxelizer: each point's row, what DynamicPillarFeatureNet pools by
+            ex["point2voxel"] = v["point2voxel"]
         return ex
 
     def __iter__(self):

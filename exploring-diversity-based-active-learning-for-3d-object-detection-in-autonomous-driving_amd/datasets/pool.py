@@ -127,6 +127,8 @@ class DeviceSweepLoader:
                 ex["voxels"] = v["voxels"]
             if self.keep_points:
                 ex["points"], ex["point_offsets"] = pts, off
+                if "point2voxel" in v:      # dynamic voxelizer: each point's row, what DynamicPillarFeatureNet pools by
+                    ex["point2voxel"] = v["point2voxel"]
             yield ex
 
 

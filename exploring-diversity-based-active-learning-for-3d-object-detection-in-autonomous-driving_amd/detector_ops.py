@@ -1031,7 +1031,8 @@ class DynamicVoxelizer:
         ``Voxelizer.__call__`` (``num_points``: unclipped counts; ``voxel_cap``: the largest per-frame voxel count) plus
         ``point2voxel [P]`` i32 (row or -1) and, on request, ``point_coords [P,3]`` i32 (x, y, z) or -1."""
         if want_voxels:
-            raise NotImplementedError("dynamic voxelization has no padded point slots (there is no dynamic pillar net)")
+            raise NotImplementedError("dynamic voxelization has no padded point slots; the dynamic pillar net "
+                                      "(DynamicPillarFeatureNet) reads points and point2voxel instead")
         points = _dev(points, torch.float32, "points")
         point_offsets = _dev(point_offsets, torch.int64, "point_offsets")
         B = point_offsets.numel() - 1
@@ -1114,8 +1115,9 @@ def build_voxelizer(voxel_cfg, max_batch, device, with_points=False):
     """The voxelizer of a ``voxel_generator`` dict, for the loaders and the pipeline stage."""
     if voxelizer_class(voxel_cfg) is DynamicVoxelizer:
         if with_points:
-            raise NotImplementedError("with_points=True (PointPillars) needs the padded point slots of the hard voxelizer; "
-                                      "there is no dynamic pillar net -- set max_points_in_voxel and max_voxel_num")
+            raise NotImplementedError("with_points=True (PillarFeatureNet) needs the padded point slots of the hard "
+                                      "voxelizer -- set max_points_in_voxel and max_voxel_num, or use the dynamic pillar "
+                                      "net (DynamicPillarFeatureNet) and build the loader with keep_points=True")
         return DynamicVoxelizer(voxel_cfg["range"], voxel_cfg["voxel_size"], reduce="mean", order="zyx", device=device)
     return Voxelizer(voxel_cfg["range"], voxel_cfg["voxel_size"], voxel_cfg["max_points_in_voxel"],
                      voxel_cfg["max_voxel_num"], max_batch=max_batch, device=device)
@@ -1140,6 +1142,7 @@ class PillarNet:
             self.packs.append((w.to(device), scale.to(device), shift.to(device), units))
         self.geom = (float(vx), float(vy), float(x_offset), float(y_offset), int(bool(with_distance)))
         self.channels = self.packs[-1][3]
+        self._status = None                         # device status word of the dynamic calls, allocated on first use
 
     def _args(self, voxels, num_points, coords):
         voxels = _dev(voxels, torch.float32, "voxels").contiguous()
@@ -1171,6 +1174,63 @@ class PillarNet:
         out = torch.empty((batch, ny, nx, self.channels), dtype=torch.float32, device=keep[0].device)
         lib.call("al3d_pillar_net_scatter_f32", *args, batch, ny, nx, _ptr(out), _stream())
         return out
+
+    # ---- all points of every pillar (csrc/pillars_dyn.hip): the dynamic voxelizer's output, no padded slots
+    def _dynamic(self, points, point2voxel, mean, coords, batch, ny, nx, canvas, check, chunk_points=0, max_blocks=0):
+        points = _dev(points, torch.float32, "points").contiguous()
+        point2voxel = _dev(point2voxel.to(torch.int32), torch.int32, "point2voxel").contiguous()
+        mean = _dev(mean, torch.float32, "mean")
+        if mean.dim() != 2 or mean.shape[1] < 3:
+            raise lib.Al3dError(f"PillarNet: mean {tuple(mean.shape)}: need [M, >= 3] rows of the pillar means")
+        if mean.shape[0] <= 1 or mean.stride(1) != 1:       # a row slice of the voxelizer's buffer is read in place
+            mean = mean.contiguous()
+        coords = _dev(coords.to(torch.int32), torch.int32, "coords").contiguous()
+        npts, F = points.shape
+        M = mean.shape[0]
+        if point2voxel.numel() != npts or tuple(coords.shape) != (M, 4):
+            raise lib.Al3dError(f"PillarNet: {npts} points but point2voxel {tuple(point2voxel.shape)}; {M} pillars but "
+                                f"coords {tuple(coords.shape)}")
+        w1, s1, b1, u1 = self.packs[0]
+        if w1.shape[0] != F + 5 + self.geom[4]:
+            raise lib.Al3dError(f"PillarNet: {F} point features need a first layer of {F + 5 + self.geom[4]} inputs, "
+                                f"got {w1.shape[0]}")
+        two = len(self.packs) == 2
+        w2, s2, b2, u2 = self.packs[1] if two else (None, None, None, 0)
+        dev = points.device
+        shape = (batch, ny, nx, self.channels) if canvas else (M, self.channels)
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+        ws = torch.empty(max(lib.load().al3d_pillar_net_dynamic_workspace_bytes(M, u1, int(two)), 1), dtype=torch.uint8,
+                         device=dev)
+        if self._status is None or self._status.device != dev:
+            self._status = torch.zeros((1,), dtype=torch.int32, device=dev)
+        ld = int(mean.stride(0)) if M > 1 else int(mean.shape[1])
+        lib.call("al3d_pillar_net_dynamic_launch_f32", _ptr(points), _ptr(point2voxel), npts, F, _ptr(mean), ld,
+                 _ptr(coords), M, *self.geom, _ptr(w1), _ptr(s1), _ptr(b1), u1, _ptr(w2), _ptr(s2), _ptr(b2), u2,
+                 batch, ny, nx, _ptr(out), int(canvas), _ptr(ws), _ptr(self._status), int(chunk_points), int(max_blocks),
+                 _stream())
+        if check:
+            self.dynamic_status()
+        return out
+
+    def dynamic_status(self):
+        """Read (one D2H) and clear the status word of the dynamic calls; raises when a point2voxel value lay outside
+        [-1, M).  The sweep does not call it: a loader's ``point2voxel`` comes from the dynamic voxelizer, whose own status
+        word was read with that batch's host sync."""
+        if self._status is None:
+            return
+        st = int(self._status.item())
+        if st:
+            self._status.zero_()
+            raise lib.Al3dError("al3d_pillar_net_dynamic_f32: a point2voxel value lies outside [-1, M) (point skipped)")
+
+    def rows_dynamic(self, points, point2voxel, mean, coords, check=True, **shape):
+        """-> [M, C] pillar features over all points: points [N, F], point2voxel [N] (row or -1), mean [M, >= 3] (the
+        dynamic voxelizer's ``feat``), coords [M, 4] (b, z, y, x).  No padded-slot row takes part in the max."""
+        return self._dynamic(points, point2voxel, mean, coords, 0, 1, 1, False, check, **shape)
+
+    def canvas_dynamic(self, points, point2voxel, mean, coords, batch, ny, nx, check=True, **shape):
+        """-> NHWC canvas [batch, ny, nx, C]: ``rows_dynamic`` fused with the scatter (zero where there is no pillar)."""
+        return self._dynamic(points, point2voxel, mean, coords, int(batch), int(ny), int(nx), True, check, **shape)
 
 
 def pillar_scatter(rows, coords, batch, ny, nx):

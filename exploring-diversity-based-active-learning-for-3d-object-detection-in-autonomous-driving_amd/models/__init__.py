@@ -1,7 +1,7 @@
 from .registry import (BACKBONES, DETECTORS, ESTIMATORS, HEADS, LOSSES, NECKS, READERS,
                        ROI_EXTRACTORS, SHARED_HEADS)
 from .builder import build_backbone, build_detector, build_estimator, build_head, build_neck, build_reader
-from .readers import PillarFeatureNet, VoxelFeatureExtractorV3
+from .readers import DynamicPillarFeatureNet, PillarFeatureNet, VoxelFeatureExtractorV3
 from .backbones import FPNSpMiddleResNetFHD, PointPillarsScatter, SparseTensor
 from .necks import RPN
 from .bbox_heads import Head, MultiGroupHead

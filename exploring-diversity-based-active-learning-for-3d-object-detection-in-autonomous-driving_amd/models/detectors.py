@@ -175,7 +175,9 @@ class PointPillars(FPNVoxelNet):
     """PointPillars (det3d/models/detectors/point_pillars.py; BEVFusion's PointPillarsEncoder,
     bevfusion/mmdet3d/models/backbones/pillar_encoder.py:243-258): ``PillarFeatureNet`` reader, ``PointPillarsScatter``
     backbone, dense neck, optional head.  Same call contract as ``FPNVoxelNet``; the example must carry the padded
-    point slots (``voxels``, ``num_points``: the loaders' ``with_points=True``).
+    point slots (``voxels``, ``num_points``: the loaders' ``with_points=True``).  With a ``DynamicPillarFeatureNet``
+    reader it carries ``points``, ``point2voxel`` and ``voxel_features`` of the dynamic voxelizer instead (the loaders'
+    ``keep_points=True``) and every point of every pillar counts (``al3d_pillar_net_dynamic_f32``, canvas form).
 
     ``sparse_stage`` runs the reader and the scatter as ONE launch (``al3d_pillar_net_scatter_f32``): the pillar rows
     go straight into the zeroed NHWC canvas.  There is no rulebook (``prepare`` returns None).  The dense kernels take
@@ -190,15 +192,41 @@ class PointPillars(FPNVoxelNet):
     def extract_feat(self, data):
         """det3d's point_pillars.py:23-39 keys (features, num_voxels, coors, batch_size, input_shape) -> (canvas, [])."""
         nx, ny = int(data["input_shape"][0]), int(data["input_shape"][1])
-        net = self.reader.net(data["features"].device)
-        x = net.canvas(data["features"].float(), data["num_voxels"], data["coors"], int(data["batch_size"]), ny, nx)
+        if self._dynamic():
+            # the dynamic reader's keys: points, point2voxel, mean_features (the voxelizer's feat), coors
+            self._need_points(data.get("points"), data.get("point2voxel"), data.get("mean_features"))
+            net = self.reader.net(data["points"].device)
+            x = net.canvas_dynamic(data["points"], data["point2voxel"], data["mean_features"], data["coors"],
+                                   int(data["batch_size"]), ny, nx, check=False)
+        else:
+            net = self.reader.net(data["features"].device)
+            x = net.canvas(data["features"].float(), data["num_voxels"], data["coors"], int(data["batch_size"]), ny, nx)
         middle = []
         if self.with_neck:
             x = self.neck(x)
             middle.append(NHWCFeature(x, getattr(self.neck, "embedding", None)))
         return x, middle
 
+    def _dynamic(self):
+        from .readers import DynamicPillarFeatureNet
+        return isinstance(self.reader, DynamicPillarFeatureNet)
+
+    @staticmethod
+    def _need_points(points, point2voxel, mean):
+        if points is None or point2voxel is None or mean is None:
+            raise RuntimeError("PointPillars with DynamicPillarFeatureNet needs the batch's points, point2voxel and voxel "
+                               "means: build the loader with keep_points=True on a dynamic voxel_generator "
+                               "(max_points_in_voxel = -1, max_voxel_num = -1)")
+
     def sparse_stage(self, example, book=None, neck_rows=False):       # the canvas is dense: neck_rows does not apply
+        if self._dynamic():
+            pts, p2v, mean = example.get("points"), example.get("point2voxel"), example.get("voxel_features")
+            self._need_points(pts, p2v, mean)
+            nx, ny = int(example["shape"][0][0]), int(example["shape"][0][1])
+            # one fused call; point2voxel was validated with the voxelizer's status word at the loader's host sync
+            x = self.reader.net(pts.device).canvas_dynamic(pts, p2v, mean, example["coordinates"],
+                                                           len(example["num_voxels"]), ny, nx, check=False)
+            return x, []
         voxels = example.get("voxels")
         if voxels is None:
             raise RuntimeError("PointPillars needs the padded point slots: build the loader with with_points=True")

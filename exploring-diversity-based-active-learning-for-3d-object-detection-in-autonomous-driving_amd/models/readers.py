@@ -99,3 +99,24 @@ class PillarFeatureNet(nn.Module):
         if not features.is_cuda:
             raise lib.Al3dError("PillarFeatureNet: device tensors required (no CPU fallback)")
         return self.net(features.device).rows(features.float(), num_voxels, coors)
+
+
+@READERS.register_module
+class DynamicPillarFeatureNet(PillarFeatureNet):
+    """``PillarFeatureNet`` over ALL points of every pillar, for the dynamic voxelizer (``max_points_in_voxel = -1`` /
+    ``max_voxel_num = -1``): no cap per pillar or per frame, so the output is a function of the point set and the
+    parameters alone.  Same constructor, module tree and parameter names: a PointPillars checkpoint loads with
+    ``strict=True``.
+
+    ``forward(points [N,F], point2voxel [N] (row or -1), mean [M,>=3], coors [M,4] (b,z,y,x))`` -> ``[M, C]`` from
+    ``al3d_pillar_net_dynamic_f32`` (csrc/pillars_dyn.hip); ``mean`` is the voxelizer's ``feat`` (reduce = mean).
+    Deviation from the hard reader, on purpose: there are no padded slots, so no ``relu(shift)`` row enters the max
+    reductions -- a pillar that fills all its slots gets the hard reader's bits, a partly filled one can come out lower."""
+
+    def __init__(self, *args, name="DynamicPillarFeatureNet", **kwargs):
+        super().__init__(*args, name=name, **kwargs)
+
+    def forward(self, points, point2voxel, mean, coors):
+        if not points.is_cuda:
+            raise lib.Al3dError("DynamicPillarFeatureNet: device tensors required (no CPU fallback)")
+        return self.net(points.device).rows_dynamic(points.float(), point2voxel, mean, coors)

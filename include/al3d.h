@@ -634,6 +634,38 @@ int al3d_pillar_net_scatter_f32(const float* voxels, const int* num_points, cons
 /* PointPillarsScatter.forward alone (same lines): rows [M,C] -> zeroed canvas [B,ny,nx,C] at (b, y, x) of coords. */
 int al3d_pillar_scatter_nhwc_f32(const float* rows, const int* coords, int M, int C, int B, int ny, int nx,
                                  float* canvas, void* stream);
+/* The same net (det3d/models/readers/pillar_encoder.py:17-152; bevfusion/mmdet3d/models/backbones/pillar_encoder.py:47-182)
+ * over ALL points of every pillar, on the output of al3d_voxelize_dynamic_f32: points [npts,F] f32 in any order,
+ * point2voxel [npts] i32 (row of the point's pillar, or -1: the point is skipped), mean [M,mean_ld] f32 whose columns
+ * 0..2 are the pillar's xyz mean (the voxelizer's feat under reduce = mean: the f32 sum in ascending point index divided
+ * by (float)count; it is read, not recomputed), coords [M,4] i32 (b,z,y,x), unique per pillar.  Decoration, layers, weight
+ * packing and limits (3 <= F <= 10; U1, U2 multiples of 16 in [16,128]; w2 = NULL for one layer) are those of
+ * al3d_pillar_net_f32, expression for expression.  The one deliberate difference: there are no padded slots, so no
+ * relu(b_1) representative row enters either max -- only points count.  A pillar whose slots are all filled gets the bits
+ * of al3d_pillar_net_f32; one with n < P slots filled has hard == max(dynamic, relu(b_1)) after one layer.
+ * The work is parallel over points; pooling is an integer atomic max on the bit pattern of the (non-negative) relu outputs
+ * into a zeroed destination.  A max does not depend on arrival order: the output is bit-identical from run to run, under
+ * any joint permutation of (points, point2voxel), and for every launch shape.
+ * canvas = 0: out is rows [M,C] (C = U2, or U1 with one layer).  canvas = 1: out is the NHWC canvas [B,ny,nx,C], zeroed by a
+ * memset; a pillar whose (b, y, x) lies outside is dropped; bit-identical to canvas = 0 followed by
+ * al3d_pillar_scatter_nhwc_f32.  npts == 0 or M == 0 launches nothing and still zeroes the output.
+ * A point2voxel value outside [-1, M) is never used as an index: bit 0 of *status (device, zeroed by the caller) is set
+ * and the point is skipped.  workspace: al3d_pillar_net_dynamic_workspace_bytes(M, U1, two_layers) bytes (0 for one
+ * layer; may then be NULL).  Stream-ordered: no host synchronisation. */
+int64_t al3d_pillar_net_dynamic_workspace_bytes(int64_t M, int U1, int two_layers);
+int al3d_pillar_net_dynamic_f32(const float* points, const int* point2voxel, int64_t npts, int F, const float* mean,
+                                int mean_ld, const int* coords, int64_t M, float vx, float vy, float x_offset,
+                                float y_offset, int with_distance, const float* w1, const float* s1, const float* b1, int U1,
+                                const float* w2, const float* s2, const float* b2, int U2, int B, int ny, int nx, float* out,
+                                int canvas, void* workspace, int* status, void* stream);
+/* The same call with the launch shape stated: chunk_points consecutive points per wave (0: the default, 64) and at most
+ * max_blocks blocks of four waves (0: the default, 2048).  The result does not depend on either; the tests vary them. */
+int al3d_pillar_net_dynamic_launch_f32(const float* points, const int* point2voxel, int64_t npts, int F, const float* mean,
+                                       int mean_ld, const int* coords, int64_t M, float vx, float vy, float x_offset,
+                                       float y_offset, int with_distance, const float* w1, const float* s1, const float* b1,
+                                       int U1, const float* w2, const float* s2, const float* b2, int U2, int B, int ny,
+                                       int nx, float* out, int canvas, void* workspace, int* status, int chunk_points,
+                                       int max_blocks, void* stream);
 
 /* ---------------------------------------------------------------- camera branch: BEV pooling (f4)
  * bevfusion/mmdet3d/models/vtransforms/base.py:127-163 (`bev_pool`: cell = ((geom - (bx - dx/2)) / dx).long(),

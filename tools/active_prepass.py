@@ -88,10 +88,12 @@ def main():
     anchors = generate_task_anchors(cfg.tasks, cfg.target_assigner.anchor_generators, [1, 128, 128]) \
         if head_cfg is not None and head_cfg.get("type") == "MultiGroupHead" else None
     with_points = cfg.model.get("reader", {}).get("type") == "PillarFeatureNet"
+    # DynamicPillarFeatureNet pools over the batch's points by point2voxel: no padded slots, the points themselves
+    keep_points = cfg.model.get("reader", {}).get("type") == "DynamicPillarFeatureNet"
     if args.synthetic_scenes:
         pool = PoolFrames.from_synthetic(len(mine), dev, seed=1000 + rank)
         loader = DeviceSweepLoader(pool, cfg.voxel_generator, anchors, batch_size=args.batch, device=dev,
-                                   with_points=with_points)
+                                   with_points=with_points, keep_points=keep_points)
     else:
         loader = FileSweepLoader([infos[i] for i in mine], cfg.voxel_generator, anchors, batch_size=args.batch, device=dev,
                                  nsweeps=cfg.nsweeps, root=cfg.data_root,

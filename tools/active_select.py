@@ -139,6 +139,8 @@ def main():
             if head_cfg is not None and head_cfg.get("type") == "MultiGroupHead" else None      # TransFusionHead is anchor-free
         # PillarFeatureNet reads the padded point slots of each pillar, not the voxelizer's mean
         with_points = cfg.model.get("reader", {}).get("type") == "PillarFeatureNet"
+        # DynamicPillarFeatureNet pools over the batch's points by point2voxel: no padded slots, the points themselves
+        dyn_points = cfg.model.get("reader", {}).get("type") == "DynamicPillarFeatureNet"
         if args.synthetic_scenes and cfg.model.get("type") == "BEVFusion":
             # camera+lidar: the lidar batch plus synthetic six-camera images and one calibration rig (configs[4])
             from al3d.datasets import CameraLidarSweepLoader
@@ -162,7 +164,7 @@ def main():
         elif args.synthetic_scenes:
             pool = PoolFrames.from_synthetic(len(mine), dev, seed=1000 + rank)
             loader = DeviceSweepLoader(pool, cfg.voxel_generator, anchors, batch_size=args.batch, device=dev,
-                                       with_points=with_points, keep_points=estimator is not None)
+                                       with_points=with_points, keep_points=estimator is not None or dyn_points)
         else:
             # real files: streamed by the native reader pool one batch ahead of the detector (the reference's
             # 8 DataLoader workers, build_loader.py:23-59), never staged as a whole pool
