@@ -60,9 +60,11 @@ __global__ __launch_bounds__(SC_THREADS) void scan_sums(int* __restrict__ sums, 
     }
 }
 
-__global__ __launch_bounds__(SC_THREADS) void scan_downsweep(const int* __restrict__ in, int64_t n,
+// `in` and `out` may be one buffer (al3d_scan.h), so neither is __restrict__: a thread reads its two items before the
+// block scan's barriers and writes the same two indices after them, and no other thread touches those.
+__global__ __launch_bounds__(SC_THREADS) void scan_downsweep(const int* in, int64_t n,
                                                              const int* __restrict__ sums,
-                                                             int* __restrict__ out)
+                                                             int* out)
 {
     __shared__ int s_wave[SC_THREADS / 64];
     const int64_t i0 = (int64_t)blockIdx.x * SC_ITEMS + 2 * threadIdx.x;
@@ -86,4 +88,17 @@ int al3d_exclusive_scan_i32(const int* in, int* out, int64_t n, void* ws, hipStr
     hipLaunchKernelGGL(scan_downsweep, dim3((unsigned)nb), dim3(SC_THREADS), 0, stream, in, n, sums, out);
     AL3D_CHECK_LAUNCH("exclusive_scan");
     return AL3D_OK;
+}
+
+// The C ABI's view of the scan (include/al3d.h): the same three launches behind argument checks.
+extern "C" int64_t al3d_scan_exclusive_workspace_bytes(int64_t n) { return al3d_scan_workspace_bytes(n > 0 ? n : 0); }
+
+extern "C" int al3d_scan_exclusive_i32(const int* in, int* out, int64_t n, void* workspace, void* stream)
+{
+    AL3D_REQUIRE(n >= 0, "al3d_scan_exclusive_i32: n must be >= 0");
+    if (n == 0) return AL3D_OK;   // nothing to address: an empty device buffer has no pointer
+    AL3D_REQUIRE(in && out && workspace, "al3d_scan_exclusive_i32: null pointer");
+    // the launches take the block count as a 32-bit grid size
+    AL3D_REQUIRE(al3d_cdiv(n, SC_ITEMS) < (1LL << 31), "al3d_scan_exclusive_i32: n too large");
+    return al3d_exclusive_scan_i32(in, out, n, workspace, (hipStream_t)stream);
 }

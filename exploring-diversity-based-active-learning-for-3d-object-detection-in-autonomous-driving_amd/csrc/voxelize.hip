@@ -294,7 +294,8 @@ extern "C" int al3d_voxelize_mean_f32(const float* points, const int64_t* point_
                                       int* num_points, float* voxels, int* num_voxels, int* row_base,
                                       void* stream)
 {
-    AL3D_REQUIRE(points && point_offsets && range_min && voxel_size && grid_size && first_grid &&
+    // an empty batch has no point buffer (a zero-size device allocation is a null pointer): no pass reads `points` then
+    AL3D_REQUIRE((points || npts == 0) && point_offsets && range_min && voxel_size && grid_size && first_grid &&
                      workspace && feat && coords && num_points && num_voxels && row_base,
                  "al3d_voxelize_mean_f32: null pointer");
     AL3D_REQUIRE(B >= 1 && nfeat >= 3 && npts >= 0 && npts < (1LL << 31), "al3d_voxelize_mean_f32: bad sizes");

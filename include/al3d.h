@@ -176,6 +176,16 @@ int al3d_merge_sweeps_f32(const float* raw, const int64_t* file_off, int nfiles,
                           const double* xform, const unsigned char* has_xform, const double* time_lag,
                           float min_distance, float* out, int* out_count, void* workspace, void* stream);
 
+/* ---------------------------------------------------------------- device-wide scan */
+
+/* Exclusive prefix sum of int32 (csrc/scan_kernels.hip): out[i] = in[0] + ... + in[i-1] in wrapping int32 arithmetic.
+ * The scan under the voxelizers, the sweep merge, the sparse rulebook and BEV pooling, exported so that it can be
+ * checked on its own.  in / out [n] i32 (device); out may be the same buffer as in (in place), any other overlap is
+ * not supported.  workspace: al3d_scan_exclusive_workspace_bytes(n) bytes (device), none of it read on entry and
+ * nothing written past it.  n == 0 launches nothing and reads no pointer; n < 0 or a NULL pointer with n > 0 is refused. */
+int64_t al3d_scan_exclusive_workspace_bytes(int64_t n);
+int al3d_scan_exclusive_i32(const int* in, int* out, int64_t n, void* workspace, void* stream);
+
 /* ---------------------------------------------------------------- detector: voxelize */
 
 /* Voxelise a batch of point clouds and reduce each voxel to its mean point (VFE).
@@ -184,7 +194,8 @@ int al3d_merge_sweeps_f32(const float* raw, const int64_t* file_off, int nfiles,
  *  det3d/ops/point_cloud/point_cloud_ops.py:213-296) for every frame of the batch,
  * collate_kitti's concatenation with a batch index (det3d/torchie/parallel/collate.py:118-131)
  * and VoxelFeatureExtractorV3.forward (det3d/models/readers/voxel_encoder.py:206-211).
- *   points        [npts, nfeat] f32, frames concatenated; point_offsets [B+1] i64 (device)
+ *   points        [npts, nfeat] f32, frames concatenated; point_offsets [B+1] i64 (device);
+ *                 points may be NULL when npts == 0 (every frame empty: num_voxels and row_base are zeros)
  *   range_min / voxel_size / grid_size   HOST arrays of 3 (x, y, z)
  *   first_grid    persistent i32 scratch of al3d_voxelize_grid_bytes() bytes, initialised
  *                 once with al3d_voxelize_grid_init(); left clean by every call

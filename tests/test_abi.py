@@ -51,6 +51,22 @@ def test_bad_arguments_fail_loudly_without_gpu():
         lib.call("al3d_combine_maps_f64", None, None, None, 4, 1, 0, 1.0, 1.0, 1.0, 1.0, None, None)
 
 
+def test_scan_entry_checks_its_arguments_without_gpu():
+    """al3d_scan_exclusive_i32 refuses n < 0 and null pointers before any launch; n == 0 is a no-op that touches nothing."""
+    from al3d import lib
+    so = lib.load()
+    p = ctypes.c_void_p(256)
+    assert so.al3d_scan_exclusive_i32(p, p, -1, p, None) == -1 and b"n must be" in so.al3d_last_error()
+    for args in ((None, p, 4, p), (p, None, 4, p), (p, p, 4, None)):
+        assert so.al3d_scan_exclusive_i32(*args, None) == -1
+        assert b"null pointer" in so.al3d_last_error()
+    assert so.al3d_scan_exclusive_i32(None, None, 0, None, None) == 0
+    with pytest.raises(lib.Al3dError):
+        lib.call("al3d_scan_exclusive_i32", None, None, 5, None, None)
+    assert so.al3d_scan_exclusive_workspace_bytes(2048 * 1024 + 1) >= 4 * 1025
+    assert so.al3d_scan_exclusive_workspace_bytes(0) >= 0
+
+
 def test_product_never_imports_oracle():
     """The product package must not reference oracle/ (no CPU fallback)."""
     pkg = os.path.join(ROOT, "exploring-diversity-based-active-learning-for-3d-object-detection-"
