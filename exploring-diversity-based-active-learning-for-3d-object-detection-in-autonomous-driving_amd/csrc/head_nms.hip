@@ -11,6 +11,16 @@
 //
 // Selection order is made deterministic: higher score first, equal scores -> lower anchor
 // index (torch.topk / numpy argsort leave ties unspecified).
+//
+// Box codes.  The kernel body is a template over the anchor width ND (7: x y z w l h r, 9: + vx vy before r), the angle
+// code VEC (1: two residuals rtx, rty and atan2f; 0: one additive residual) and DIR (the direction classifier's fix-up of
+// mg_head.py:839-842,1042-1051).  al3d_head_decode_nms runs <9, 1, false>: the 10-wide vector code of the CBGS configs,
+// nothing else compiled in.  al3d_head_decode_nms_codes runs that same instantiation for the same code without a classifier
+// and <ND, VEC, true> otherwise; there the fix-up reads two logits per box that SURVIVED the NMS and passed the range filter
+// (<= post_max per workgroup), never per anchor, and a task offset of -1 switches it off.
+// GroundBox3dCoderTorch.decode_torch (box_coders.py:106-109) passes linear_dim POSITIONALLY into second_box_decode's
+// bin_loss and never passes norm_velo, so smooth_dim and norm_velo are always False in the reference's decode: there is no
+// (lt + 1) * la or velocity-times-diagonal variant to build, whatever the coder's settings say.
 #include "al3d_common.h"
 #include "al3d_rbox.h"
 
@@ -48,16 +58,20 @@ struct HeadParams {
     int64_t task_soff[8];   // offset of task t inside one sample's block of sbits
     int64_t sample_stride;  // sum of A over the tasks
     int order[8];           // tasks by anchor count, largest first: the long problems of a launch start first
+    // direction classifier (DIR instantiations only): channel offset of task t's na*2 logits, -1 = none
+    int dir_off[8];
+    float direction_offset;
 };
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
-// second_box_decode with encode_angle_to_vector=True, smooth_dim=False, norm_velo=False
-__device__ __forceinline__ void decode_box(const float* __restrict__ t, const float* __restrict__ a,
-                                           float* __restrict__ o)
+// second_box_decode with smooth_dim=False, norm_velo=False: t [ND + VEC], a [ND] -> o [ND]
+template <int ND, int VEC>
+__device__ __forceinline__ void decode_box_t(const float* __restrict__ t, const float* __restrict__ a,
+                                             float* __restrict__ o)
 {
-    const float xa = a[0], ya = a[1], za = a[2], wa = a[3], la = a[4], ha = a[5], vxa = a[6], vya = a[7],
-                ra = a[8];
+    static_assert((ND == 7 || ND == 9) && (VEC == 0 || VEC == 1), "anchor widths 7 and 9, scalar or vector angle");
+    const float xa = a[0], ya = a[1], za = a[2], wa = a[3], la = a[4], ha = a[5], ra = a[ND - 1];
     const float diag = sqrtf(la * la + wa * wa);
     o[0] = t[0] * diag + xa;
     o[1] = t[1] * diag + ya;
@@ -65,9 +79,19 @@ __device__ __forceinline__ void decode_box(const float* __restrict__ t, const fl
     o[3] = expf(t[3]) * wa;
     o[4] = expf(t[4]) * la;
     o[5] = expf(t[5]) * ha;
-    o[6] = t[6] + vxa;
-    o[7] = t[7] + vya;
-    o[8] = atan2f(t[9] + sinf(ra), t[8] + cosf(ra));
+    if (ND == 9) {
+        o[6] = t[6] + a[6];
+        o[7] = t[7] + a[7];
+    }
+    if (VEC) o[ND - 1] = atan2f(t[ND] + sinf(ra), t[ND - 1] + cosf(ra));
+    else o[ND - 1] = t[ND - 1] + ra;
+}
+
+// the 10-wide vector code of the CBGS configs
+__device__ __forceinline__ void decode_box(const float* __restrict__ t, const float* __restrict__ a,
+                                           float* __restrict__ o)
+{
+    decode_box_t<9, 1>(t, a, o);
 }
 
 // Upper bound of the intersection of rectangle P (corners p, area pa) with rectangle Q from Q's bounding box in P's OWN frame
@@ -153,6 +177,7 @@ __global__ __launch_bounds__(256) void head_score_rows_kernel(HeadParams p, int 
     }
 }
 
+template <int ND, int VEC, bool DIR>
 __global__ __launch_bounds__(HN_THREADS) void head_nms_kernel(HeadParams p)
 {
     // 768 problems on 512 resident workgroups (two per CU): the ones that start late should be the short ones
@@ -348,19 +373,20 @@ __global__ __launch_bounds__(HN_THREADS) void head_nms_kernel(HeadParams p)
         }
     }
     // ---- decode the selected boxes, corners, standup boxes
-    float box[9];
-    int my_label = 0;
+    float box[ND];
+    int my_label = 0, my_anchor = 0;
     float my_score = 0.f;
     if (tid < n) {
         const unsigned long long key = key_s[tid];
         const int a = (int)(0xffffffffu - (unsigned)(key & 0xffffffffull));
+        my_anchor = a;
         my_score = __uint_as_float((unsigned)(key >> 32));
         int lab;
         anchor_score(a, lab);
         my_label = lab;
         const int loc = a / tk.na, j = a % tk.na;
-        decode_box(hb + (int64_t)loc * p.CH + tk.box_off + j * 10, tk.anchors + (int64_t)a * 9, box);
-        box_corners(box[0], box[1], box[3], box[4], box[8], cx_s[tid], cy_s[tid]);
+        decode_box_t<ND, VEC>(hb + (int64_t)loc * p.CH + tk.box_off + j * (ND + VEC), tk.anchors + (int64_t)a * ND, box);
+        box_corners(box[0], box[1], box[3], box[4], box[ND - 1], cx_s[tid], cy_s[tid]);
         float x1 = cx_s[tid][0], x2 = x1, y1 = cy_s[tid][0], y2 = y1;
 #pragma unroll
         for (int k = 1; k < 4; ++k) {
@@ -502,8 +528,17 @@ __global__ __launch_bounds__(HN_THREADS) void head_nms_kernel(HeadParams p)
         int dst = 0;
         for (int q = 0; q < kpos; ++q) dst += pass_s[q];
         const int64_t o = ((int64_t)b * p.ntasks + t) * p.post_max + dst;
+        if (DIR && p.dir_off[t] >= 0) {
+            // mg_head.py:842,1042-1051: the NMS above ran on the un-flipped angle, the range filter reads xyz only.
+            // torch.max over the two logits: label 1 iff l1 > l0, or l1 is NaN and l0 is not.
+            const float* d = hb + (int64_t)(my_anchor / tk.na) * p.CH + p.dir_off[t] + (my_anchor % tk.na) * 2;
+            const float l0 = d[0], l1 = d[1];
+            const bool dir_label = l1 > l0 || (l1 != l1 && l0 == l0);
+            const bool opp = ((box[ND - 1] - p.direction_offset) > 0.f) != dir_label;
+            if (opp) box[ND - 1] += 3.14159274f;           // float32 np.pi
+        }
 #pragma unroll
-        for (int k = 0; k < 9; ++k) p.boxes[o * 9 + k] = box[k];
+        for (int k = 0; k < ND; ++k) p.boxes[o * ND + k] = box[k];
         p.scores[o] = my_score;
         p.labels[o] = my_label + tk.label_off;
     }
@@ -521,32 +556,59 @@ extern "C" int64_t al3d_head_decode_nms_workspace_bytes(int B, int ntasks, const
     return (a * (B > 0 ? B : 1) + 1) * 4;
 }
 
-extern "C" int al3d_head_decode_nms(const float* hout, int B, int HW, int CH, int ntasks,
-                                    const float* const* anchors, const int* task_A, const int* task_na,
-                                    const int* task_nc, const int* box_off, const int* cls_off,
-                                    const int* label_off, float score_thresh, float iou_thresh,
-                                    int pre_max, int post_max, const float* range6, float* boxes,
-                                    float* scores, int* labels, int* counts, void* workspace, void* stream)
+// Shared host side of the two entries: argument checks, the score pre-pass and the per-(sample, task) launch.
+// dir_off == nullptr: no classifier argument at all (the old entry).
+static int head_decode_nms_launch(const char* who, const float* hout, int B, int HW, int CH, int ntasks,
+                                  const float* const* anchors, const int* task_A, const int* task_na,
+                                  const int* task_nc, const int* box_off, const int* cls_off,
+                                  const int* label_off, float score_thresh, float iou_thresh,
+                                  int pre_max, int post_max, const float* range6, int n_dim, int vec_encode,
+                                  const int* dir_off, float direction_offset, float* boxes,
+                                  float* scores, int* labels, int* counts, void* workspace, void* stream)
 {
     AL3D_REQUIRE(hout && anchors && task_A && task_na && task_nc && box_off && cls_off && label_off &&
-                     range6 && boxes && scores && labels && counts, "al3d_head_decode_nms: null pointer");
-    AL3D_REQUIRE(ntasks >= 1 && ntasks <= 8, "al3d_head_decode_nms: ntasks must be in [1,8]");
-    AL3D_REQUIRE(pre_max >= 1 && pre_max <= HN_MAXK, "al3d_head_decode_nms: pre_max must be in [1,%d]", HN_MAXK);
-    AL3D_REQUIRE(post_max >= 1 && post_max <= 128, "al3d_head_decode_nms: post_max must be in [1,128]");
+                     range6 && boxes && scores && labels && counts, "%s: null pointer", who);
+    AL3D_REQUIRE(ntasks >= 1 && ntasks <= 8, "%s: ntasks must be in [1,8]", who);
+    AL3D_REQUIRE(pre_max >= 1 && pre_max <= HN_MAXK, "%s: pre_max must be in [1,%d]", who, HN_MAXK);
+    AL3D_REQUIRE(post_max >= 1 && post_max <= 128, "%s: post_max must be in [1,128]", who);
+    AL3D_REQUIRE(n_dim == 7 || n_dim == 9, "%s: n_dim must be 7 or 9", who);
+    AL3D_REQUIRE(vec_encode == 0 || vec_encode == 1, "%s: vec_encode must be 0 or 1", who);
+    const int code = n_dim + vec_encode;
     HeadParams p;
     p.hout = hout; p.B = B; p.HW = HW; p.CH = CH; p.ntasks = ntasks;
     p.score_thresh = score_thresh; p.iou_thresh = iou_thresh; p.pre_max = pre_max; p.post_max = post_max;
     for (int k = 0; k < 6; ++k) p.range[k] = range6[k];
+    for (int t = 0; t < 8; ++t) p.dir_off[t] = -1;
+    p.direction_offset = direction_offset;
+    bool with_dir = false;
     for (int t = 0; t < ntasks; ++t) {
-        AL3D_REQUIRE(task_A[t] == HW * task_na[t], "al3d_head_decode_nms: task %d anchor count mismatch", t);
+        AL3D_REQUIRE(task_na[t] >= 1 && task_nc[t] >= 1 && box_off[t] >= 0 && cls_off[t] >= 0,
+                     "%s: task %d: na, nc must be positive and the offsets non-negative", who, t);
+        AL3D_REQUIRE(task_A[t] == HW * task_na[t], "%s: task %d anchor count mismatch", who, t);
         p.task[t].anchors = anchors[t]; p.task[t].A = task_A[t]; p.task[t].na = task_na[t];
         p.task[t].nc = task_nc[t]; p.task[t].box_off = box_off[t]; p.task[t].cls_off = cls_off[t];
         p.task[t].label_off = label_off[t];
-        AL3D_REQUIRE(box_off[t] + task_na[t] * 10 <= CH && cls_off[t] + task_na[t] * task_nc[t] <= CH,
-                     "al3d_head_decode_nms: task %d channel window exceeds CH", t);
+        AL3D_REQUIRE(anchors[t], "%s: null pointer", who);
+        AL3D_REQUIRE(box_off[t] + task_na[t] * code <= CH && cls_off[t] + task_na[t] * task_nc[t] <= CH,
+                     "%s: task %d channel window exceeds CH", who, t);
+        if (dir_off) {
+            const int d = dir_off[t];
+            AL3D_REQUIRE(d >= -1, "%s: task %d dir_off must be -1 or a channel offset", who, t);
+            AL3D_REQUIRE((d >= 0) == (dir_off[0] >= 0), "%s: dir_off mixes -1 and channel offsets across tasks", who);
+            if (d >= 0) {
+                const int dw = task_na[t] * 2;
+                AL3D_REQUIRE(d + dw <= CH, "%s: task %d direction window exceeds CH", who, t);
+                AL3D_REQUIRE(d + dw <= box_off[t] || d >= box_off[t] + task_na[t] * code,
+                             "%s: task %d direction window overlaps its box window", who, t);
+                AL3D_REQUIRE(d + dw <= cls_off[t] || d >= cls_off[t] + task_na[t] * task_nc[t],
+                             "%s: task %d direction window overlaps its class window", who, t);
+                with_dir = true;
+            }
+            p.dir_off[t] = d;
+        }
     }
     p.boxes = boxes; p.scores = scores; p.labels = labels; p.counts = counts;
-    AL3D_REQUIRE(workspace, "al3d_head_decode_nms: null workspace");
+    AL3D_REQUIRE(workspace, "%s: null workspace", who);
     p.sbits = (unsigned*)workspace;
     int64_t soff = 0;
     int amax = 0;
@@ -568,10 +630,47 @@ extern "C" int al3d_head_decode_nms(const float* hout, int B, int HW, int CH, in
     else
         hipLaunchKernelGGL(head_score_kernel, dim3((unsigned)al3d_cdiv(amax, 256), (unsigned)ntasks, (unsigned)B), dim3(256),
                            0, (hipStream_t)stream, p);
-    hipLaunchKernelGGL(head_nms_kernel, dim3((unsigned)(B * ntasks)), dim3(HN_THREADS), 0,
-                       (hipStream_t)stream, p);
+    const dim3 grid((unsigned)(B * ntasks)), block(HN_THREADS);
+    // the CBGS code without a classifier is ONE instantiation whichever entry asks for it
+    if (n_dim == 9 && vec_encode && !with_dir)
+        hipLaunchKernelGGL((head_nms_kernel<9, 1, false>), grid, block, 0, (hipStream_t)stream, p);
+    else if (n_dim == 9 && vec_encode)
+        hipLaunchKernelGGL((head_nms_kernel<9, 1, true>), grid, block, 0, (hipStream_t)stream, p);
+    else if (n_dim == 9)
+        hipLaunchKernelGGL((head_nms_kernel<9, 0, true>), grid, block, 0, (hipStream_t)stream, p);
+    else if (vec_encode)
+        hipLaunchKernelGGL((head_nms_kernel<7, 1, true>), grid, block, 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL((head_nms_kernel<7, 0, true>), grid, block, 0, (hipStream_t)stream, p);
     AL3D_CHECK_LAUNCH("head_nms_kernel");
     return AL3D_OK;
+}
+
+extern "C" int al3d_head_decode_nms(const float* hout, int B, int HW, int CH, int ntasks,
+                                    const float* const* anchors, const int* task_A, const int* task_na,
+                                    const int* task_nc, const int* box_off, const int* cls_off,
+                                    const int* label_off, float score_thresh, float iou_thresh,
+                                    int pre_max, int post_max, const float* range6, float* boxes,
+                                    float* scores, int* labels, int* counts, void* workspace, void* stream)
+{
+    return head_decode_nms_launch("al3d_head_decode_nms", hout, B, HW, CH, ntasks, anchors, task_A, task_na, task_nc,
+                                  box_off, cls_off, label_off, score_thresh, iou_thresh, pre_max, post_max, range6, 9, 1,
+                                  nullptr, 0.f, boxes, scores, labels, counts, workspace, stream);
+}
+
+extern "C" int al3d_head_decode_nms_codes(const float* hout, int B, int HW, int CH, int ntasks,
+                                          const float* const* anchors, const int* task_A, const int* task_na,
+                                          const int* task_nc, const int* box_off, const int* cls_off,
+                                          const int* label_off, float score_thresh, float iou_thresh,
+                                          int pre_max, int post_max, const float* range6, int n_dim, int vec_encode,
+                                          const int* dir_off, float direction_offset, float* boxes,
+                                          float* scores, int* labels, int* counts, void* workspace, void* stream)
+{
+    AL3D_REQUIRE(dir_off, "al3d_head_decode_nms_codes: null pointer");
+    return head_decode_nms_launch("al3d_head_decode_nms_codes", hout, B, HW, CH, ntasks, anchors, task_A, task_na,
+                                  task_nc, box_off, cls_off, label_off, score_thresh, iou_thresh, pre_max, post_max,
+                                  range6, n_dim, vec_encode, dir_off, direction_offset, boxes, scores, labels, counts,
+                                  workspace, stream);
 }
 
 // Stand-alone decode (GroundBox3dCoderTorch.decode_torch, det3d/core/bbox/box_coders.py:106-109).
@@ -594,5 +693,38 @@ extern "C" int al3d_box_decode_f32(const float* enc, const float* anchors, int64
     hipLaunchKernelGGL(box_decode_kernel, dim3((unsigned)al3d_cdiv(n, 256)), dim3(256), 0,
                        (hipStream_t)stream, enc, anchors, n, out);
     AL3D_CHECK_LAUNCH("box_decode_kernel");
+    return AL3D_OK;
+}
+
+// Stand-alone decode of the other codes: enc [n, n_dim + vec_encode], anchors [n, n_dim] -> [n, n_dim].
+template <int ND, int VEC>
+__global__ void box_decode_codes_kernel(const float* __restrict__ enc, const float* __restrict__ anc, int64_t n,
+                                        float* __restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float o[ND];
+    decode_box_t<ND, VEC>(enc + (ND + VEC) * i, anc + ND * i, o);
+#pragma unroll
+    for (int k = 0; k < ND; ++k) out[ND * i + k] = o[k];
+}
+
+extern "C" int al3d_box_decode_codes_f32(const float* enc, const float* anchors, int64_t n, int n_dim, int vec_encode,
+                                         float* out, void* stream)
+{
+    AL3D_REQUIRE(n_dim == 7 || n_dim == 9, "al3d_box_decode_codes_f32: n_dim must be 7 or 9");
+    AL3D_REQUIRE(vec_encode == 0 || vec_encode == 1, "al3d_box_decode_codes_f32: vec_encode must be 0 or 1");
+    AL3D_REQUIRE(n >= 0 && (n == 0 || (enc && anchors && out)), "al3d_box_decode_codes_f32: bad arguments");
+    if (n == 0) return AL3D_OK;
+    const dim3 grid((unsigned)al3d_cdiv(n, 256)), block(256);
+    if (n_dim == 9 && vec_encode)
+        hipLaunchKernelGGL((box_decode_codes_kernel<9, 1>), grid, block, 0, (hipStream_t)stream, enc, anchors, n, out);
+    else if (n_dim == 9)
+        hipLaunchKernelGGL((box_decode_codes_kernel<9, 0>), grid, block, 0, (hipStream_t)stream, enc, anchors, n, out);
+    else if (vec_encode)
+        hipLaunchKernelGGL((box_decode_codes_kernel<7, 1>), grid, block, 0, (hipStream_t)stream, enc, anchors, n, out);
+    else
+        hipLaunchKernelGGL((box_decode_codes_kernel<7, 0>), grid, block, 0, (hipStream_t)stream, enc, anchors, n, out);
+    AL3D_CHECK_LAUNCH("box_decode_codes_kernel");
     return AL3D_OK;
 }

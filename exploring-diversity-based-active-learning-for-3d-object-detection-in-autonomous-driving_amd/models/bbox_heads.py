@@ -1,7 +1,11 @@
-"""CBGS multi-group anchor head (reference det3d/models/bbox_heads/mg_head.py:199-231,386-533,
-697-1085).  Parameter names match (``tasks.<t>.conv_{box,cls}.{weight,bias}``); the twelve 1x1
-convs run as ONE fused GEMM on the matrix cores and decode/score/top-k/rotated-NMS run in one
-device kernel per batch (no host round trips per task and sample)."""
+"""Multi-group anchor head (reference det3d/models/bbox_heads/mg_head.py:199-231,386-533,
+697-1085).  Parameter names match (``tasks.<t>.conv_{box,cls,dir}.{weight,bias}``); the 1x1
+convs of all tasks run as ONE fused GEMM on the matrix cores and decode/score/top-k/rotated-NMS
+(and the direction classifier's fix-up) run in one device kernel per batch (no host round trips
+per task and sample).  Built: the CBGS form (10-wide vector code, no classifier) and det3d's own
+PointPillars / SECOND form (``loss_aux = direction_classifier``, 7- or 9-dim anchors, scalar or
+vector angle).  Refused, each by name: axis-aligned NMS, multi-class NMS, ``mode="bev"``,
+background-class scores."""
 import ctypes
 import logging
 
@@ -115,11 +119,11 @@ class Head(nn.Module):
     def __init__(self, num_input, num_pred, num_cls, use_dir=False, num_dir=0, header=True, name="",
                  focal_loss_init=False, **kwargs):
         super().__init__()
-        if use_dir:
-            raise NotImplementedError("direction classifier is not on the sweep path")
         self.use_dir = use_dir
         self.conv_box = nn.Conv2d(num_input, num_pred, 1)
         self.conv_cls = nn.Conv2d(num_input, num_cls, 1)
+        if use_dir:
+            self.conv_dir = nn.Conv2d(num_input, num_dir, 1)
 
 
 @HEADS.register_module
@@ -131,8 +135,11 @@ class MultiGroupHead(nn.Module):
                  loss_aux=None, direction_offset=0.0, name="rpn", logger=None):
         super().__init__()
         assert with_cls or with_reg
-        if loss_aux is not None or mode == "bev" or not encode_background_as_zeros:
-            raise NotImplementedError("only the configuration used by examples/active/cbgs_*.py is built")
+        if mode == "bev":
+            raise NotImplementedError('mode="bev" is not built: the device decoder takes whole 7- or 9-dim box codes')
+        if not encode_background_as_zeros:
+            raise NotImplementedError("encode_background_as_zeros=False is not built: the device kernel scores with "
+                                      "sigmoid over foreground classes only")
         assert use_sigmoid_score is True
         num_classes = [len(t["class_names"]) for t in tasks]
         self.class_names = [t["class_names"] for t in tasks]
@@ -142,25 +149,36 @@ class MultiGroupHead(nn.Module):
         self.in_channels = in_channels
         self.encode_background_as_zeros = encode_background_as_zeros
         self.use_sigmoid_score = use_sigmoid_score
-        self.use_direction_classifier = False
+        # a non-None loss_aux is the direction classifier (mg_head.py:457-459); the loss itself is a training piece
+        self.use_direction_classifier = loss_aux is not None
+        self.direction_offset = float(direction_offset)
         self.box_n_dim = box_coder.code_size
         self.anchor_dim = box_coder.n_dim
-        assert self.box_n_dim == 10 and self.anchor_dim == 9 and box_coder.vec_encode and \
-            not box_coder.linear_dim, "the device decoder implements the 9-dim vector-angle code"
+        self.vec_encode = bool(box_coder.vec_encode)
+        # linear_dim / norm_velo never reach the reference's decode (box_coders.py:106-109): nothing to refuse
+        assert self.anchor_dim in (7, 9) and self.box_n_dim == self.anchor_dim + int(self.vec_encode), \
+            "the device decoder implements 7- and 9-dim anchors with a scalar or vector angle code"
+        # the 10-wide vector code without a classifier keeps the entry point it always had
+        self._codes_entry = self.use_direction_classifier or not (self.anchor_dim == 9 and self.vec_encode)
         self.logger = logger or logging.getLogger("MultiGroupHead")
         self.tasks = nn.ModuleList()
         for nc, na in zip(num_classes, self.num_anchor_per_locs):
-            self.tasks.append(Head(in_channels, na * self.box_n_dim, na * nc, header=False))
+            self.tasks.append(Head(in_channels, na * self.box_n_dim, na * nc, use_dir=self.use_direction_classifier,
+                                   num_dir=na * 2, header=False))
         # channel order of the fused output: the box regressions of all tasks, then the class logits of all tasks.
         # The score pre-pass of the decode reads ONLY the class logits: kept together (36 of 236 channels for the six
         # CBGS tasks) they are two 128-byte lines of a pixel's 944-byte record instead of pieces of all eight
         # (head_score_kernel 1.04 -> 0.3 ms per batch of 128).  The offsets travel with the C call.
+        # With a direction classifier its logits follow: [all box | all class | all dir], the class window still contiguous.
         self._convs = [t.conv_box for t in self.tasks] + [t.conv_cls for t in self.tasks]
+        if self.use_direction_classifier:
+            self._convs += [t.conv_dir for t in self.tasks]
         offs = [0]
         for c in self._convs:
             offs.append(offs[-1] + c.out_channels)
         nt = len(self.tasks)
-        self._box_off, self._cls_off, self._ch = offs[:nt], offs[nt:-1], offs[-1]
+        self._box_off, self._cls_off, self._ch = offs[:nt], offs[nt:2 * nt], offs[-1]
+        self._dir_off = offs[2 * nt:3 * nt] if self.use_direction_classifier else [-1] * nt
         self.packs = PackCache()
         self.logger.info("Finish MultiGroupHead Initialization")
 
@@ -192,8 +210,8 @@ class MultiGroupHead(nn.Module):
 
     def forward(self, x, finetune=False, in_pair=False):
         """x NHWC [B,H,W,512] -> list of per-task dicts with NHWC views
-        (``box_preds [B,H,W,na*10]``, ``cls_preds [B,H,W,na*nc]``) like Head.forward
-        (mg_head.py:222-231), plus the fused buffer under ``_fused``."""
+        (``box_preds [B,H,W,na*code]``, ``cls_preds [B,H,W,na*nc]``, with a direction classifier
+        ``dir_cls_preds [B,H,W,na*2]``) like Head.forward (mg_head.py:222-231), plus the fused buffer under ``_fused``."""
         self._prepare(x.device)
         fused = D.conv2d_nhwc(x, self._w, self._wscale, self._b, 1, 1, 0, False, io=D.IO_IN_PAIR if in_pair else 0)
         rets = []
@@ -202,11 +220,14 @@ class MultiGroupHead(nn.Module):
             rets.append({"box_preds": fused[..., b0:b0 + task.conv_box.out_channels],
                          "cls_preds": fused[..., c0:c0 + task.conv_cls.out_channels],
                          "_fused": fused})
+            if self.use_direction_classifier:
+                d0 = self._dir_off[t]
+                rets[-1]["dir_cls_preds"] = fused[..., d0:d0 + task.conv_dir.out_channels]
         return rets
 
     # ------------------------------------------------------------ decode + NMS
     def predict(self, example, preds_dicts, test_cfg, **kwargs):
-        """Returns list[dict(box3d_lidar [K,9], scores [K], label_preds [K] i64, metadata)]
+        """Returns list[dict(box3d_lidar [K,n_dim], scores [K], label_preds [K] i64, metadata)]
         per sample (mg_head.py:697-803)."""
         fused = preds_dicts[0]["_fused"]
         B, H, W, CH = fused.shape
@@ -219,8 +240,12 @@ class MultiGroupHead(nn.Module):
             a = a[0] if a.dim() == 3 else a          # identical for every sample of the batch
             a_dev.append(a.reshape(-1, self.anchor_dim).float().contiguous().to(dev))
         nms = test_cfg["nms"] if isinstance(test_cfg, dict) else test_cfg.nms
-        if not nms["use_rotate_nms"] or nms["use_multi_class_nms"]:
-            raise NotImplementedError("only rotate NMS without multi-class NMS is built")
+        if not nms["use_rotate_nms"]:
+            raise NotImplementedError("use_rotate_nms=False is not built: the reference's axis-aligned path is its CUDA "
+                                      "nms_gpu")
+        if nms["use_multi_class_nms"]:
+            raise NotImplementedError("use_multi_class_nms=True is not built: the reference's branch reads "
+                                      "self.target_assigners, which its head never sets")
         post = int(nms["nms_post_max_size"])
         IntA = ctypes.c_int * nt
         label_off, acc = [], 0
@@ -247,7 +272,7 @@ class MultiGroupHead(nn.Module):
             self._side.wait_event(ready)
             if gate is not None:
                 self._side.wait_event(gate)
-            boxes = torch.empty((B, nt, post, 9), dtype=torch.float32, device=dev)
+            boxes = torch.empty((B, nt, post, self.anchor_dim), dtype=torch.float32, device=dev)
             scores = torch.empty((B, nt, post), dtype=torch.float32, device=dev)
             labels = torch.empty((B, nt, post), dtype=torch.int32, device=dev)
             counts = torch.empty((B, nt), dtype=torch.int32, device=dev)
@@ -257,13 +282,18 @@ class MultiGroupHead(nn.Module):
             task_a = IntA(*[a.shape[0] for a in a_dev])
             ws = torch.empty(lib.load().al3d_head_decode_nms_workspace_bytes(B, nt, task_a), dtype=torch.uint8,
                              device=dev)
-            lib.call("al3d_head_decode_nms", _ptr(fused), B, H * W, CH, nt,
-                     (ctypes.c_void_p * nt)(*[a.data_ptr() for a in a_dev]),
-                     task_a, IntA(*self.num_anchor_per_locs),
-                     IntA(*self.num_classes), IntA(*self._box_off), IntA(*self._cls_off), IntA(*label_off),
-                     float(test_cfg["score_threshold"]), float(nms["nms_iou_threshold"]),
-                     int(nms["nms_pre_max_size"]), post, (ctypes.c_float * 6)(*[float(v) for v in rng]),
-                     _ptr(boxes), _ptr(scores), _ptr(labels), _ptr(counts), _ptr(ws), self._side.cuda_stream)
+            head = (_ptr(fused), B, H * W, CH, nt,
+                    (ctypes.c_void_p * nt)(*[a.data_ptr() for a in a_dev]),
+                    task_a, IntA(*self.num_anchor_per_locs),
+                    IntA(*self.num_classes), IntA(*self._box_off), IntA(*self._cls_off), IntA(*label_off),
+                    float(test_cfg["score_threshold"]), float(nms["nms_iou_threshold"]),
+                    int(nms["nms_pre_max_size"]), post, (ctypes.c_float * 6)(*[float(v) for v in rng]))
+            outs = (_ptr(boxes), _ptr(scores), _ptr(labels), _ptr(counts), _ptr(ws), self._side.cuda_stream)
+            if self._codes_entry:
+                lib.call("al3d_head_decode_nms_codes", *head, self.anchor_dim, int(self.vec_encode),
+                         IntA(*self._dir_off), self.direction_offset, *outs)
+            else:
+                lib.call("al3d_head_decode_nms", *head, *outs)
             done = torch.cuda.Event()
             done.record(self._side)
           return boxes, scores, labels, counts, done, meta

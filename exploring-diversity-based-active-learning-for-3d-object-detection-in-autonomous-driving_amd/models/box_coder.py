@@ -1,6 +1,9 @@
 """Box coder objects configs pass to the head (reference det3d/core/bbox/box_coders.py:40-109,
 det3d/builder.py:399-432).  Decoding itself happens inside the head's device kernel; the
-object carries the settings the reference's ``MultiGroupHead`` reads (``code_size``, ``n_dim``)."""
+object carries the settings the reference's ``MultiGroupHead`` reads (``code_size``, ``n_dim``).
+The device decoder takes ``n_dim`` 7 or 9 with either angle code; ``linear_dim`` and ``norm_velo`` are kept
+but, as in the reference's ``decode_torch`` (which hands ``linear_dim`` to ``bin_loss`` and drops
+``norm_velo``), never change the decode."""
 
 
 class GroundBox3dCoderTorch:

@@ -281,6 +281,39 @@ int64_t al3d_head_decode_nms_workspace_bytes(int B, int ntasks, const int* task_
  * (det3d/core/bbox/box_coders.py:106-109, det3d/core/bbox/box_torch_ops.py:80-148). */
 int al3d_box_decode_f32(const float* enc, const float* anchors, int64_t n, float* out, void* stream);
 
+/* al3d_head_decode_nms for the other box codes of GroundBox3dCoderTorch and for heads with a direction classifier
+ * (det3d's PointPillars / SECOND heads: loss_aux = direction_classifier, encode_angle_vector=False).  Arguments as above, plus
+ *   n_dim       7 (x y z w l h r) or 9 (x y z w l h vx vy r): anchors are [A_t, n_dim], boxes [B, ntasks, post_max, n_dim];
+ *   vec_encode  0: one additive angle residual (r = rt + ra), 1: two (r = atan2f(rty + sin ra, rtx + cos ra)); a task's box
+ *               codes are na * (n_dim + vec_encode) channels at box_off[t];
+ *   dir_off     HOST array [ntasks]: channel offset of the task's na*2 direction logits, or -1 for EVERY task (no classifier);
+ *   direction_offset  the head's direction_offset.
+ * Centre, exp dims and additive velocities decode as in al3d_head_decode_nms.  smooth_dim and norm_velo do not exist here
+ * because they never reach the reference's decode: GroundBox3dCoderTorch.decode_torch (det3d/core/bbox/box_coders.py:106-109)
+ * passes linear_dim positionally into second_box_decode's bin_loss and does not pass norm_velo.
+ * Direction fix-up (mg_head.py:839-842,1042-1051), on the boxes that survived the NMS only: dir_label = argmax of the two
+ * logits by torch's rule (1 iff l1 > l0, or l1 is NaN and l0 is not); where ((r - direction_offset) > 0) != dir_label,
+ * r += float32(pi).  Scores, top-k, the rotated NMS (un-flipped angle) and the centre-range filter (xyz) do not see it.
+ * n_dim 9, vec_encode 1 and no classifier run the kernel of al3d_head_decode_nms itself: same bits.
+ * AL3D_EINVAL before any launch: n_dim not 7 or 9, vec_encode not 0 or 1, a direction window that overlaps its task's box or
+ * class window or runs past CH, -1 mixed with offsets.  Limits and workspace (al3d_head_decode_nms_workspace_bytes) are those
+ * of al3d_head_decode_nms.
+ * Replaces MultiGroupHead.predict/get_task_detections (det3d/models/bbox_heads/mg_head.py:697-1085) with
+ * use_direction_classifier, and second_box_decode (det3d/core/bbox/box_torch_ops.py:80-148) for all four codes. */
+int al3d_head_decode_nms_codes(const float* hout, int B, int HW, int CH, int ntasks,
+                               const float* const* anchors, const int* task_A, const int* task_na,
+                               const int* task_nc, const int* box_off, const int* cls_off,
+                               const int* label_off, float score_thresh, float iou_thresh, int pre_max,
+                               int post_max, const float* range6, int n_dim, int vec_encode, const int* dir_off,
+                               float direction_offset, float* boxes, float* scores, int* labels, int* counts,
+                               void* workspace, void* stream);
+
+/* Residual box decode for n_dim in {7, 9}, scalar or vector angle: enc [n, n_dim + vec_encode], anchors [n, n_dim]
+ * -> [n, n_dim].  Replaces GroundBox3dCoderTorch.decode_torch -> second_box_decode
+ * (det3d/core/bbox/box_coders.py:106-109, det3d/core/bbox/box_torch_ops.py:80-148). */
+int al3d_box_decode_codes_f32(const float* enc, const float* anchors, int64_t n, int n_dim, int vec_encode, float* out,
+                              void* stream);
+
 /* ---------------------------------------------------------------- detector: sparse encoder */
 
 /* Sparse 3-D convolution pieces.  Replace the spconv calls of FPNSpMiddleResNetFHD
