@@ -12,6 +12,13 @@
 // (the reference's argsort leaves ties unspecified), sorts the P winners by (score descending, index ascending) and writes
 // class, cell, the C masked scores of each winning cell, the query position and the query feature row (gathered token row +
 // the class-encoding column + bias).  No library kernel between the heat-map convolution and the decoder.
+// Fewer positive masked scores than proposals: the remaining winners are zero-score cells in ascending flat index, so the P
+// winners are always distinct.
+// NaN logits: the score of such a cell is NaN, and as a key its bits lie above every finite score's, so where the cell may
+// propose (interior, or a free class) it is taken FIRST, as torch's descending argsort puts it; on the frame of another class
+// it is masked to 0 like any score (the reference's heatmap * 0 keeps it NaN there).  A NaN never suppresses a neighbour
+// (the reference's max_pool2d would: `neighbour > score` is false here).  Class, cell, positions and features stay in
+// range and distinct; only the NaN cells' own masked scores are NaN.
 #include "al3d_common.h"
 
 #define TP_THREADS 1024

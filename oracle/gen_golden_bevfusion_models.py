@@ -7,7 +7,10 @@ torch modules run on the CPU in this container with seeded parameters:
   * ``ConvFuser`` (fusers/conv.py:11-25);
   * ``TransformerDecoderLayer`` with ``PositionEmbeddingLearned`` and the file's own ``MultiheadAttention``
     (utils/transformer.py:14-112,114-493): one layer of the TransFusion query decoder;
-  * ``TransFusionBBoxCoder.decode`` (bevfusion/mmdet3d/core/bbox/coders/transfusion_bbox_coder.py:39-123, filter=True).
+  * ``TransFusionBBoxCoder.decode`` (bevfusion/mmdet3d/core/bbox/coders/transfusion_bbox_coder.py:39-123, filter=True);
+  * ``circle_nms`` (bevfusion/mmdet3d/core/post_processing/box3d_nms.py:180-219), run as plain Python: ``numba.jit`` is the
+    identity stand-in of ``ref_import.install_standins``, and ``mmdet3d.ops.iou3d.iou3d_utils`` a stand-in that exports the two
+    names the module imports and never calls here.
 
 The modules import mmcv / mmdet3d registries at module level (absent here: ordinary ModuleNotFoundErrors); content-free
 stand-ins are registered first: ``force_fp32`` as a decorator that returns the function unchanged, registries whose decorator
@@ -17,7 +20,8 @@ extension, not run here).  The sum that op performs is then evaluated in this sc
 recorded (features, voxel index) pairs -- that one step is a statement of the op's semantics (out[b, :, z, x, y] += feature),
 not a reference output; everything up to the op's inputs, and ``downsample`` applied to that sum, IS the reference's code.
 Run in the build container only (needs /root/reference); writes tests/golden/bevfusion_depth_lss.npz,
-bevfusion_conv_fuser.npz, bevfusion_decoder_layer.npz, bevfusion_transfusion_decode.npz.
+bevfusion_conv_fuser.npz, bevfusion_decoder_layer.npz, bevfusion_transfusion_decode.npz, bevfusion_circle_nms.npz; names on the
+command line (depth_lss, conv_fuser, decoder_layer, decode, circle_nms) restrict the run to those.
 """
 import importlib
 import os
@@ -241,14 +245,84 @@ def gen_decode(coder_mod, out):
     print("wrote", out, [tuple(r["bboxes"].shape) for r in res])
 
 
-def main():
+def import_circle_nms():
+    """The reference's ``circle_nms`` as a plain Python function (after ``import_reference``)."""
+    sys.path.insert(0, HERE)
+    import ref_import
+    ref_import.install_standins()                                        # numba.jit: an identity decorator
+    _mod("mmdet3d.ops.iou3d")
+    _mod("mmdet3d.ops.iou3d.iou3d_utils", nms_gpu=None, nms_normal_gpu=None)
+    _pkg("mmdet3d.core.post_processing", os.path.join(BEV, "mmdet3d", "core", "post_processing"))
+    return importlib.import_module("mmdet3d.core.post_processing.box3d_nms").circle_nms
+
+
+def _pair_at(target):
+    """A float32 offset (dx, dy) from the origin whose squared length, evaluated in float32 as the function does, is exactly
+    ``target``: dx among the neighbours of sqrt(target), dy on a 2^-14 grid."""
+    root = np.float32(np.sqrt(np.float64(target)))
+    for m in range(4000):
+        dy = np.float32(m * 2.0 ** -14)
+        dx = np.float32(np.sqrt(max(np.float64(target) - np.float64(dy) ** 2, 0.0)))
+        for _ in range(3):
+            dx = np.nextafter(dx, np.float32(0))
+        for _ in range(7):
+            if (np.float32(0) - dx) ** 2 + (np.float32(0) - dy) ** 2 == target:
+                return dx, dy
+            dx = np.nextafter(dx, np.float32(2) * root)
+    raise RuntimeError(f"no float32 pair at squared distance {target!r}")
+
+
+def gen_circle_nms(circle_nms, out):
+    """Inputs and kept indices only.  Thresholds are handed over as the Python floats the head's task tables hold."""
+    g = np.random.default_rng(14)
+    cases = []
+
+    def add(name, dets, thresh, post_max_size=83):
+        dets = np.ascontiguousarray(dets, np.float32).reshape(-1, 3)
+        keep = [int(i) for i in circle_nms(dets, thresh, post_max_size)]
+        cases.append((name, dets, thresh, post_max_size, keep))
+
+    def cloud(n, side):
+        return np.concatenate([g.random((n, 2)) * side - side / 2, g.random((n, 1))], 1)
+    add("n0", np.zeros((0, 3)), 0.175)
+    add("n1", [[1.0, 2.0, 0.3]], 0.175)
+    add("n2_close", [[0.0, 0.0, 0.4], [0.3, 0.2, 0.6]], 0.175)
+    add("n2_apart", [[0.0, 0.0, 0.4], [0.5, 0.2, 0.6]], 0.175)
+    add("n200_r0175", cloud(200, 6.0), 0.175)
+    add("n200_r07", cloud(200, 10.0), 0.7)
+    d = cloud(60, 5.0)
+    d[:, 2] = 0.5                                                         # every score equal
+    add("equal_scores_all", d, 0.7)
+    d = cloud(90, 6.0)
+    d[:, 2] = np.repeat(g.random(9), 10)                                  # nine groups of ten equal scores
+    add("equal_scores_groups", d[g.permutation(90)], 0.7)
+    for thresh in (0.175, 0.7):
+        t32 = np.float32(thresh)
+        for rel, target in (("under", np.nextafter(t32, np.float32(0))), ("at", t32), ("over", np.nextafter(t32, np.float32(1)))):
+            dx, dy = _pair_at(target)
+            add(f"pair_{rel}_{thresh}", [[0.0, 0.0, 0.9], [dx, dy, 0.8], [50.0, 50.0, 0.7]], thresh)
+    iso = np.stack([np.arange(120) % 12 * 5.0, np.arange(120) // 12 * 5.0, g.permutation(120) / 120.0], 1)
+    add("isolated120_cut_at_83", iso, 0.7)
+    add("isolated120_cut_at_10", iso, 0.175, 10)
+    store = dict(names=np.array([c[0] for c in cases]))
+    for name, dets, thresh, post, keep in cases:
+        store[f"{name}.dets"], store[f"{name}.keep"] = dets, np.array(keep, np.int64)
+        store[f"{name}.thresh"], store[f"{name}.post_max_size"] = np.array([thresh], np.float64), np.array([post])
+    np.savez_compressed(out, **store)
+    print("wrote", out, {c[0]: len(c[4]) for c in cases})
+
+
+def main(only=()):
     depth_lss, fuser, transformer, coder = import_reference()
     gold = os.path.join(os.path.dirname(HERE), "tests", "golden")
-    gen_depth_lss(depth_lss, os.path.join(gold, "bevfusion_depth_lss.npz"))
-    gen_conv_fuser(fuser, os.path.join(gold, "bevfusion_conv_fuser.npz"))
-    gen_decoder_layer(transformer, os.path.join(gold, "bevfusion_decoder_layer.npz"))
-    gen_decode(coder, os.path.join(gold, "bevfusion_transfusion_decode.npz"))
+    jobs = dict(depth_lss=lambda: gen_depth_lss(depth_lss, os.path.join(gold, "bevfusion_depth_lss.npz")),
+                conv_fuser=lambda: gen_conv_fuser(fuser, os.path.join(gold, "bevfusion_conv_fuser.npz")),
+                decoder_layer=lambda: gen_decoder_layer(transformer, os.path.join(gold, "bevfusion_decoder_layer.npz")),
+                decode=lambda: gen_decode(coder, os.path.join(gold, "bevfusion_transfusion_decode.npz")),
+                circle_nms=lambda: gen_circle_nms(import_circle_nms(), os.path.join(gold, "bevfusion_circle_nms.npz")))
+    for name in only or jobs:
+        jobs[name]()
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1:])
