@@ -1342,7 +1342,7 @@ def center_decode_nms(hout, task_ncls, chan_off, *, swapped, max_num, norm_bbox,
     IntT, F6 = ctypes.c_int * nt, ctypes.c_float * 6
     scale = [1.0] * (4 * nt)
     for t in range(nt):
-        for c in range(task_ncls[t]):
+        for c in range(min(task_ncls[t], 4)):          # a fifth class is the library's to refuse, not an IndexError here
             scale[4 * t + c] = float(nms_scale[t][c])
     radius = [float(min_radius[t]) if kinds[t] == "circle" else 0.0 for t in range(nt)]
     limit = None if post_center_limit_range is None or len(post_center_limit_range) == 0 \
