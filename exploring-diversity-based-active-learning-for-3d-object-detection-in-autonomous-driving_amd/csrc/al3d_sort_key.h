@@ -1,8 +1,7 @@
-// Sort key of al3d_argsort_desc_f32, in one place for the kernel and for the test suite's CPU
-// check of the formula: plain C, no device intrinsics.
+// The 64-bit sort word of every top-K selection (al3d_select.h) and the key of al3d_argsort_desc_f32, in one place for
+// the kernels and for the test suite's CPU check of the formula: plain C, no device intrinsics.
 //
-// torch.argsort(-x, stable=True): descending, NaN last, equal values by ascending index.
-// key = (order-preserving bits of x) << 32 | ~index; a larger key sorts first.
+// word = (order-preserving 32 bits) << 32 | ~index; a larger word sorts first: bits descending, equal bits by ascending index.
 #pragma once
 
 #ifdef __HIPCC__
@@ -11,6 +10,11 @@
 #define AL3D_SORT_KEY_FN static inline
 #endif
 
+AL3D_SORT_KEY_FN unsigned long long sel_word(unsigned bits, unsigned index) { return ((unsigned long long)bits << 32) | (unsigned)~index; }
+AL3D_SORT_KEY_FN unsigned sel_word_bits(unsigned long long w) { return (unsigned)(w >> 32); }
+AL3D_SORT_KEY_FN unsigned sel_word_index(unsigned long long w) { return ~(unsigned)w; }
+
+// torch.argsort(-x, stable=True): descending, NaN last, equal values by ascending index.
 AL3D_SORT_KEY_FN unsigned long long al3d_sort_key(float v, unsigned idx)
 {
     unsigned u;
@@ -20,5 +24,5 @@ AL3D_SORT_KEY_FN unsigned long long al3d_sort_key(float v, unsigned idx)
         if (u == 0x80000000u) u = 0u;                       // -0.0 == +0.0: one key, index decides
         u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);     // total order, larger float -> larger key
     }
-    return ((unsigned long long)u << 32) | (unsigned)(0xffffffffu - idx);
+    return sel_word(u, idx);
 }

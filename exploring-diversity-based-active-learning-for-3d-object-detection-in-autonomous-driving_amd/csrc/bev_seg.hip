@@ -33,6 +33,7 @@
 // order into the workgroup's partial, and seg_reduce_kernel adds the partials of a frame: 16 interleaved slots, each in
 // ascending workgroup order, then the slots in ascending order.
 #include "al3d_common.h"
+#include "al3d_select.h"
 
 // ------------------------------------------------------------------ BEVGridTransform
 __global__ __launch_bounds__(256) void bev_grid_resample_kernel(const float* __restrict__ src, int h, int w, int C,
@@ -179,7 +180,7 @@ __global__ __launch_bounds__(256) void seg_classify_kernel(const float* __restri
     for (int k = 0; k < KP; ++k) {
         if (k < K) {
             const float z = zw[k * 64 + lane] + bias[k];
-            const float pr = 1.0f / (1.0f + expf(-z));
+            const float pr = al3d_sigmoid(z);
             if (valid) prob[((int64_t)n * K + k) * HW + px] = pr;
             if (partial) {
                 float e = 0.f;

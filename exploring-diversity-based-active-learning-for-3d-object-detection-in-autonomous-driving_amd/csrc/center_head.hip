@@ -9,13 +9,14 @@
 // (a host synchronisation each) and an NMS that copies to the host; here a whole-GPU pre-pass writes the sigmoid scores
 // as sortable keys and one workgroup per (sample, task) does everything else in LDS, with no host synchronisation.
 //
-// torch.topk leaves the order of equal scores open.  Device rule, as in al3d_tf_proposals_f32: among equal scores the
-// smaller flat index class * D0 * D1 + cell wins, cell = d0 * D1 + d1 in the map as it is handed to the kernel.
+// torch.topk leaves the order of equal scores open.  The tie rule of al3d_select.h decides, on the flat index
+// class * D0 * D1 + cell, cell = d0 * D1 + d1 in the map as it is handed to the kernel.
 // Comparisons: the coder's score filter is strict (score > threshold, coder :196), its centre range closed (:198-216);
 // get_task_detections keeps score >= test score threshold (:818); the rotated NMS suppresses on IoU > nms_thr, strictly
 // (iou3d_kernel.cu:326; the anchor head's loop in head_nms.hip uses >=); the circle NMS on squared distance <= radius.
 #include "al3d_common.h"
 #include "al3d_rbox.h"
+#include "al3d_select.h"
 
 #define CT_THREADS 1024
 #define CT_MAXK 1024            // max_num <= 1024
@@ -51,8 +52,6 @@ struct CenterParams {
     unsigned* keys;             // workspace [B, sumC, D0 * D1]: bits of sigmoid(logit)
 };
 
-__device__ __forceinline__ float ct_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 // whole GPU: one thread per (sample, cell) writes the score keys of every class (a non-negative float's bits order like
 // the float; NaN -> 0)
 __global__ __launch_bounds__(256) void center_score_kernel(CenterParams p)
@@ -65,35 +64,10 @@ __global__ __launch_bounds__(256) void center_score_kernel(CenterParams p)
     for (int t = 0; t < p.ntasks; ++t) {
         const CenterTask& tk = p.task[t];
         for (int c = 0; c < tk.ncls; ++c) {
-            const float s = ct_sigmoid(px[tk.heat_off + c]);
+            const float s = al3d_sigmoid(px[tk.heat_off + c]);
             p.keys[(b * p.sumC + tk.key_off + c) * HW + cell] = s == s ? __float_as_uint(s) : 0u;
         }
     }
-}
-
-__device__ __forceinline__ int ct_block_exclusive_scan(int v, int* s_wave, int& total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int x = v;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int y = __shfl_up(x, off);
-        if (lane >= off) x += y;
-    }
-    if (lane == 63) s_wave[wave] = x;
-    __syncthreads();
-    if (wave == 0) {
-        int w = lane < CT_THREADS / 64 ? s_wave[lane] : 0;
-        for (int off = 1; off < CT_THREADS / 64; off <<= 1) {
-            const int y = __shfl_up(w, off);
-            if (lane >= off) w += y;
-        }
-        if (lane < CT_THREADS / 64) s_wave[lane] = w;
-    }
-    __syncthreads();
-    const int base = wave > 0 ? s_wave[wave - 1] : 0;
-    total = s_wave[CT_THREADS / 64 - 1];
-    __syncthreads();
-    return base + x - v;
 }
 
 // One workgroup per (sample, task).  LDS: 16 KB candidate keys, 32 KB corners, 4 KB areas, 1 KB live flags, 1 KB
@@ -102,13 +76,11 @@ __global__ __launch_bounds__(CT_THREADS) void center_nms_kernel(CenterParams p)
 {
     const int b = blockIdx.x / p.ntasks, t = blockIdx.x % p.ntasks;
     const CenterTask& tk = p.task[t];
-    const int tid = threadIdx.x, lane = tid & 63;
+    const int tid = threadIdx.x;
     const int HW = p.D0 * p.D1, K = p.K;
 
-    __shared__ unsigned hist[256];
-    __shared__ int s_wave[CT_THREADS / 64];
-    __shared__ unsigned s_prefix, s_need, s_cnt;
-    __shared__ unsigned long long cand[CT_MAXCAND];     // (score bits << 32) | ~flat index
+    __shared__ SelScratch<CT_THREADS> sel;
+    __shared__ unsigned long long cand[CT_MAXCAND];     // sel_word(score bits, flat index)
     __shared__ float cx_s[CT_MAXK][4], cy_s[CT_MAXK][4];
     __shared__ float area_s[CT_MAXK];
     __shared__ unsigned char alive_s[CT_MAXK];
@@ -117,65 +89,9 @@ __global__ __launch_bounds__(CT_THREADS) void center_nms_kernel(CenterParams p)
     // ---- per class: the K best cells (ties: the smaller cell), by a four-pass radix select over the class's key plane
     for (int c = 0; c < tk.ncls; ++c) {
         const unsigned* __restrict__ kb = p.keys + ((int64_t)b * p.sumC + tk.key_off + c) * HW;
-        unsigned prefix = 0u, need = (unsigned)K;
-        for (int pass = 0; pass < 4; ++pass) {
-            const int shift = 24 - 8 * pass;
-            if (tid < 256) hist[tid] = 0u;
-            __syncthreads();
-            const unsigned hi_mask = pass == 0 ? 0u : 0xffffffffu << (shift + 8);
-            for (int i0 = 0; i0 < HW; i0 += CT_THREADS) {
-                const int i = i0 + tid;
-                int bin = -1;
-                if (i < HW) {
-                    const unsigned v = kb[i];
-                    if ((v & hi_mask) == prefix) bin = (int)((v >> shift) & 255u);
-                }
-                // background scores share their leading byte: one aggregated atomic for the first lane's bin, plain LDS
-                // atomics for the rest
-                const unsigned long long pending = __ballot(bin >= 0);
-                if (pending) {
-                    const int leader = (int)__builtin_ctzll(pending);
-                    const int lb = __shfl(bin, leader);
-                    const unsigned long long same = __ballot(bin == lb);
-                    if (lane == leader) atomicAdd(&hist[lb], (unsigned)__popcll(same));
-                    if (bin >= 0 && bin != lb) atomicAdd(&hist[bin], 1u);
-                }
-            }
-            __syncthreads();
-            if (tid == 0) {
-                unsigned acc = 0u;
-                int d = 255;
-                for (; d > 0; --d) {
-                    if (acc + hist[d] >= need) break;
-                    acc += hist[d];
-                }
-                s_prefix = prefix | ((unsigned)d << shift);
-                s_need = need - acc;
-            }
-            __syncthreads();
-            prefix = s_prefix;
-            need = s_need;
-            __syncthreads();
-        }
-        const unsigned T = prefix;                  // K-th largest key; `need` of the keys equal to it are taken, smallest cells first
-        if (tid == 0) s_cnt = 0u;
-        const int chunk = (HW + CT_THREADS - 1) / CT_THREADS;
-        const int i0 = tid * chunk < HW ? tid * chunk : HW, i1 = i0 + chunk < HW ? i0 + chunk : HW;
-        int neq = 0;
-        for (int i = i0; i < i1; ++i) neq += kb[i] == T;
-        int tot_eq;
-        int peq = ct_block_exclusive_scan(neq, s_wave, tot_eq);      // barriers inside: s_cnt is visible
-        unsigned long long* dst = cand + c * K;
-        for (int i = i0; i < i1; ++i) {
-            const unsigned v = kb[i];
-            bool take = v > T;
-            if (v == T) { take = peq < (int)need; ++peq; }
-            if (take) {
-                const unsigned slot = atomicAdd(&s_cnt, 1u);
-                if (slot < (unsigned)K) dst[slot] = ((unsigned long long)v << 32) | (unsigned)(~(unsigned)(c * HW + i));
-            }
-        }
-        __syncthreads();
+        unsigned T, need;
+        blk_radix_threshold<CT_THREADS>(kb, HW, (unsigned)K, sel, T, need);
+        blk_collect_topk<CT_THREADS>(kb, HW, T, need, (unsigned)(c * HW), cand + c * K, (unsigned)K, sel);
     }
     // ---- the K best of the ncls * K candidates: bitonic sort, (score descending, flat index ascending)
     const int total = tk.ncls * K;
@@ -183,16 +99,7 @@ __global__ __launch_bounds__(CT_THREADS) void center_nms_kernel(CenterParams p)
     while (N < total) N <<= 1;
     for (int q = total + tid; q < N; q += CT_THREADS) cand[q] = 0ull;
     __syncthreads();
-    for (int size = 2; size <= N; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            if (tid < N / 2) {
-                const int i = ((tid & ~(stride - 1)) << 1) | (tid & (stride - 1)), j = i | stride;
-                const unsigned long long x = cand[i], y = cand[j];
-                const bool desc = (i & size) == 0;
-                if (desc ? x < y : x > y) { cand[i] = y; cand[j] = x; }
-            }
-            __syncthreads();
-        }
+    blk_sort_desc_u64<CT_THREADS>(cand, N);
     // ---- gather + decode (coder :146-189), the coder's filters (:194-216) and, for the rotated NMS, the score filter of
     // get_task_detections (:814-824)
     float box[9];
@@ -200,11 +107,10 @@ __global__ __launch_bounds__(CT_THREADS) void center_nms_kernel(CenterParams p)
     int label = 0;
     bool ok = false;
     if (tid < K) {
-        const unsigned long long key = cand[tid];
-        const unsigned flat = ~(unsigned)(key & 0xffffffffull);
+        const unsigned flat = sel_word_index(cand[tid]);
         label = (int)(flat / (unsigned)HW);
         const int cell = (int)(flat % (unsigned)HW);
-        score = __uint_as_float((unsigned)(key >> 32));
+        score = __uint_as_float(sel_word_bits(cand[tid]));
         const int d0 = cell / p.D1, d1 = cell % p.D1;
         float xs = (float)(p.swapped ? d1 : d0), ys = (float)(p.swapped ? d0 : d1);
         const float* px = p.hout + ((int64_t)b * HW + cell) * p.CH;
@@ -224,7 +130,7 @@ __global__ __launch_bounds__(CT_THREADS) void center_nms_kernel(CenterParams p)
         if (tk.nms_kind == 0) ok = ok && score >= p.test_thr;
     }
     int n;
-    int pos = ct_block_exclusive_scan(ok ? 1 : 0, s_wave, n);           // survivors stay in descending score order
+    int pos = blk_exclusive_scan<CT_THREADS>(ok ? 1 : 0, sel.wave, n);         // survivors stay in descending score order
     if (tk.nms_kind == 0 && n > p.pre_max) n = p.pre_max;
     ok = ok && pos < n;
     float x1 = 0.f, y1 = 0.f, x2 = 0.f, y2 = 0.f;

@@ -9,8 +9,8 @@
 // through the host (D2H -> boost::geometry loop -> H2D); here one workgroup per
 // (sample, task) does select + sort + NMS entirely in LDS.
 //
-// Selection order is made deterministic: higher score first, equal scores -> lower anchor
-// index (torch.topk / numpy argsort leave ties unspecified).
+// Selection order is made deterministic by the tie rule of al3d_select.h on the anchor index
+// (torch.topk / numpy argsort leave ties unspecified).
 //
 // Box codes.  The kernel body is a template over the anchor width ND (7: x y z w l h r, 9: + vx vy before r), the angle
 // code VEC (1: two residuals rtx, rty and atan2f; 0: one additive residual) and DIR (the direction classifier's fix-up of
@@ -23,6 +23,7 @@
 // (lt + 1) * la or velocity-times-diagonal variant to build, whatever the coder's settings say.
 #include "al3d_common.h"
 #include "al3d_rbox.h"
+#include "al3d_select.h"
 
 #define HN_THREADS 1024
 #define HN_MAXK 1024            // nms_pre_max_size <= 1024
@@ -62,8 +63,6 @@ struct HeadParams {
     int dir_off[8];
     float direction_offset;
 };
-
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // second_box_decode with smooth_dim=False, norm_velo=False: t [ND + VEC], a [ND] -> o [ND]
 template <int ND, int VEC>
@@ -130,8 +129,8 @@ __global__ __launch_bounds__(256) void head_score_kernel(HeadParams p)
     const float* hb = p.hout + (int64_t)b * p.HW * p.CH;
     const int loc = a / tk.na, j = a % tk.na;
     const float* c = hb + (int64_t)loc * p.CH + tk.cls_off + j * tk.nc;
-    float best = sigmoidf_(c[0]);
-    for (int q = 1; q < tk.nc; ++q) { const float s = sigmoidf_(c[q]); if (s > best) best = s; }
+    float best = al3d_sigmoid(c[0]);
+    for (int q = 1; q < tk.nc; ++q) { const float s = al3d_sigmoid(c[q]); if (s > best) best = s; }
     p.sbits[(int64_t)b * p.sample_stride + p.task_soff[t] + a] = best >= p.score_thresh ? __float_as_uint(best) : 0u;
 }
 
@@ -170,8 +169,8 @@ __global__ __launch_bounds__(256) void head_score_rows_kernel(HeadParams p, int 
         unsigned* o = p.sbits + (int64_t)b * p.sample_stride + p.task_soff[t] + (int64_t)(loc0 + l) * tk.na;
         for (int j = 0; j < tk.na; ++j) {
             const float* c = lg + l * pitch + (tk.cls_off - cls_lo) + j * tk.nc;
-            float best = sigmoidf_(c[0]);
-            for (int q = 1; q < tk.nc; ++q) { const float s2 = sigmoidf_(c[q]); if (s2 > best) best = s2; }
+            float best = al3d_sigmoid(c[0]);
+            for (int q = 1; q < tk.nc; ++q) { const float s2 = al3d_sigmoid(c[q]); if (s2 > best) best = s2; }
             o[j] = best >= p.score_thresh ? __float_as_uint(best) : 0u;
         }
     }
@@ -189,7 +188,7 @@ __global__ __launch_bounds__(HN_THREADS) void head_nms_kernel(HeadParams p)
 
     __shared__ unsigned hist[256];
     __shared__ unsigned s_prefix, s_need, s_sel_cnt, s_eq_seen;
-    __shared__ unsigned long long key_s[HN_MAXK];       // (score bits << 32) | ~anchor
+    __shared__ unsigned long long key_s[HN_MAXK];       // sel_word(score bits, anchor)
     __shared__ float cx_s[HN_MAXK][4], cy_s[HN_MAXK][4];
     // per-wave histograms of the select passes: 16 x 256 words in cx_s's storage (free until the decode phase)
     unsigned (*hist_w)[256] = reinterpret_cast<unsigned (*)[256]>(&cx_s[0][0]);
@@ -203,14 +202,16 @@ __global__ __launch_bounds__(HN_THREADS) void head_nms_kernel(HeadParams p)
     auto anchor_score = [&](int a, int& label) -> float {
         const int loc = a / tk.na, j = a % tk.na;
         const float* c = hb + (int64_t)loc * p.CH + tk.cls_off + j * tk.nc;
-        float best = sigmoidf_(c[0]);
+        float best = al3d_sigmoid(c[0]);
         label = 0;
-        for (int q = 1; q < tk.nc; ++q) { const float s = sigmoidf_(c[q]); if (s > best) { best = s; label = q; } }
+        for (int q = 1; q < tk.nc; ++q) { const float s = al3d_sigmoid(c[q]); if (s > best) { best = s; label = q; } }
         return best;
     };
 
     // ---- radix select of the pre_max largest scores among those >= score_thresh
     // scores are in (0,1): positive floats order like their bit patterns.
+    // Not blk_radix_threshold: these passes skip zero keys, leave early when fewer than pre_max keys pass, batch four loads
+    // per trip and keep per-wave histograms in cx_s's storage -- tuned by measurement on the headline path.
     const int K = p.pre_max < HN_MAXK ? p.pre_max : HN_MAXK;
     unsigned prefix = 0, need = K;
     if (tid == 0) { s_sel_cnt = 0; s_eq_seen = 0; }
@@ -304,7 +305,7 @@ __global__ __launch_bounds__(HN_THREADS) void head_nms_kernel(HeadParams p)
         if (!bits) continue;
         if (need == 0xffffffffu || bits > thr_bits) {
             const unsigned slot = atomicAdd(&s_sel_cnt, 1u);
-            if (slot < HN_MAXK) key_s[slot] = ((unsigned long long)bits << 32) | (unsigned)(0xffffffffu - (unsigned)a);
+            if (slot < HN_MAXK) key_s[slot] = sel_word(bits, (unsigned)a);
         } else if (bits == thr_bits) {
             const unsigned e = atomicAdd(&s_eq_cnt, 1u);
             if (e < HN_MAXK) eq_list[e] = a;
@@ -321,7 +322,7 @@ __global__ __launch_bounds__(HN_THREADS) void head_nms_kernel(HeadParams p)
             for (unsigned q = 0; q < neq; ++q) rank += eq_list[q] < a ? 1u : 0u;
             if (rank < need) {
                 const unsigned slot = atomicAdd(&s_sel_cnt, 1u);
-                if (slot < HN_MAXK) key_s[slot] = ((unsigned long long)thr_bits << 32) | (unsigned)(0xffffffffu - (unsigned)a);
+                if (slot < HN_MAXK) key_s[slot] = sel_word(thr_bits, (unsigned)a);
             }
         }
         __syncthreads();
@@ -349,7 +350,7 @@ __global__ __launch_bounds__(HN_THREADS) void head_nms_kernel(HeadParams p)
         if (tid == 0) { unsigned tot = 0; for (int w = 0; w < HN_THREADS / 64; ++w) tot += eq_wave[w]; s_eq_seen += tot; }
         if (take) {
             const unsigned slot = atomicAdd(&s_sel_cnt, 1u);
-            if (slot < HN_MAXK) key_s[slot] = ((unsigned long long)bits << 32) | (unsigned)(0xffffffffu - (unsigned)a);
+            if (slot < HN_MAXK) key_s[slot] = sel_word(bits, (unsigned)a);
         }
         __syncthreads();
     }
@@ -361,26 +362,15 @@ __global__ __launch_bounds__(HN_THREADS) void head_nms_kernel(HeadParams p)
     // ---- bitonic sort of the (<= 1024) keys, descending
     for (int q = n + tid; q < HN_MAXK; q += HN_THREADS) key_s[q] = 0ull;
     __syncthreads();
-    for (int size = 2; size <= HN_MAXK; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            const int i = tid, j = i ^ stride;
-            if (j > i) {
-                const bool desc = (i & size) == 0;
-                const unsigned long long x = key_s[i], y = key_s[j];
-                if (desc ? x < y : x > y) { key_s[i] = y; key_s[j] = x; }
-            }
-            __syncthreads();
-        }
-    }
+    blk_sort_desc_u64<HN_THREADS>(key_s, HN_MAXK);
     // ---- decode the selected boxes, corners, standup boxes
     float box[ND];
     int my_label = 0, my_anchor = 0;
     float my_score = 0.f;
     if (tid < n) {
-        const unsigned long long key = key_s[tid];
-        const int a = (int)(0xffffffffu - (unsigned)(key & 0xffffffffull));
+        const int a = (int)sel_word_index(key_s[tid]);
         my_anchor = a;
-        my_score = __uint_as_float((unsigned)(key >> 32));
+        my_score = __uint_as_float(sel_word_bits(key_s[tid]));
         int lab;
         anchor_score(a, lab);
         my_label = lab;

@@ -8,8 +8,8 @@
 //               query_pos = bev_pos[cell]; query_heatmap_score = heatmap[:, :, cell].
 // Here: (1) one thread per cell evaluates the sigmoid of its C logits and of the ring around it and writes the masked scores
 // as order-preserving 32-bit keys [B][C * HW] (a non-negative float's bits sort like the float); (2) one workgroup per
-// sample selects the P largest keys by a four-pass radix select over LDS histograms, breaks ties by the smaller flat index
-// (the reference's argsort leaves ties unspecified), sorts the P winners by (score descending, index ascending) and writes
+// sample selects and sorts the P largest keys with the pieces and the tie rule of al3d_select.h (flat index = class * HW +
+// cell; the reference's argsort leaves ties unspecified) and writes
 // class, cell, the C masked scores of each winning cell, the query position and the query feature row (gathered token row +
 // the class-encoding column + bias).  No library kernel between the heat-map convolution and the decoder.
 // Fewer positive masked scores than proposals: the remaining winners are zero-score cells in ascending flat index, so the P
@@ -20,11 +20,10 @@
 // (the reference's max_pool2d would: `neighbour > score` is false here).  Class, cell, positions and features stay in
 // range and distinct; only the NaN cells' own masked scores are NaN.
 #include "al3d_common.h"
+#include "al3d_select.h"
 
 #define TP_THREADS 1024
 #define TP_MAXP 256
-
-__device__ __forceinline__ float tp_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // logits [B][H][W][C] (channels-last) -> keys [B][C][H*W] (bits of the masked sigmoid score; 0 = not a local maximum)
 __global__ __launch_bounds__(256) void tp_peak_kernel(const float* __restrict__ logits, int B, int H, int W, int C, int k,
@@ -37,43 +36,18 @@ __global__ __launch_bounds__(256) void tp_peak_kernel(const float* __restrict__ 
     const bool interior = y >= r && y < H - r && x >= r && x < W - r;
     const float* row = logits + ((int64_t)b * H * W) * C;
     for (int c = 0; c < C; ++c) {
-        const float s = tp_sigmoid(row[((int64_t)y * W + x) * C + c]);
+        const float s = al3d_sigmoid(row[((int64_t)y * W + x) * C + c]);
         bool peak = r == 0 || ((free_mask >> c) & 1u);
         if (!peak && interior) {
             peak = true;
             for (int dy = -r; dy <= r && peak; ++dy)
                 for (int dx = -r; dx <= r; ++dx) {
                     if (!dy && !dx) continue;
-                    if (tp_sigmoid(row[((int64_t)(y + dy) * W + (x + dx)) * C + c]) > s) { peak = false; break; }
+                    if (al3d_sigmoid(row[((int64_t)(y + dy) * W + (x + dx)) * C + c]) > s) { peak = false; break; }
                 }
         }
         keys[((int64_t)b * C + c) * H * W + (int64_t)y * W + x] = peak ? __float_as_uint(s) : 0u;
     }
-}
-
-__device__ __forceinline__ int tp_block_exclusive_scan(int v, int* s_wave, int& total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int x = v;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int y = __shfl_up(x, off);
-        if (lane >= off) x += y;
-    }
-    if (lane == 63) s_wave[wave] = x;
-    __syncthreads();
-    if (wave == 0) {
-        int w = lane < TP_THREADS / 64 ? s_wave[lane] : 0;
-        for (int off = 1; off < TP_THREADS / 64; off <<= 1) {
-            const int y = __shfl_up(w, off);
-            if (lane >= off) w += y;
-        }
-        if (lane < TP_THREADS / 64) s_wave[lane] = w;
-    }
-    __syncthreads();
-    const int base = wave > 0 ? s_wave[wave - 1] : 0;
-    total = s_wave[TP_THREADS / 64 - 1];
-    __syncthreads();
-    return base + x - v;
 }
 
 __global__ __launch_bounds__(TP_THREADS) void tp_select_kernel(const unsigned* __restrict__ keys, int HW, int C, int P,
@@ -85,97 +59,36 @@ __global__ __launch_bounds__(TP_THREADS) void tp_select_kernel(const unsigned* _
                                                                float* __restrict__ qscore, float* __restrict__ qfeat,
                                                                float* __restrict__ qpos)
 {
-    __shared__ unsigned hist[256];
-    __shared__ int s_wave[TP_THREADS / 64];
-    __shared__ unsigned s_prefix, s_need;
+    __shared__ SelScratch<TP_THREADS> sel;
     __shared__ unsigned long long s_sel[TP_MAXP];
     const int tid = threadIdx.x, b = blockIdx.x;
     const int64_t N = (int64_t)C * HW;
     const unsigned* kb = keys + (int64_t)b * N;
-    // ---- the P-th largest key: radix select, most significant byte first
-    unsigned prefix = 0u, need = (unsigned)P;
-    for (int pass = 0; pass < 4; ++pass) {
-        const int shift = 24 - 8 * pass;
-        if (tid < 256) hist[tid] = 0u;
-        __syncthreads();
-        const unsigned hi_mask = pass == 0 ? 0u : 0xffffffffu << (shift + 8);
-        for (int64_t i = tid; i < N; i += TP_THREADS) {
-            const unsigned v = kb[i];
-            if ((v & hi_mask) == prefix) atomicAdd(&hist[(v >> shift) & 255u], 1u);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            unsigned acc = 0u;
-            int d = 255;
-            for (; d > 0; --d) {
-                if (acc + hist[d] >= need) break;
-                acc += hist[d];
-            }
-            s_prefix = prefix | ((unsigned)d << shift);
-            s_need = need - acc;
-        }
-        __syncthreads();
-        prefix = s_prefix;
-        need = s_need;
-        __syncthreads();
-    }
-    const unsigned T = prefix;                       // the threshold key; `need` of the keys equal to T are taken (lowest indices)
-    // ---- collect: every key > T, and the first `need` keys == T in index order.  A thread owns a contiguous index chunk,
-    // so exclusive scans of the per-thread counts give positions in index order
-    const int64_t chunk = (N + TP_THREADS - 1) / TP_THREADS;
-    const int64_t i0 = (int64_t)tid * chunk, i1 = i0 + chunk < N ? i0 + chunk : N;
-    int ngt = 0, neq = 0;
-    for (int64_t i = i0; i < i1; ++i) {
-        const unsigned v = kb[i];
-        ngt += v > T;
-        neq += v == T;
-    }
-    int tot_gt, tot_eq;
-    int pgt = tp_block_exclusive_scan(ngt, s_wave, tot_gt);
-    int peq = tp_block_exclusive_scan(neq, s_wave, tot_eq);
     for (int i = tid; i < TP_MAXP; i += TP_THREADS) s_sel[i] = 0ull;          // padding sorts last (key 0, index "infinity")
-    __syncthreads();
-    for (int64_t i = i0; i < i1; ++i) {
-        const unsigned v = kb[i];
-        int slot = -1;
-        if (v > T) slot = pgt++;
-        else if (v == T) { if (peq < (int)need) slot = tot_gt + peq; ++peq; }
-        // composite sort word: key descending, index ascending  ->  (key << 32) | ~index, sorted descending
-        if (slot >= 0 && slot < TP_MAXP) s_sel[slot] = ((unsigned long long)v << 32) | (unsigned)(~(unsigned)i);
-    }
-    __syncthreads();
-    // ---- bitonic sort of TP_MAXP words, descending
-    for (int k2 = 2; k2 <= TP_MAXP; k2 <<= 1)
-        for (int j = k2 >> 1; j > 0; j >>= 1) {
-            if (tid < TP_MAXP) {
-                const int ixj = tid ^ j;
-                if (ixj > tid) {
-                    const unsigned long long a = s_sel[tid], c2 = s_sel[ixj];
-                    const bool up = (tid & k2) == 0;                        // descending blocks where (tid & k2) == 0
-                    if (up ? a < c2 : a > c2) { s_sel[tid] = c2; s_sel[ixj] = a; }
-                }
-            }
-            __syncthreads();
-        }
+    // ---- the P largest keys (N >= P: exactly P words), then sorted: key descending, index ascending
+    unsigned T, need;
+    blk_radix_threshold<TP_THREADS>(kb, (int)N, (unsigned)P, sel, T, need);     // barriers inside: the padding is visible
+    blk_collect_topk<TP_THREADS>(kb, (int)N, T, need, 0u, s_sel, TP_MAXP, sel);
+    blk_sort_desc_u64<TP_THREADS>(s_sel, TP_MAXP);
     // ---- outputs
     for (int p = tid; p < P; p += TP_THREADS) {
-        const unsigned idx = ~(unsigned)(s_sel[p] & 0xffffffffull);
+        const unsigned idx = sel_word_index(s_sel[p]);
         top_class[(int64_t)b * P + p] = idx / HW;
         top_cell[(int64_t)b * P + p] = idx % HW;
     }
     for (int e = tid; e < P * C; e += TP_THREADS) {
         const int c = e / P, p = e % P;
-        const unsigned idx = ~(unsigned)(s_sel[p] & 0xffffffffull);
+        const unsigned idx = sel_word_index(s_sel[p]);
         qscore[((int64_t)b * C + c) * P + p] = __uint_as_float(kb[(int64_t)c * HW + idx % HW]);
     }
     for (int e = tid; e < P * 2; e += TP_THREADS) {
         const int p = e >> 1;
-        const unsigned idx = ~(unsigned)(s_sel[p] & 0xffffffffull);
+        const unsigned idx = sel_word_index(s_sel[p]);
         qpos[((int64_t)b * P + p) * 2 + (e & 1)] = bev_pos[(int64_t)(idx % HW) * 2 + (e & 1)];
     }
     for (int e = tid; e < P * hidden; e += TP_THREADS) {
         const int p = e / hidden, h = e % hidden;
-        const unsigned idx = ~(unsigned)(s_sel[p] & 0xffffffffull);
+        const unsigned idx = sel_word_index(s_sel[p]);
         const int cls = idx / HW, cell = idx % HW;
         // key_rows[cell] + class_encoding.weight[:, cls] + bias, in that order (the reference adds the Conv1d output)
         qfeat[((int64_t)b * P + p) * hidden + h] =

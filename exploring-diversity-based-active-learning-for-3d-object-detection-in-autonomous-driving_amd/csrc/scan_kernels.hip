@@ -3,35 +3,10 @@
 // walks the block sums in 1024-wide chunks with a running base, so any n works.
 #include "al3d_common.h"
 #include "al3d_scan.h"
+#include "al3d_select.h"
 
 #define SC_THREADS 1024
 #define SC_ITEMS 2048
-
-__device__ __forceinline__ int block_exclusive_scan(int v, int* s_wave, int& total)
-{
-    // inclusive scan inside the wave
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int x = v;
-    for (int off = 1; off < 64; off <<= 1) {
-        int y = __shfl_up(x, off);
-        if (lane >= off) x += y;
-    }
-    if (lane == 63) s_wave[wave] = x;
-    __syncthreads();
-    if (wave == 0) {
-        int w = lane < SC_THREADS / 64 ? s_wave[lane] : 0;
-        for (int off = 1; off < SC_THREADS / 64; off <<= 1) {
-            int y = __shfl_up(w, off);
-            if (lane >= off) w += y;
-        }
-        if (lane < SC_THREADS / 64) s_wave[lane] = w;   // inclusive wave totals
-    }
-    __syncthreads();
-    const int base = wave > 0 ? s_wave[wave - 1] : 0;
-    total = s_wave[SC_THREADS / 64 - 1];
-    __syncthreads();
-    return base + x - v;
-}
 
 __global__ __launch_bounds__(SC_THREADS) void scan_block_sums(const int* __restrict__ in, int64_t n,
                                                               int* __restrict__ sums)
@@ -42,7 +17,7 @@ __global__ __launch_bounds__(SC_THREADS) void scan_block_sums(const int* __restr
     if (i0 < n) v += in[i0];
     if (i0 + 1 < n) v += in[i0 + 1];
     int total;
-    block_exclusive_scan(v, s_wave, total);
+    blk_exclusive_scan<SC_THREADS>(v, s_wave, total);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
@@ -54,7 +29,7 @@ __global__ __launch_bounds__(SC_THREADS) void scan_sums(int* __restrict__ sums, 
         const int64_t i = c0 + threadIdx.x;
         const int v = i < nb ? sums[i] : 0;
         int total;
-        const int ex = block_exclusive_scan(v, s_wave, total);
+        const int ex = blk_exclusive_scan<SC_THREADS>(v, s_wave, total);
         if (i < nb) sums[i] = base + ex;
         base += total;
     }
@@ -71,7 +46,7 @@ __global__ __launch_bounds__(SC_THREADS) void scan_downsweep(const int* in, int6
     const int a = i0 < n ? in[i0] : 0;
     const int b = i0 + 1 < n ? in[i0 + 1] : 0;
     int total;
-    const int ex = block_exclusive_scan(a + b, s_wave, total) + sums[blockIdx.x];
+    const int ex = blk_exclusive_scan<SC_THREADS>(a + b, s_wave, total) + sums[blockIdx.x];
     if (i0 < n) out[i0] = ex;
     if (i0 + 1 < n) out[i0 + 1] = ex + a;
 }

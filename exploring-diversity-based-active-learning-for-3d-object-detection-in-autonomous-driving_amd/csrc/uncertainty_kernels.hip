@@ -5,7 +5,7 @@
 // Reference: det3d/selectors/entropy_selector.py:50-86,121-147, badge_selector.py:50-90,
 // uwe_selector.py:51-111.
 #include "al3d_common.h"
-#include "al3d_sort_key.h"
+#include "al3d_select.h"
 
 // H = -s log s - (1-s) log(1-s), mean over the kept boxes of the frame; empty frame -> NaN
 // (torch.mean of an empty tensor).
@@ -97,26 +97,15 @@ extern "C" int al3d_minmax_norm_f32(const float* x, int64_t n, float* out, void*
 }
 
 // argsort descending (torch.argsort(-x)): NaN last, equal values (+0.0 and -0.0 included) by
-// ascending index.  Keys from al3d_sort_key.h, bitonic sort by one workgroup.
+// ascending index.  Keys from al3d_sort_key.h, sorted by one workgroup (al3d_select.h).
 __global__ __launch_bounds__(1024) void argsort_desc_kernel(const float* __restrict__ x, int64_t n, int64_t np2,
                                                             unsigned long long* __restrict__ keys,
                                                             int64_t* __restrict__ out)
 {
     for (int64_t i = threadIdx.x; i < np2; i += 1024) keys[i] = i < n ? al3d_sort_key(x[i], (unsigned)i) : 0ull;
     __syncthreads();
-    for (int64_t size = 2; size <= np2; size <<= 1)
-        for (int64_t stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int64_t i = threadIdx.x; i < np2; i += 1024) {
-                const int64_t j = i ^ stride;
-                if (j > i) {
-                    const bool desc = (i & size) == 0;
-                    const unsigned long long a = keys[i], b = keys[j];
-                    if (desc ? a < b : a > b) { keys[i] = b; keys[j] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    for (int64_t i = threadIdx.x; i < n; i += 1024) out[i] = (int64_t)(0xffffffffu - (unsigned)(keys[i] & 0xffffffffull));
+    blk_sort_desc_u64<1024>(keys, np2);
+    for (int64_t i = threadIdx.x; i < n; i += 1024) out[i] = (int64_t)sel_word_index(keys[i]);
 }
 
 extern "C" int64_t al3d_argsort_workspace_bytes(int64_t n)

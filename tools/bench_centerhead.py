@@ -11,11 +11,13 @@ reference calls a CUDA kernel (``nms_gpu``) and copies its mask to the host; the
 port, against the fused call WITH its suppression.
 
 Each side runs in a child process of its own under its own time limit: warm-up, then rounds of timed calls, host clock
-around work that ends in a device synchronise; the median and the spread of the rounds are printed as one JSON line.
+around work that ends in a device synchronise; the median and the spread of the rounds are printed as one JSON line, with
+a ``digest`` of the last call's boxes, scores and labels, so that two builds of the library can be compared bit for bit.
 
   python tools/bench_centerhead.py [--batch 16] [--size 180] [--rounds 7] [--calls 10]
 """
 import argparse
+import hashlib
 import json
 import os
 import statistics
@@ -151,7 +153,11 @@ def child(side, kind, B, size, rounds, calls):
                 out = fn(h, rows, kind)
             torch.cuda.synchronize()
             ms.append((time.perf_counter() - t0) * 1e3 / calls)
-    print(json.dumps(dict(side=side, nms=kind, batch=B, size=size, ms_per_batch=round(statistics.median(ms), 3),
+    h = hashlib.sha256()
+    for o in out:
+        for t in o:
+            h.update(t.detach().cpu().contiguous().numpy().tobytes())
+    print(json.dumps(dict(side=side, nms=kind, batch=B, size=size, digest=h.hexdigest()[:16], ms_per_batch=round(statistics.median(ms), 3),
                           ms_min=round(min(ms), 3), ms_max=round(max(ms), 3), rounds=rounds, calls_per_round=calls,
                           detections_per_sample=round(sum(len(o[1]) for o in out) / B, 1))))
 
