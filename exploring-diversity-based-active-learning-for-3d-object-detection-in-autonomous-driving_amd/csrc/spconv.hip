@@ -778,6 +778,7 @@ extern "C" int al3d_sp_conv_f32(const float* fin, const int* nbr, int K, const f
     hipStream_t s = (hipStream_t)stream;
     SP_DISPATCH(5, 16) SP_DISPATCH(4, 16) SP_DISPATCH(16, 16) SP_DISPATCH(16, 32) SP_DISPATCH(32, 32)
     SP_DISPATCH(32, 64) SP_DISPATCH(64, 64) SP_DISPATCH(64, 128) SP_DISPATCH(128, 128)
+    SP_DISPATCH(128, 16)        // SpMiddleFHD behind a 128-channel VFE reader (SECOND): its first layer, in every arithmetic
     return al3d_fail(AL3D_EINVAL, "al3d_sp_conv_f32: unsupported channel pair %d -> %d", cin, cout);
 }
 

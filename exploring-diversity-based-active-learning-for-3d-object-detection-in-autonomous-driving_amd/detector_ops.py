@@ -1233,6 +1233,59 @@ class PillarNet:
         return self._dynamic(points, point2voxel, mean, coords, int(batch), int(ny), int(nx), True, check, **shape)
 
 
+# ------------------------------------------------------------------ fused VFE reader
+class VfeNet:
+    """Folded layers of a ``VoxelFeatureExtractor`` / ``VoxelFeatureExtractorV2`` for ``al3d_vfe_net_*`` (csrc/vfe.hip).
+    ``layers``: ``(linear, norm)`` pairs in eval mode, the one or two VFE layers first and the final linear last; a norm
+    without running statistics (``use_norm=False``) folds to scale 1, shift ``linear.bias``.  Weights are transposed to
+    [in, units]."""
+
+    def __init__(self, layers, with_distance, device):
+        if not 2 <= len(layers) <= 3:
+            raise lib.Al3dError(f"VfeNet: 1 or 2 VFE layers + the final linear supported, got {len(layers)} layers")
+        self.packs = []
+        for lin, bn in layers:
+            units = lin.weight.shape[0]
+            if isinstance(bn, torch.nn.BatchNorm1d):
+                scale, shift = fold_bn(bn, lin.bias)
+            else:
+                scale = torch.ones(units, dtype=torch.float32)
+                shift = (lin.bias.detach().float().cpu() if lin.bias is not None else torch.zeros(units)).contiguous()
+            w = lin.weight.detach().float().t().contiguous()
+            self.packs.append((w.to(device), scale.to(device), shift.to(device), units))
+        for _, _, _, units in self.packs[:-1]:
+            if units % 16 or not 16 <= units <= 64:
+                raise lib.Al3dError(f"VfeNet: a VFE layer has {units} units; the kernel needs a multiple of 16 in [16, 64]")
+        self.with_distance = int(bool(with_distance))
+        self.channels = self.packs[-1][3]
+        if self.channels != 2 * self.packs[-2][3]:
+            raise lib.Al3dError(f"VfeNet: the final linear has {self.channels} units, the last VFE layer gives "
+                                f"{2 * self.packs[-2][3]}")
+
+    def rows(self, voxels, num_points, voxels_per_wave=None, max_blocks=None):
+        """-> [M, C] voxel features; ``voxels_per_wave`` / ``max_blocks`` state the launch shape (same bits)."""
+        voxels = _dev(voxels, torch.float32, "voxels").contiguous()
+        num_points = _dev(num_points.to(torch.int32), torch.int32, "num_points").contiguous()
+        if voxels.dim() != 3 or num_points.numel() != voxels.shape[0]:
+            raise lib.Al3dError(f"VfeNet: voxels {tuple(voxels.shape)} (need [M, T, F]), num_points "
+                                f"{tuple(num_points.shape)}")
+        M, T, F = voxels.shape
+        w1, s1, b1, u1 = self.packs[0]
+        if w1.shape[0] != F + 3 + self.with_distance:
+            raise lib.Al3dError(f"VfeNet: {F} point features need a first layer of {F + 3 + self.with_distance} inputs, "
+                                f"got {w1.shape[0]}")
+        w2, s2, b2, u2 = self.packs[1] if len(self.packs) == 3 else (None, None, None, 0)
+        w3, s3, b3, c = self.packs[-1]
+        out = torch.empty((M, c), dtype=torch.float32, device=voxels.device)
+        args = (_ptr(voxels), _ptr(num_points), M, T, F, self.with_distance, _ptr(w1), _ptr(s1), _ptr(b1), u1,
+                _ptr(w2), _ptr(s2), _ptr(b2), u2, _ptr(w3), _ptr(s3), _ptr(b3), c, _ptr(out))
+        if voxels_per_wave is None and max_blocks is None:
+            lib.call("al3d_vfe_net_f32", *args, _stream())
+        else:
+            lib.call("al3d_vfe_net_launch_f32", *args, int(voxels_per_wave or 0), int(max_blocks or 0), _stream())
+        return out
+
+
 def pillar_scatter(rows, coords, batch, ny, nx):
     """PointPillarsScatter: rows [M, C] at coords (b, z, y, x) -> NHWC canvas [batch, ny, nx, C], zero elsewhere."""
     rows = _dev(rows, torch.float32, "rows").contiguous()

@@ -1,8 +1,9 @@
 from .registry import (BACKBONES, DETECTORS, ESTIMATORS, HEADS, LOSSES, NECKS, READERS,
                        ROI_EXTRACTORS, SHARED_HEADS)
 from .builder import build_backbone, build_detector, build_estimator, build_head, build_neck, build_reader
-from .readers import DynamicPillarFeatureNet, PillarFeatureNet, VoxelFeatureExtractorV3
-from .backbones import FPNSpMiddleResNetFHD, PointPillarsScatter, SparseTensor
+from .readers import (DynamicPillarFeatureNet, PillarFeatureNet, SimpleVoxel, VFELayer, VFEV3_ablation,
+                      VoxelFeatureExtractor, VoxelFeatureExtractorV2, VoxelFeatureExtractorV3)
+from .backbones import FPNSpMiddleResNetFHD, PointPillarsScatter, SparseTensor, SpMiddleFHD, SpMiddleResNetFHD
 from .necks import RPN
 from .bbox_heads import Head, MultiGroupHead
 from .detectors import FPNVoxelNet, PointPillars, VoxelNet

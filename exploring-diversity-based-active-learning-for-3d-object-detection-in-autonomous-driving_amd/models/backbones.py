@@ -294,6 +294,22 @@ class _SparseEncoderBase(nn.Module):
         last = middle[-1]
         return SparseTensor(feats, last.indices, last.spatial_shape, batch_size), middle
 
+    def rulebook_for(self, coors, batch_size, input_shape, frame_rows_max=0, neck_rows=False):
+        return self.build_rulebook(coors, batch_size, np.array(input_shape[::-1]) + [1, 0, 0], frame_rows_max, neck_rows)
+
+    def _forward(self, voxel_features, coors, batch_size, input_shape, book=None, frame_rows_max=0, neck_rows=False):
+        """-> (dense NHWC map or ``detector_ops.BevRows``, the stages' SparseTensors) on the reference's sparse shape
+        ``input_shape[::-1] + [1, 0, 0]``."""
+        sparse_shape = np.array(input_shape[::-1]) + [1, 0, 0]
+        if book is None:
+            book = self.build_rulebook(coors, batch_size, sparse_shape, frame_rows_max, neck_rows)
+        final, middle = self._run(voxel_features, coors, batch_size, sparse_shape, book=book)
+        index = book.get("bev_index")
+        if index is not None:
+            rows = D.BevRows(final.features, final.indices, index)
+            return (rows if neck_rows else rows.dense()), middle
+        return self.dense_nhwc(final, out=book.pop("dense", None)), middle
+
     @staticmethod
     def dense_nhwc(sp, out=None):
         """``ret.dense()`` + ``view(N, C*D, H, W)`` in NHWC: [B, H, W, C*D], channel = c*D + z.
@@ -329,22 +345,70 @@ class FPNSpMiddleResNetFHD(_SparseEncoderBase):
     def _stages(self):
         return [self.middle_conv0, self.middle_conv1, self.middle_conv2, self.middle_conv3]
 
-    def rulebook_for(self, coors, batch_size, input_shape, frame_rows_max=0, neck_rows=False):
-        return self.build_rulebook(coors, batch_size, np.array(input_shape[::-1]) + [1, 0, 0], frame_rows_max, neck_rows)
-
     def forward(self, voxel_features, coors, batch_size, input_shape, book=None, frame_rows_max=0, neck_rows=False):
         """-> (dense NHWC [B,128,128,256], middle list of 4 SparseTensor) -- the reference
         returns NCHW (scn.py:371-392); this build keeps activations channels-last.  ``neck_rows=True`` (a caller whose
         neck takes it): a ``detector_ops.BevRows`` in place of the dense map when the book carries the row index."""
-        sparse_shape = np.array(input_shape[::-1]) + [1, 0, 0]
-        if book is None:
-            book = self.build_rulebook(coors, batch_size, sparse_shape, frame_rows_max, neck_rows)
-        final, middle = self._run(voxel_features, coors, batch_size, sparse_shape, book=book)
-        index = book.get("bev_index")
-        if index is not None:
-            rows = D.BevRows(final.features, final.indices, index)
-            return (rows if neck_rows else rows.dense()), middle
-        return self.dense_nhwc(final, out=book.pop("dense", None)), middle
+        return self._forward(voxel_features, coors, batch_size, input_shape, book, frame_rows_max, neck_rows)
+
+
+class _SingleStageEncoder(_SparseEncoderBase):
+    """det3d's encoders that are ONE ``middle_conv`` sequence (scn.py:100-205, 395-457): the state-dict keys are the
+    reference's ``middle_conv.<i>.*``.  Same call as the FPN encoder (``book``, ``frame_rows_max``, ``neck_rows``,
+    ``rulebook_for``), but like the reference they return the dense map alone -- there is no ``middle``."""
+
+    def _stages(self):
+        return [self.middle_conv]
+
+    def forward(self, voxel_features, coors, batch_size, input_shape, book=None, frame_rows_max=0, neck_rows=False):
+        """-> dense NHWC [B, H, W, C*D] with channel = c*D + z (the reference returns NCHW, scn.py:192-205), or a
+        ``detector_ops.BevRows`` under ``neck_rows=True`` when the book carries the row index."""
+        return self._forward(voxel_features, coors, batch_size, input_shape, book, frame_rows_max, neck_rows)[0]
+
+
+@BACKBONES.register_module
+class SpMiddleResNetFHD(_SingleStageEncoder):
+    """The residual encoder without the FPN taps (reference scn.py:395-457; the model of ``cbgs_full.py``): the layers
+    of ``FPNSpMiddleResNetFHD`` in one sequence -- convs at ``middle_conv.{0,5,10,15,20}``, ``SparseBasicBlock`` s at
+    ``{3,4,8,9,13,14,18,19}``."""
+
+    def __init__(self, num_input_features=128, norm_cfg=None, name="SpMiddleResNetFHD", **kwargs):
+        super().__init__()
+        self.name = name
+        self.middle_conv = nn.Sequential(
+            SubMConv3d(num_input_features, 16, 3, bias=False, indice_key="res0"), _bn(16), nn.ReLU(),
+            SparseBasicBlock(16, 16, indice_key="res0"), SparseBasicBlock(16, 16, indice_key="res0"),
+            SparseConv3d(16, 32, 3, 2, padding=1, bias=False), _bn(32), nn.ReLU(),
+            SparseBasicBlock(32, 32, indice_key="res1"), SparseBasicBlock(32, 32, indice_key="res1"),
+            SparseConv3d(32, 64, 3, 2, padding=1, bias=False), _bn(64), nn.ReLU(),
+            SparseBasicBlock(64, 64, indice_key="res2"), SparseBasicBlock(64, 64, indice_key="res2"),
+            SparseConv3d(64, 128, 3, 2, padding=[0, 1, 1], bias=False), _bn(128), nn.ReLU(),
+            SparseBasicBlock(128, 128, indice_key="res3"), SparseBasicBlock(128, 128, indice_key="res3"),
+            SparseConv3d(128, 128, (3, 1, 1), (2, 1, 1), bias=False), _bn(128), nn.ReLU())
+
+
+@BACKBONES.register_module
+class SpMiddleFHD(_SingleStageEncoder):
+    """SECOND's plain encoder (reference scn.py:100-205): fourteen bias-free conv + BN + ReLU triples at
+    ``middle_conv.{0,3,...,39}``, channels 16,16 | 32,32,32 | 64,64,64,64 | 64,64,64,64; the dense map has
+    64 * 2 = 128 channels."""
+
+    def __init__(self, num_input_features=128, norm_cfg=None, name="SpMiddleFHD", **kwargs):
+        super().__init__()
+        self.name = name
+
+        def subm(cin, cout, key):
+            return [SubMConv3d(cin, cout, 3, bias=False, indice_key=key), _bn(cout), nn.ReLU()]
+
+        def down(cin, cout, k=3, s=2, p=1):
+            return [SparseConv3d(cin, cout, k, s, padding=p, bias=False), _bn(cout), nn.ReLU()]
+
+        self.middle_conv = nn.Sequential(
+            *subm(num_input_features, 16, "subm0"), *subm(16, 16, "subm0"),
+            *down(16, 32), *subm(32, 32, "subm1"), *subm(32, 32, "subm1"),
+            *down(32, 64), *subm(64, 64, "subm2"), *subm(64, 64, "subm2"), *subm(64, 64, "subm2"),
+            *down(64, 64, p=[0, 1, 1]), *subm(64, 64, "subm3"), *subm(64, 64, "subm3"), *subm(64, 64, "subm3"),
+            *down(64, 64, (3, 1, 1), (2, 1, 1), 0))
 
 
 @BACKBONES.register_module

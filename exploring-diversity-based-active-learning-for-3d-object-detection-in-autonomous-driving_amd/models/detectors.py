@@ -77,13 +77,29 @@ class FPNVoxelNet(SingleStageDetector):
         return bool(self.neck_rows and self.with_neck and hasattr(self.neck, "rows_input_ok") and
                     "neck_rows" in inspect.signature(self.backbone.forward).parameters and self.neck.rows_input_ok())
 
+    def _input_features(self, data):
+        """The encoder's input rows.  A mean reader's (``mean_reader``, VoxelFeatureExtractorV3) output is what the device
+        voxelizer already emits as ``voxel_features``: that shortcut is taken only for such a reader.  Any other reader
+        runs on the padded point slots, which the loader yields under ``with_points=True``."""
+        if getattr(self.reader, "mean_reader", False) and data.get("mean_features") is not None:
+            return data["mean_features"]
+        if data.get("features") is None or data.get("num_voxels") is None:
+            raise RuntimeError(f"{type(self).__name__} with a {type(self.reader).__name__} reader needs the padded point "
+                               "slots (voxels, num_points): build the loader with with_points=True")
+        return self.reader(data["features"], data["num_voxels"])
+
+    @staticmethod
+    def _map_and_middle(out):
+        """An encoder returns (map, middle) -- the FPN encoder -- or, like the reference's SpMiddleFHD /
+        SpMiddleResNetFHD, the map alone: ``middle`` then starts empty (the neck's output is still appended)."""
+        if isinstance(out, tuple):
+            return out[0], out[1]
+        return out, []
+
     def extract_feat(self, data):
-        if data.get("mean_features") is not None:     # device voxelizer already reduced the points
-            input_features = data["mean_features"]
-        else:
-            input_features = self.reader(data["features"], data["num_voxels"])
-        x, middle = self.backbone(input_features, data["coors"], data["batch_size"], data["input_shape"],
-                                  **self._cap_kw(data.get("voxel_cap", 0)))
+        input_features = self._input_features(data)
+        x, middle = self._map_and_middle(self.backbone(input_features, data["coors"], data["batch_size"],
+                                                       data["input_shape"], **self._cap_kw(data.get("voxel_cap", 0))))
         if self.with_neck:
             x = self.neck(x)
             middle.append(NHWCFeature(x, getattr(self.neck, "embedding", None)))
@@ -118,15 +134,12 @@ class FPNVoxelNet(SingleStageDetector):
         data = dict(features=example.get("voxels"), num_voxels=example.get("num_points"),
                     mean_features=example.get("voxel_features"), coors=example["coordinates"],
                     batch_size=len(num_voxels), input_shape=example["shape"][0], voxel_cap=example.get("voxel_cap", 0))
-        if data.get("mean_features") is not None:     # device voxelizer already reduced the points
-            input_features = data["mean_features"]
-        else:
-            input_features = self.reader(data["features"], data["num_voxels"])
+        input_features = self._input_features(data)
         if book is not None:
-            return self.backbone(input_features, data["coors"], data["batch_size"], data["input_shape"], book=book,
-                                 **rows_kw)
-        return self.backbone(input_features, data["coors"], data["batch_size"], data["input_shape"],
-                             **self._cap_kw(data["voxel_cap"]), **rows_kw)
+            return self._map_and_middle(self.backbone(input_features, data["coors"], data["batch_size"],
+                                                      data["input_shape"], book=book, **rows_kw))
+        return self._map_and_middle(self.backbone(input_features, data["coors"], data["batch_size"], data["input_shape"],
+                                                  **self._cap_kw(data["voxel_cap"]), **rows_kw))
 
     def dense_stage(self, example, x, middle, finetune=False, **kwargs):
         pair = False
@@ -163,7 +176,10 @@ class FPNVoxelNet(SingleStageDetector):
 
 @DETECTORS.register_module
 class VoxelNet(FPNVoxelNet):
-    """Same graph; ``forward`` returns detections only (voxelnet.py:8-55)."""
+    """Same graph; ``forward`` returns detections only (voxelnet.py:8-55).  The reference's ``VoxelNet.extract_feat``
+    calls its reader with two arguments (voxelnet.py:24), which its own ``VoxelFeatureExtractor`` -- three positional
+    parameters -- does not accept; here every reader takes ``coors=None``, so SECOND's learned reader runs under this
+    detector too."""
 
     def forward(self, example, return_loss=True, **kwargs):
         kwargs.pop("estimate", None)

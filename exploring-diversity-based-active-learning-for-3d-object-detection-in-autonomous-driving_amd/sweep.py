@@ -159,6 +159,16 @@ def _tensors_of(obj):
                 yield from _tensors_of(v)
 
 
+def _estimate(detector, example, **kw):
+    """``detector(example, return_loss=False, estimate=True)`` -> (preds, middle).  det3d's ``VoxelNet.forward`` drops
+    ``estimate`` and returns the detections alone (voxelnet.py:31-55); the sweep runs the graph it shares with
+    ``FPNVoxelNet``, whose ``middle`` ends in the neck's output."""
+    from .models.detectors import FPNVoxelNet, VoxelNet
+    if isinstance(detector, VoxelNet):
+        return FPNVoxelNet.forward(detector, example, return_loss=False, estimate=True, **kw)
+    return detector(example, return_loss=False, estimate=True, **kw)
+
+
 # report of the last sweep_embeddings call on this rank: math, batches, recovered_batches (batch ordinals), tripped_frames
 # (dataset indices of the non-finite rows), recovered_frames (every frame of the re-run batches)
 LAST_SWEEP = {}
@@ -245,7 +255,7 @@ def sweep_embeddings(detector, dataloader, device, num_frames=None, with_entropy
             with torch.cuda.stream(main):
                 t[0].record(main)
                 # no `book`: the batch's rulebook was built for the f16x3 kernels (raster level 0, tiled tables)
-                preds, middle = detector(example, return_loss=False, estimate=True)
+                preds, middle = _estimate(detector, example)
                 emb, ent, _ = outputs(preds, middle)
                 t[1].record(main)
         finally:
@@ -269,7 +279,7 @@ def sweep_embeddings(detector, dataloader, device, num_frames=None, with_entropy
         if mode is None:
             for data_batch in dataloader:
                 example = example_to_device(data_batch, device, non_blocking=False)
-                preds, middle = detector(example, return_loss=False, estimate=True)
+                preds, middle = _estimate(detector, example)
                 finish(example, preds, middle)
                 if checks:
                     torch.cuda.current_stream(device).synchronize()
@@ -328,7 +338,7 @@ def sweep_embeddings(detector, dataloader, device, num_frames=None, with_entropy
                                       _side.wait_event(e_)
                               bb.stage_hook = _hook
                           try:
-                              preds, middle = detector(example, return_loss=False, estimate=True, book=ahead)
+                              preds, middle = _estimate(detector, example, book=ahead)
                           finally:
                               if bb is not None and SIDE_AFTER_STAGE >= 0:
                                   bb.stage_hook = None

@@ -711,6 +711,35 @@ int al3d_pillar_net_dynamic_launch_f32(const float* points, const int* point2vox
                                        int nx, float* out, int canvas, void* workspace, int* status, int chunk_points,
                                        int max_blocks, void* stream);
 
+/* ---------------------------------------------------------------- detector: fused VFE reader (f32)
+ * VoxelFeatureExtractor.forward / VoxelFeatureExtractorV2.forward + VFELayer.forward
+ * (det3d/models/readers/voxel_encoder.py:13-176), eval mode, BatchNorm folded, on the voxelizer's padded slots:
+ * voxels [M,T,F] f32 (slots at or past num_points are zero and are not read), num_points [M] i32, n = clip(num_points,
+ * 0, T).  mean = (f32 sum of xyz over slots 0..n-1 in ascending slot order) / (float)max(n, 1); a real slot is
+ * [f_0..f_{F-1}, xyz - mean, |xyz| if with_distance].  Padded slots are NOT masked in front of the first layer
+ * (voxel_encoder.py:98-99 applies the mask after vfe1): each enters vfe1 as [0..0, -mean, (0)] and its
+ * relu(linear * s1 + b1) takes part in vfe1's max over all T slots.  After vfe1 the padded rows are zero (pointwise and
+ * repeated max alike): in vfe2 they hold relu(b2) and take part in its max; after the last linear they are zero, so the
+ * final max runs over the real rows and, when n < T, one 0.  Deviation: the reference divides by zero for n = 0 (NaN);
+ * here such a row is computed as if every slot were padded (it comes out 0).
+ * Layer l: h = relu(fma(dot, s_l, b_l)) with dot accumulated by fmaf in ascending k; agg = max over the T slots; the next
+ * layer reads [h, agg].  use_norm=False is s = 1, b = linear.bias.  w1 [F+3+wd, U1], w2 [2*U1, U2] (NULL: one VFE layer)
+ * and w3 [C, C] are the linear weights transposed; C = 2*U2 (or 2*U1).  Limits: 1 <= T <= 64; 3 <= F <= 10; U1, U2
+ * multiples of 16 in [16, 64]; C twice the last VFE layer's units.  M == 0 launches nothing.  out [M, C].
+ * One launch, no per-slot activation in HBM, no atomics: a row depends on its own voxel and the parameters only and is
+ * bit-identical for every launch shape and every position of the voxel in the batch. */
+int al3d_vfe_net_f32(const float* voxels, const int* num_points, int64_t M, int T, int F, int with_distance,
+                     const float* w1, const float* s1, const float* b1, int U1, const float* w2, const float* s2,
+                     const float* b2, int U2, const float* w3, const float* s3, const float* b3, int C, float* out,
+                     void* stream);
+/* The same call with the launch shape stated: at most voxels_per_wave voxels side by side in a wave (0: the default, 2;
+ * at most 16; fewer where LDS runs out) and at most max_blocks persistent blocks (0: what the chip holds at once).  The
+ * result does not depend on either; the tests vary them. */
+int al3d_vfe_net_launch_f32(const float* voxels, const int* num_points, int64_t M, int T, int F, int with_distance,
+                            const float* w1, const float* s1, const float* b1, int U1, const float* w2, const float* s2,
+                            const float* b2, int U2, const float* w3, const float* s3, const float* b3, int C,
+                            float* out, int voxels_per_wave, int max_blocks, void* stream);
+
 /* ---------------------------------------------------------------- camera branch: BEV pooling (f4)
  * bevfusion/mmdet3d/models/vtransforms/base.py:127-163 (`bev_pool`: cell = ((geom - (bx - dx/2)) / dx).long(),
  * points outside the grid dropped) + ops/bev_pool/bev_pool.py:82-97 + src/bev_pool_cuda.cu:21-44 (sum of the points

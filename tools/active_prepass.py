@@ -47,6 +47,7 @@ def main():
     from al3d import synthetic
     from al3d.datasets import DeviceSweepLoader, FileSweepLoader, PoolFrames, generate_task_anchors
     from al3d.models import build_detector
+    from al3d.models.readers import needs_point_slots
     from al3d.selectors import prepass as P
     from al3d.utils import Config, fileio
 
@@ -87,7 +88,7 @@ def main():
     head_cfg = cfg.model.get("bbox_head")
     anchors = generate_task_anchors(cfg.tasks, cfg.target_assigner.anchor_generators, [1, 128, 128]) \
         if head_cfg is not None and head_cfg.get("type") == "MultiGroupHead" else None
-    with_points = cfg.model.get("reader", {}).get("type") == "PillarFeatureNet"
+    with_points = needs_point_slots(cfg.model.get("reader"))
     # DynamicPillarFeatureNet pools over the batch's points by point2voxel: no padded slots, the points themselves
     keep_points = cfg.model.get("reader", {}).get("type") == "DynamicPillarFeatureNet"
     if args.synthetic_scenes:

@@ -107,6 +107,7 @@ def main():
     if args.pred:
         from al3d.datasets import DeviceSweepLoader, PoolFrames, generate_task_anchors
         from al3d.models import build_detector
+        from al3d.models.readers import needs_point_slots
         dev = torch.device("cuda", local_rank)
         model = build_detector(cfg.model, train_cfg=None, test_cfg=cfg.test_cfg)
         if args.checkpoint:
@@ -137,8 +138,8 @@ def main():
         head_cfg = cfg.model.get("bbox_head")
         anchors = generate_task_anchors(cfg.tasks, cfg.target_assigner.anchor_generators, [1, 128, 128]) \
             if head_cfg is not None and head_cfg.get("type") == "MultiGroupHead" else None      # TransFusionHead is anchor-free
-        # PillarFeatureNet reads the padded point slots of each pillar, not the voxelizer's mean
-        with_points = cfg.model.get("reader", {}).get("type") == "PillarFeatureNet"
+        # a reader that reads the padded point slots (PillarFeatureNet, the VFE readers) says so in its class attribute
+        with_points = needs_point_slots(cfg.model.get("reader"))
         # DynamicPillarFeatureNet pools over the batch's points by point2voxel: no padded slots, the points themselves
         dyn_points = cfg.model.get("reader", {}).get("type") == "DynamicPillarFeatureNet"
         if args.synthetic_scenes and cfg.model.get("type") == "BEVFusion":
