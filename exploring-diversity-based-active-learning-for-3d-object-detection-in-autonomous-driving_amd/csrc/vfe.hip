@@ -14,6 +14,13 @@
 //     the row is 0.
 //   - layer l: h = relu(fma(dot, s_l, b_l)), dot accumulated by fmaf in ascending k; agg = max over the T slots; the next
 //     layer reads [h, agg].
+//   - NaN input (a deviation: the reference's relu / max give the voxel a NaN row).  ReLU is fmaxf(pre, 0), which drops a
+//     NaN operand, so a NaN pre-activation gives 0 and no NaN outlives vfe1.  A NaN in a feature past xyz makes its own
+//     slot's vfe1 pre-activations NaN in every unit (NaN * w is NaN, whatever w): that slot's vfe1 row is 0, the others
+//     are untouched.  A NaN in x, y or z also makes the mean NaN and with it xyz - mean of every real slot and -mean of
+//     the padded representative: all vfe1 rows and vfe1's max are 0, and the voxel goes on as if vfe1 had given 0
+//     everywhere.  The row is finite either way; other voxels are never touched.  inf follows IEEE arithmetic through
+//     the chains (inf - inf and 0 * inf give NaN, then the rule above) and is not pinned beyond staying in its voxel.
 //
 // Shape: persistent workgroups of up to eight wave64, all folded weights resident in LDS (w3 alone is 64 KB at C = 128).
 // A wave takes V consecutive voxels at a time and keeps their rows in its own LDS region; nothing per slot goes to HBM.

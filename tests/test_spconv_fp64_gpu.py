@@ -36,7 +36,8 @@ GEOMS = {"subm": ((3, 3, 3), (1, 1, 1), (0, 0, 0), True),
 F32 = (False, True)                                  # VALU f32, f32 MFMA
 BF16X6 = ("bf16x6", "wave", "wave2")
 F16X3 = ("wave2_f16x3", "wave2_f16x3_tiles", "glds_f16x3", "rng_f16x3", "blk_f16x3", "r16_f16x3")
-PAIRS = [(5, 16), (16, 16), (16, 32), (32, 32), (32, 64), (64, 64), (64, 128), (128, 128)]
+# (128, 16): SpMiddleFHD's first layer behind a 128-channel VFE reader; no matrix-core structure, the VALU kernel alone
+PAIRS = [(5, 16), (16, 16), (16, 32), (32, 32), (32, 64), (64, 64), (64, 128), (128, 128), (128, 16)]
 
 
 def structures(cin, cout, geom):
@@ -222,7 +223,7 @@ def _edge_coords(rng, name, shape, batch):
 EDGE_CASES = ["faces", "single", "empty_frame", "block5"] + [f"n{m}" for m in (31, 32, 33, 127, 128, 129, 255, 256, 257)]
 # (geometry, channel pair) runs of each edge case: between them every structure runs at least once
 EDGE_RUNS = [("subm", 16, 16), ("subm", 64, 64), ("subm", 128, 128), ("down", 16, 32), ("down011", 32, 64),
-             ("down311", 64, 128)]
+             ("down311", 64, 128), ("subm", 128, 16)]
 
 
 @pytest.mark.parametrize("name", EDGE_CASES)

@@ -4,7 +4,11 @@
 Accuracy: e = max |got - ref64| / absum, absum the abs chain through decoration and all layers (vfe_fp64.vfe_net).  The
 bound is the first-order worst case of the f32 chains, not a measured number: B = 1.25 * (T + K1 + K2 + K3 + 5) * 2^-24
 with K_l the layers' input widths (vfe_fp64.bound): every dot of length K rounds at most K times plus the fold FMA, the
-mean at most T + 1 times, the subtraction once; ReLU and max are exact; 1.25 covers the second-order terms."""
+mean at most T + 1 times, the subtraction once; ReLU and max are exact; 1.25 covers the second-order terms.
+
+Beside B, the tight gate e <= 3 e32 + 1e-8: e32 is the largest error of three float32 evaluations of the same formula on
+the same case (vfe_fp64.e32, computed on the host, never from the kernel); factor and floor are the split rule of
+tests/test_spconv_fp64_gpu.py.  B alone lets a kernel thousands of times less accurate than float32 through."""
 import os
 
 import numpy as np
@@ -45,6 +49,12 @@ def _err(got, ref, absum):
     return float((np.abs(got.astype(np.float64) - ref) / absum).max()) if ref.size else 0.0
 
 
+def _tight(tag, e, vox, num, layers, wd, ref, absum):
+    e32 = V.e32(vox, num, layers, wd, ref, absum)
+    print(f"{tag}: e = {e:.3e}, e32 = {e32:.3e}, 3 e32 + 1e-8 = {V.gate(e32):.3e}")
+    assert e <= V.gate(e32), f"{tag}: e = {e:.3e} > 3 e32 + 1e-8 = {V.gate(e32):.3e} (e32 = {e32:.3e})"
+
+
 # ---------------------------------------------------------------- the reference's own outputs
 def _golden(tag):
     c = [int(v) for v in G[f"{tag}.config"]]
@@ -73,6 +83,7 @@ def test_module_matches_reference_and_fp64(tag):
     print(f"{tag}: e = {e:.3e}, B = {B:.3e}")
     assert got.shape == ref.shape
     assert e <= B, f"e = {e:.3e} > B = {B:.3e}"
+    _tight(tag, e, vox, num, layers, cfg["wd"], ref, absum)
     assert (np.abs(got - G[f"{tag}.out"]) <= 2 * B * absum).all()
 
 
@@ -104,6 +115,7 @@ def test_kernel_matches_fp64(T, filters, scale):
         print(f"T {T} F {F} filters {filters} scale {scale}: e = {e:.3e}, B = {B:.3e}")
         assert got.shape == ref.shape == (257, filters[-1])
         assert e <= B, f"F {F}: e = {e:.3e} > B = {B:.3e}"
+        _tight(f"T {T} F {F} filters {filters} scale {scale}", e, vox, num, layers, F == 4, ref, absum)
         assert not got[0].any()                                   # count 0: every slot padded, the row is 0
         for m in (0, 1, 3):
             sub = mod(*_dev(vox[:m], num[:m]))
@@ -116,7 +128,9 @@ def test_use_norm_false_matches_fp64():
     assert "linear.bias" in mod.state_dict() and "norm.weight" not in mod.state_dict()
     got = mod(*_dev(vox, num)).cpu().numpy()
     ref, absum = V.vfe_net(vox, num, layers, True)
-    assert _err(got, ref, absum) <= V.bound(10, _widths(layers))
+    e = _err(got, ref, absum)
+    assert e <= V.bound(10, _widths(layers))
+    _tight("use_norm=False", e, vox, num, layers, True, ref, absum)
 
 
 def test_padded_slot_wins_vfe1_max():

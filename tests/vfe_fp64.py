@@ -12,9 +12,23 @@ all layers (sum |a||w| * |s| + |b|), taken as the maximum over the T slots at ev
 wins -- the normaliser of the GPU tests' error e = |got - ref| / absum.
 
 ``pad_in_max1=False`` restates the WRONG reading -- padded slots masked in front of vfe1, so only real slots enter its max
--- for the tests that must tell the two apart.
+-- for the tests that must tell the two apart.  ``pad_in_max2=False`` is the other wrong reading: the padded slots, which
+hold relu(b2) in a second VFE layer, left out of that layer's max.
+
+``nan_rule=True`` restates what the kernel documents for NaN input (csrc/vfe.hip): ReLU is fmax(pre, 0), so a NaN
+pre-activation gives 0.  A NaN in a feature past xyz therefore zeroes its own slot's vfe1 row; a NaN in x, y or z makes the
+mean NaN, which zeroes every real slot's vfe1 row and the padded slots' alike, so the voxel goes on as if vfe1 had given 0
+everywhere.  The reference (torch.relu, torch.max) gives NaN for such a voxel.  The abs chain drops the NaN terms with the
+values.
+
+``vfe_net_f32`` evaluates the same formula with every operation rounded to float32 (numpy float32 arrays, no fused
+multiply-add) in three accumulation orders; ``e32`` is the largest of their errors against ``vfe_net`` under the same
+``absum``: what a float32 evaluation of this formula costs on the case at hand, the yardstick of the GPU tests' tight gate
+e <= 3 e32 + 1e-8.  Neither calls the library.
 """
 import numpy as np
+
+ORDERS = ("ascending", "descending", "matmul")
 
 
 def fold_bn(gamma, beta, mean, var, eps):
@@ -37,9 +51,14 @@ def fold_layers(params, prefixes, eps=1e-3):
     return out
 
 
-def vfe_net(voxels, num_points, layers, with_distance, pad_in_max1=True):
+def vfe_net(voxels, num_points, layers, with_distance, pad_in_max1=True, pad_in_max2=True, nan_rule=False):
     """layers: [(W [units, in], scale [units], shift [units]), ...]: the one or two VFE layers, then the final linear.
     Returns (out [M, C], absum [M, C])."""
+    with np.errstate(invalid="ignore"):
+        return _vfe_net(voxels, num_points, layers, with_distance, pad_in_max1, pad_in_max2, nan_rule)
+
+
+def _vfe_net(voxels, num_points, layers, with_distance, pad_in_max1, pad_in_max2, nan_rule):
     v = np.asarray(voxels, np.float64)
     M, T, F = v.shape
     n = np.clip(np.asarray(num_points, np.int64), 0, T)
@@ -55,11 +74,15 @@ def vfe_net(voxels, num_points, layers, with_distance, pad_in_max1=True):
     x, ax = np.concatenate(parts, -1), np.concatenate(aparts, -1)
     for li, (w, scale, shift) in enumerate(layers):
         w = np.asarray(w, np.float64)
-        y = np.maximum(np.einsum("mtk,uk->mtu", x, w) * scale + shift, 0.0)
+        pre = np.einsum("mtk,uk->mtu", x, w) * scale + shift
         ay = np.einsum("mtk,uk->mtu", ax, np.abs(w)) * np.abs(scale) + np.abs(shift)
+        if nan_rule:
+            y, ay = np.fmax(pre, 0.0), np.where(np.isnan(ay), 0.0, ay)
+        else:
+            y = np.maximum(pre, 0.0)
         if li == len(layers) - 1:
             return (y * mask).max(1), ay.max(1)
-        if li == 0 and not pad_in_max1:
+        if (li == 0 and not pad_in_max1) or (li == 1 and not pad_in_max2):
             ymax = np.where(real[..., None], y, 0.0).max(1)
         else:
             ymax = y.max(1)
@@ -67,6 +90,67 @@ def vfe_net(voxels, num_points, layers, with_distance, pad_in_max1=True):
         x = np.concatenate([y, np.repeat(ymax[:, None, :], T, 1)], -1) * mask
         ax = np.concatenate([ay, np.repeat(amax[:, None, :], T, 1)], -1) * mask
     raise ValueError("no layers")
+
+
+def _dot32(x, w, order):
+    """[M, T, K] x [U, K] -> [M, T, U] in float32: every product rounded, then added to the rounded running sum."""
+    if order == "matmul":
+        return np.matmul(x, np.ascontiguousarray(w.T))
+    K = x.shape[-1]
+    acc = np.zeros(x.shape[:2] + (w.shape[0],), np.float32)
+    for k in (range(K) if order == "ascending" else range(K - 1, -1, -1)):
+        acc = acc + x[:, :, k, None] * w[None, None, :, k]
+    return acc
+
+
+def vfe_net_f32(voxels, num_points, layers, with_distance, order="ascending"):
+    """``vfe_net``'s formula (the right reading, finite input) with every operation rounded to float32: the folded scale
+    and shift rounded once, the mean summed in ascending slot order and divided by float32(max(n, 1)), every dot a
+    separate multiply and add per term in ``order`` -- "ascending" k, "descending" k, or "matmul" (numpy's float32
+    matmul, whatever order it takes) --, then * scale, + shift, ReLU, max.  Returns out [M, C] float32."""
+    assert order in ORDERS, order
+    f32 = np.float32
+    v = np.asarray(voxels, f32)
+    M, T, F = v.shape
+    n = np.clip(np.asarray(num_points, np.int64), 0, T)
+    real = np.arange(T)[None, :] < n[:, None]
+    mask = real.astype(f32)[..., None]
+    v = v * mask
+    total = np.zeros((M, 3), f32)
+    for p in range(T):
+        total = total + v[:, p, :3]
+    mean = (total / np.maximum(n, 1).astype(f32)[:, None])[:, None, :]
+    parts = [v, v[:, :, :3] - mean]
+    if with_distance:
+        sq = v[:, :, :3] * v[:, :, :3]
+        parts.append(np.sqrt((sq[..., 0] + sq[..., 1]) + sq[..., 2])[..., None])
+    x = np.concatenate(parts, -1)
+    assert x.dtype == f32
+    for li, (w, scale, shift) in enumerate(layers):
+        w, scale, shift = (np.asarray(a, np.float64).astype(f32) for a in (w, scale, shift))
+        y = np.maximum(_dot32(x, w, order) * scale + shift, f32(0))
+        assert y.dtype == f32
+        if li == len(layers) - 1:
+            return (y * mask).max(1)
+        x = np.concatenate([y, np.repeat(y.max(1)[:, None, :], T, 1)], -1) * mask
+    raise ValueError("no layers")
+
+
+def err(got, ref, absum):
+    """e = max |got - ref| / absum over the outputs (0 for no rows)."""
+    return float((np.abs(np.asarray(got, np.float64) - ref) / absum).max()) if ref.size else 0.0
+
+
+def e32(voxels, num_points, layers, with_distance, ref=None, absum=None):
+    """The largest error of the three float32 evaluations against the float64 reference, relative to ``absum``."""
+    if ref is None:
+        ref, absum = vfe_net(voxels, num_points, layers, with_distance)
+    return max(err(vfe_net_f32(voxels, num_points, layers, with_distance, o), ref, absum) for o in ORDERS)
+
+
+def gate(e_32):
+    """The tight gate of the GPU tests: 3 e32 + 1e-8 (the split rule of tests/test_spconv_fp64_gpu.py)."""
+    return 3.0 * e_32 + 1e-8
 
 
 def bound(T, widths):
