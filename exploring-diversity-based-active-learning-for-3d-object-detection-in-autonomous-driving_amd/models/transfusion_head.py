@@ -397,7 +397,8 @@ class TransFusionHead(nn.Module):
 
     def get_bboxes(self, preds_dicts):
         """transfusion.py:714-851 for one feature level: scores = sigmoid(heatmap) x query heatmap score x one-hot of
-        the query's class; decode; optional per-group circle NMS (nuScenes: pedestrians and cones, radius 0.175)."""
+        the query's class; decode; optional per-group circle NMS (nuScenes: pedestrians and cones, radius 0.175) or, for
+        any other ``nms_type`` ("rotate"), the rotated NMS of ``al3d.ops.iou3d.nms_gpu`` with the radius as IoU threshold."""
         p = preds_dicts[0]
         P = self.num_proposals
         # Post-processing on the HOST (round 5): the query decoder's outputs for a batch are a few hundred KB; one D2H
@@ -415,8 +416,10 @@ class TransFusionHead(nn.Module):
         temp = self._decode(score, host["rot"], host["dim"], host["center"], host["height"], host.get("vel"))
         if self.test_cfg.get("nms_type") is None:
             return self._to_device(temp, dev)
-        if self.test_cfg["nms_type"] != "circle":
-            raise NotImplementedError("only nms_type null / circle are built")
+        rotate = self.test_cfg["nms_type"] != "circle"         # transfusion.py:809-822: any other type is the rotated NMS
+        if rotate and torch.device(dev).type != "cuda":
+            from ..lib import Al3dError
+            raise Al3dError("TransFusionHead: nms_type other than circle runs the device NMS (no CPU fallback)")
         dataset = self.test_cfg.get("dataset", "nuScenes")
         if dataset == "nuScenes":                      # transfusion.py:751-771
             tasks = [dict(indices=[0, 1, 2, 3, 4, 5, 6, 7], radius=-1), dict(indices=[8], radius=0.175),
@@ -424,7 +427,7 @@ class TransFusionHead(nn.Module):
         elif dataset == "Waymo":                       # transfusion.py:772-779
             tasks = [dict(indices=[0], radius=0.7), dict(indices=[1], radius=0.7), dict(indices=[2], radius=0.7)]
         else:
-            raise NotImplementedError(f"circle NMS task table for dataset {dataset!r} (the reference knows nuScenes, Waymo)")
+            raise NotImplementedError(f"NMS task table for dataset {dataset!r} (the reference knows nuScenes, Waymo)")
         rets = []
         for t in temp:
             boxes3d, scores, labels = t["bboxes"], t["scores"], t["labels"]
@@ -434,7 +437,16 @@ class TransFusionHead(nn.Module):
                 for cls_idx in task["indices"]:
                     task_mask += labels == cls_idx
                 task_mask = task_mask.bool()
-                if task["radius"] > 0:
+                if task["radius"] > 0 and rotate:
+                    # LiDARInstance3DBoxes.bev = columns (0, 1, 3, 4, 6), xywhr2xyxyr, nms_gpu with thresh = the radius
+                    from ..ops.iou3d import nms_gpu
+                    bev = boxes3d[task_mask][:, [0, 1, 3, 4, 6]].to(dev)
+                    half = bev[:, 2:4] / 2
+                    rows = torch.cat([bev[:, :2] - half, bev[:, :2] + half, bev[:, 4:5]], dim=1)
+                    keep = nms_gpu(rows, scores[task_mask].to(dev), thresh=task["radius"],
+                                   pre_maxsize=self.test_cfg.get("pre_maxsize"),
+                                   post_max_size=self.test_cfg.get("post_maxsize")).cpu()
+                elif task["radius"] > 0:
                     dets = torch.cat([boxes3d[task_mask][:, :2], scores[:, None][task_mask]], dim=1)
                     keep = torch.tensor(circle_nms(dets.detach().numpy(), task["radius"]), dtype=torch.long)
                 else:

@@ -1,0 +1,7 @@
+"""Drop-in mirrors of the reference's box-geometry extensions on the HIP ops of ``selector_ops``:
+
+* ``al3d.ops.iou3d_nms``  for ``det3d.ops.iou3d_nms.iou3d_nms_utils``   (7-column boxes)
+* ``al3d.ops.iou3d``      for ``mmdet3d.ops.iou3d.iou3d_utils``         ([x1, y1, x2, y2, r] rows)
+* ``al3d.ops.rotate_iou`` for ``det3d.datasets.utils.kitti_object_eval_python.rotate_iou`` / ``eval`` (numpy in, numpy out)
+"""
+from . import iou3d, iou3d_nms, rotate_iou  # noqa: F401

@@ -226,6 +226,132 @@ def match_boxes(boxes, scores, labels, counts, ref_boxes, ref_labels, ref_scores
     return out
 
 
+# ---------------------------------------------------------------- rotated box IoU and NMS (al3d_box_iou_* / al3d_nms_boxes_*)
+BOX_CONVENTION = {"det3d": 0, "heading": 1}                      # AL3D_BOX_*
+BOX_LAYOUT = {"xyzwlhr": 0, "xyxyr": 1}                          # AL3D_BOX_ROWS_*
+IOU_HEIGHT = {"_bev": 0, "3d": 1, "3d_kitti": 2}                 # name suffix -> AL3D_IOU_H_*
+# metric name -> (AL3D_IOU_* formula, height rule): iou_bev, iou3d, iou3d_kitti, overlap_bev, over_a3d, ...
+IOU_METRIC = {k + h: (v, hv) for k, v in (("overlap", 0), ("iou", 1), ("over_a", 2), ("over_b", 3))
+              for h, hv in IOU_HEIGHT.items()}
+NMS_MODE = {"rotated": 0, "normal": 1}                           # AL3D_NMS_*
+BOX_IOU_TILE_ROWS, BOX_IOU_TILE_COLS, BOX_IOU_ROWS_MAX = 16, 64, 128
+NMS_MAX_CANDIDATES = 4096
+IOU_BAD_OFFSETS = 1
+
+
+def _enum(table, key, what):
+    if key not in table:
+        raise lib.Al3dError(f"{what}: {key!r} is not one of {sorted(table)}")
+    return table[key]
+
+
+def _box_rows(t, name, layout, rot_col):
+    t = _dev(t, torch.float32, name)
+    need = 5 if layout == "xyxyr" else 7
+    if t.dim() != 2 or t.shape[1] < need:
+        raise lib.Al3dError(f"{name}: [n, >={need}] float32 rows expected for layout {layout!r}")
+    if layout != "xyxyr" and not 6 <= int(rot_col) < t.shape[1]:
+        raise lib.Al3dError(f"{name}: rot_col {rot_col} outside [6, {t.shape[1]})")
+    return t
+
+
+def box_iou_matrix(a, b, metric="iou_bev", convention="det3d", rot_col=6, layout="xyzwlhr", rot_col_b=None, launch=None):
+    """``a [N,D]``, ``b [M,D']`` f32 device rows -> ``[N, M]`` f32 (``al3d_box_iou_matrix_f32`` in include/al3d.h).
+
+    ``metric``: ``iou`` / ``overlap`` / ``over_a`` / ``over_b`` + ``_bev`` (footprints), ``3d`` (height z +- h/2, volumes) or
+    ``3d_kitti`` (height [z - h, z]); ``convention``: ``det3d`` (rotation_2d) or ``heading`` (OpenPCDet); ``layout``:
+    ``xyzwlhr`` (angle in ``rot_col`` / ``rot_col_b``) or ``xyxyr``.  ``launch = (tile_rows, threads, reject)`` is for the
+    tests and the benchmark."""
+    m, h = _enum(IOU_METRIC, metric, "box_iou_matrix: metric")
+    conv, lay = _enum(BOX_CONVENTION, convention, "box_iou_matrix: convention"), _enum(BOX_LAYOUT, layout, "box_iou_matrix: layout")
+    rot_b = rot_col if rot_col_b is None else rot_col_b
+    a, b = _box_rows(a, "a", layout, rot_col), _box_rows(b, "b", layout, rot_b)
+    if lay == 1 and h:
+        raise lib.Al3dError("box_iou_matrix: [x1, y1, x2, y2, r] rows have no height; use a _bev metric")
+    n, mm = a.shape[0], b.shape[0]
+    out = torch.empty((n, mm), dtype=torch.float32, device=a.device)
+    args = (_ptr(a) if n else None, n, a.shape[1], int(rot_col), _ptr(b) if mm else None, mm, b.shape[1], int(rot_b), lay, conv, m,
+            h, _ptr(out) if n * mm else None)
+    if launch is None:
+        lib.call("al3d_box_iou_matrix_f32", *args, _stream())
+    else:
+        lib.call("al3d_box_iou_matrix_launch_f32", *args, int(launch[0]), int(launch[1]), int(launch[2]), _stream())
+    return out
+
+
+def box_iou_best(boxes, labels, counts, ref_boxes, ref_labels, ref_off, metric="iou3d", convention="det3d", rot_col=None,
+                 ref_rot_col=6, same_class=False, launch=None):
+    """The best IoU of every detection against its frame's reference boxes (``al3d_box_iou_best_f32``), on the raw NMS
+    buffers: ``boxes [B,nt,post,D]`` f32, ``labels [B,nt,post]`` i32, ``counts [B,nt]`` i32; ``ref_boxes [R,>=7]`` f32,
+    ``ref_labels [R]`` i32, ``ref_off [B+1]`` i32 (``FrameRefs.batch``).  ``rot_col`` defaults to the last column, as the
+    9-column NMS buffers keep the angle.  -> ``(best_iou [B,nt,post] f32, best_ref [B,nt,post] i32)``; the row maximum of
+    ``box_iou_matrix`` per frame with the lowest row among equal maxima, 0 / -1 where there is none.  Reads the status word
+    back (one small D2H).  ``launch = (chunk, ref_tile, threads, reject)`` is for the tests and the benchmark."""
+    m, h = _enum(IOU_METRIC, metric, "box_iou_best: metric")
+    conv = _enum(BOX_CONVENTION, convention, "box_iou_best: convention")
+    boxes = _dev(boxes, torch.float32, "boxes")
+    labels = _dev(labels, torch.int32, "labels")
+    counts = _dev(counts, torch.int32, "counts")
+    ref_labels = _dev(ref_labels, torch.int32, "ref_labels")
+    ref_off = _dev(ref_off, torch.int32, "ref_off")
+    if boxes.dim() != 4 or labels.shape != boxes.shape[:3] or counts.shape != boxes.shape[:2] or boxes.shape[3] < 7:
+        raise lib.Al3dError("box_iou_best: boxes [B,nt,post,>=7], labels [B,nt,post], counts [B,nt] expected")
+    B, nt, post, bd = boxes.shape
+    rot_col = bd - 1 if rot_col is None else int(rot_col)
+    if not 6 <= rot_col < bd:
+        raise lib.Al3dError(f"box_iou_best: rot_col {rot_col} outside [6, {bd})")
+    ref_boxes = _box_rows(ref_boxes, "ref_boxes", "xyzwlhr", ref_rot_col)
+    R = ref_boxes.shape[0]
+    if ref_labels.shape != (R,) or ref_off.shape != (B + 1,):
+        raise lib.Al3dError("box_iou_best: ref_boxes [R,>=7], ref_labels [R], ref_off [B+1] expected")
+    dev = boxes.device
+    best_iou = torch.empty((B, nt, post), dtype=torch.float32, device=dev)
+    best_ref = torch.empty((B, nt, post), dtype=torch.int32, device=dev)
+    status = torch.empty((1,), dtype=torch.int32, device=dev)
+    args = (_ptr(boxes), _ptr(labels), _ptr(counts), B, nt, post, bd, rot_col, _ptr(ref_boxes) if R else None,
+            _ptr(ref_labels) if R else None, _ptr(ref_off), R, ref_boxes.shape[1], int(ref_rot_col), conv, m, h,
+            1 if same_class else 0, _ptr(best_iou), _ptr(best_ref), _ptr(status))
+    if launch is None:
+        lib.call("al3d_box_iou_best_f32", *args, _stream())
+    else:
+        lib.call("al3d_box_iou_best_launch_f32", *args, *(int(v) for v in launch), _stream())
+    if int(status.item()) & IOU_BAD_OFFSETS:
+        raise lib.Al3dError(f"box_iou_best: ref_off is not ascending inside [0, {R}]")
+    return best_iou, best_ref
+
+
+def nms_boxes(boxes, scores, thresh, pre_max=None, post_max=None, mode="rotated", convention="heading", rot_col=6,
+              layout="xyzwlhr", launch=None):
+    """Greedy NMS on device rows (``al3d_nms_boxes_f32``): ``boxes [N,D]``, ``scores [N]`` f32 -> ``keep [k]`` i64, indices into
+    the input in descending score order (NaN scores last, equal scores by the lower index).  A box falls when its IoU with an
+    earlier kept one is ``> thresh``; ``mode="normal"`` compares the axis-aligned boxes.  At most 4096 candidates after
+    ``pre_max``.  Reads the count back (one small D2H).  ``launch = (sort_threads, mask_threads, reject)`` is for the tests."""
+    mode_i = _enum(NMS_MODE, mode, "nms_boxes: mode")
+    conv, lay = _enum(BOX_CONVENTION, convention, "nms_boxes: convention"), _enum(BOX_LAYOUT, layout, "nms_boxes: layout")
+    boxes = _box_rows(boxes, "boxes", layout, rot_col)
+    scores = _dev(scores, torch.float32, "scores")
+    n = boxes.shape[0]
+    if scores.shape != (n,):
+        raise lib.Al3dError("nms_boxes: boxes [N,D] and scores [N] expected")
+    pre = 0 if pre_max is None else int(pre_max)
+    post = 0 if post_max is None else int(post_max)
+    cand = min(n, pre) if pre > 0 else n
+    if cand > NMS_MAX_CANDIDATES:
+        raise lib.Al3dError(f"nms_boxes: {cand} candidates after pre_max, at most {NMS_MAX_CANDIDATES}")
+    cap = min(cand, post) if post > 0 else cand
+    dev = boxes.device
+    keep = torch.empty((max(cap, 1),), dtype=torch.int32, device=dev)
+    count = torch.empty((1,), dtype=torch.int32, device=dev)
+    ws = torch.empty((lib.load().al3d_nms_boxes_workspace_bytes(n),), dtype=torch.uint8, device=dev)
+    args = (_ptr(boxes) if n else None, _ptr(scores) if n else None, n, boxes.shape[1], int(rot_col), lay, conv, mode_i,
+            float(thresh), pre, post, _ptr(keep), cap, _ptr(count), _ptr(ws))
+    if launch is None:
+        lib.call("al3d_nms_boxes_f32", *args, _stream())
+    else:
+        lib.call("al3d_nms_boxes_launch_f32", *args, *(int(v) for v in launch), _stream())
+    return keep[:int(count.item())].long()
+
+
 EST_MAX_BOXES, EST_MAX_CLASSES, EST_BAD_OFFSETS, EST_BAD_LABEL = 1024, 32, 1, 2      # AL3D_EST_* of include/al3d.h
 
 

@@ -172,6 +172,74 @@ def sweep_matches(detector, dataloader, device, refs: FrameRefs, view=None, ncls
     return res
 
 
+def sweep_iou_targets(detector, dataloader, device, refs: FrameRefs, metric: str = "iou3d", same_class: bool = False,
+                      convention: str = "det3d") -> Dict[str, np.ndarray]:
+    """The Estimator's training targets (det3d/models/detectors/estimator.py:98-115: ``boxes_iou3d_gpu(pred, gt).max(1)``)
+    for every detection of the pool: the loop of ``sweep_matches`` with ``selector_ops.box_iou_best`` on each batch's raw
+    NMS buffers beside the sweep -- no IoU matrix is written.  ``refs``: the ground truth (``FrameRefs.from_infos``), angle
+    in the last column like the detections'.  Returns, in dataset order, ``off [N+1]`` i64 and per detection ``best_iou``
+    f32, ``best_ref`` i64 (row of ``refs.boxes``, -1 where the frame has no reference box -- of the detection's class under
+    ``same_class``), ``scores`` f32 and ``labels`` i32 (host).  ``same_class=False`` is the reference's class-agnostic
+    target.  Under ``torch.distributed`` every rank sweeps its loader's frames and the rows are all-gathered (a collective).
+
+    Difference kept on purpose: the reference computes targets only for the boxes that contain a point
+    (estimator.py:491); here every detection carries one, and a trainer drops the others."""
+    import torch.distributed as dist
+    from ..sweep import gather_in_dataset_order
+    from .. import selector_ops as ops
+    if refs.boxes.shape[1] < 7:
+        raise ValueError(f"sweep_iou_targets: reference boxes need an angle column, got {refs.boxes.shape[1]} columns")
+    n = len(refs)
+    index, rows = [], {"best_iou": [], "best_ref": [], "scores": [], "labels": [], "valid": []}
+    for ids, preds in _batches(detector, dataloader, device):
+        boxes, scores, labels, counts = _raw_of(preds)
+        rb, rl, _, roff = refs.batch(ids, device)
+        iou, ref = ops.box_iou_best(boxes, labels, counts, rb, rl, roff, metric=metric, convention=convention,
+                                    ref_rot_col=rb.shape[1] - 1, same_class=same_class)
+        first = torch.as_tensor([int(refs.off[i]) for i in ids], dtype=torch.int64, device=device)
+        ref = torch.where(ref >= 0, ref.long() - roff[:-1].long()[:, None, None] + first[:, None, None], ref.long())
+        b, post = len(ids), boxes.shape[2]
+        valid = (torch.arange(post, device=device)[None, None, :] < counts.clamp(0, post)[:, :, None]).reshape(b, -1)
+        front = torch.argsort((~valid).to(torch.int8), dim=1, stable=True)      # a frame's detections first, order kept
+        for k, v in (("best_iou", iou), ("best_ref", ref), ("scores", scores), ("labels", labels)):
+            rows[k].append(v.reshape(b, -1).gather(1, front))
+        rows["valid"].append(valid.sum(1, keepdim=True).to(torch.int32))
+        index.extend(int(i) for i in ids)
+    # batches (pack_detections) and ranks may differ in their slots per frame: one width for the gathers
+    width = torch.tensor([max([r.shape[1] for r in rows["scores"]] or [0])], device=device)
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        dist.all_reduce(width, op=dist.ReduceOp.MAX)        # a rank whose shard is empty still joins the gathers
+    width = int(width)
+    idx = torch.as_tensor(index, dtype=torch.int64, device=device)
+    dtypes = dict(best_iou=torch.float32, best_ref=torch.int64, scores=torch.float32, labels=torch.int32, valid=torch.int32)
+    full = {}
+    for k, v in rows.items():
+        w = 1 if k == "valid" else width
+        v = [torch.nn.functional.pad(r.to(dtypes[k]), (0, w - r.shape[1])) for r in v]
+        local = torch.cat(v) if v else torch.empty((0, w), dtype=dtypes[k], device=device)
+        full[k] = gather_in_dataset_order(local, idx, n).cpu().numpy()
+    keep = np.arange(width)[None, :] < full["valid"]
+    res = {"off": np.concatenate([[0], np.cumsum(full["valid"][:, 0])]).astype(np.int64)}
+    for k in ("best_iou", "best_ref", "scores", "labels"):
+        res[k] = full[k][keep]
+    return res
+
+
+def run_iou_targets(detector, dataloader, device, infos, out_path, **kw):
+    """``sweep_iou_targets`` against the ground truth of ``infos`` -> ``out_path`` (.npz, rank 0 writes)."""
+    from .base_selector import master_only
+    res = sweep_iou_targets(detector, dataloader, device, FrameRefs.from_infos(infos, head_class_names(detector)), **kw)
+
+    @master_only
+    def write():
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        tmp = out_path + ".tmp.npz"
+        np.savez(tmp, **res)
+        os.replace(tmp, out_path)
+    write()
+    return res
+
+
 # ------------------------------------------------------------------------------------------- closing formulas (host, f64)
 def ppal_class_weights(cls_count, cls_quality, labelled: Sequence[int], class_names: Sequence[str], alpha: float = 3.0,
                        ub: float = 2.0) -> Dict[str, float]:

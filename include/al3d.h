@@ -1212,6 +1212,102 @@ int al3d_estimator_f32(const float* boxes, const int* labels, const int* counts,
                        int64_t wts_elems, int num_classes, float* out_boxes, float* out_scores, int* out_labels,
                        int* out_counts, void* workspace, int* status, void* stream);
 
+/* ---------------------------------------------------------------- rotated box IoU and NMS as ops of their own
+ * Replace det3d/ops/iou3d_nms/iou3d_nms_utils.py:13-107 over src/iou3d_nms_kernel.cu and src/iou3d_cpu.cpp:118-229
+ * (boxes_iou_bev, boxes_iou3d_gpu, nms_gpu, nms_normal_gpu), bevfusion/mmdet3d/ops/iou3d/iou3d_utils.py:6-68 over
+ * src/iou3d_kernel.cu (the same three on [x1, y1, x2, y2, r] rows) and the numba.cuda kernel of
+ * det3d/datasets/utils/kitti_object_eval_python/rotate_iou.py:250-341 with eval.py:123-161 (rotate_iou_gpu_eval,
+ * bev_box_overlap, d3_box_overlap).  The intersection is the rotated-rectangle clip of the head kernels (csrc/al3d_rbox.h);
+ * the reference's clipping code is not ported.  f32 under every AL3D_MATH.
+ *
+ * Box rows.  layout AL3D_BOX_ROWS_XYZ: [n, box_dim] f32, box_dim >= 7, columns 0..5 = x, y, z and three sizes, the angle in
+ * rot_col (6 <= rot_col < box_dim).  layout AL3D_BOX_ROWS_XYXYR: [n, box_dim >= 5] = [x1, y1, x2, y2, r] (mmdet3d's
+ * xywhr2xyxyr): the centre is the midpoint, the sizes are the differences; no height rule.  convention (both layouts):
+ * AL3D_BOX_DET3D: the corners of det3d's rotation_2d, (+-s0/2, +-s1/2) turned by x' = x cos r + y sin r, y' = -x sin r +
+ * y cos r -- also the sense of mmdet3d's rotate_around_center (iou3d_kernel.cu:111-119) and of rbbox_to_corners
+ * (rotate_iou.py:207-229); AL3D_BOX_HEADING: centre + [[cos,-sin],[sin,cos]] (+-s0/2, +-s1/2), the first size along the
+ * heading (iou3d_cpu.cpp:118-163; OpenPCDet).  DET3D(w, l, r) and HEADING(l, w, -r - pi/2) are the same rectangle
+ * (to_pcdet, iou3d_nms_utils.py:29-33).
+ *
+ * Metrics.  inter = the footprints' intersection area, sa / sb = the footprints' areas; with a height rule inter is
+ * multiplied by max(min(hi_a, hi_b) - max(lo_a, lo_b), 0) and sa / sb are the volumes s0 * s1 * h, where [lo, hi] is
+ * [z - h/2, z + h/2] (AL3D_IOU_H_CENTRE, iou3d_nms_utils.py:50-70) or [z - h, z] (AL3D_IOU_H_TOP, eval.py:129-155 with the
+ * camera frame's y in column 2).  eps = 1e-8 without a height rule (iou3d_cpu.cpp:222-229), 1e-6 with one.
+ *   AL3D_IOU_OVERLAP  inter                             (criterion 2 of rotate_iou.py:250-261)
+ *   AL3D_IOU_IOU      inter / max(sa + sb - inter, eps) (criterion -1)
+ *   AL3D_IOU_OVER_A   inter / max(sa, eps)              (a = the ROW box)
+ *   AL3D_IOU_OVER_B   inter / max(sb, eps)              (b = the COLUMN box)
+ * DEVIATIONS.  (1) The clamps on OVER_A / OVER_B and on the KITTI rule are ours: the reference divides by zero for a box of
+ * zero area; a degenerate box -- a footprint size that is not positive -- gives 0 here with every box, for every metric.
+ * (2) Non-finite input: a row with a NaN or an inf in x, y, z, a size or the angle is not a box either -- every pair it
+ * takes part in gives 0 for every metric, and like a degenerate box it neither suppresses nor is suppressed in the NMS; a
+ * result that would be NaN because finite sizes overflow is 0 too.  Rows and pairs without such input keep
+ * their bits.  (3) A pair whose bounding circles lie apart (with 1e-4 of slack) is not clipped: its intersection is empty.
+ * Every output is bit-identical from run to run and for every launch shape; the _launch variants take the shape (and
+ * reject = 0 switches the circle test off) for the tests and the benchmark.
+ *
+ * (a) al3d_box_iou_matrix_f32: a [N, a_dim], b [M, b_dim] -> out [N, M].  Tiles of AL3D_BOX_IOU_TILE_ROWS x 64.
+ *     _launch: tile_rows in [1, 128], threads 64 / 128 / 256. */
+#define AL3D_BOX_DET3D 0
+#define AL3D_BOX_HEADING 1
+#define AL3D_BOX_ROWS_XYZ 0
+#define AL3D_BOX_ROWS_XYXYR 1
+#define AL3D_IOU_OVERLAP 0
+#define AL3D_IOU_IOU 1
+#define AL3D_IOU_OVER_A 2
+#define AL3D_IOU_OVER_B 3
+#define AL3D_IOU_H_NONE 0
+#define AL3D_IOU_H_CENTRE 1
+#define AL3D_IOU_H_TOP 2
+#define AL3D_BOX_IOU_TILE_ROWS 16
+int al3d_box_iou_matrix_f32(const float* a, int64_t N, int a_dim, int a_rot, const float* b, int64_t M, int b_dim, int b_rot,
+                            int layout, int convention, int metric, int height, float* out, void* stream);
+int al3d_box_iou_matrix_launch_f32(const float* a, int64_t N, int a_dim, int a_rot, const float* b, int64_t M, int b_dim,
+                                   int b_rot, int layout, int convention, int metric, int height, float* out, int tile_rows,
+                                   int threads, int reject, void* stream);
+/* (b) The best IoU of every detection against the frame's reference boxes: the Estimator's training target
+ * (det3d/models/detectors/estimator.py:98-115: boxes_iou3d_gpu(...).max(1)), on the raw NMS buffers of
+ * al3d_match_boxes_f32 (boxes [B,nt,post,box_dim], labels [B,nt,post], counts [B,nt]; ref_boxes [R,ref_dim], ref_labels [R],
+ * ref_off [B+1]; XYZ rows).  best_iou [B,nt,post] f32 and best_ref [B,nt,post] i32 (row of ref_boxes) equal the row maximum
+ * of (a) over the frame's rows [ref_off[b], ref_off[b+1]) -- with same_class != 0 over those whose ref_labels equals the
+ * detection's label -- and the LOWEST such row among equal maxima.  0 and -1 where there is no such row and for the slots
+ * outside [0, clamp(count, 0, post)).  The matrix is never written and no size is limited: the reference rows pass through
+ * LDS 64 at a time.  *status (device int): AL3D_IOU_BAD_OFFSETS when ref_off is not ascending inside [0, R]; such a frame
+ * has no reference rows and nothing is read out of bounds.  _launch: chunk (slots in LDS at a time) in [1, 128], ref_tile
+ * in [1, 64], threads 64 / 128 / 256. */
+#define AL3D_IOU_BAD_OFFSETS 1
+int al3d_box_iou_best_f32(const float* boxes, const int* labels, const int* counts, int B, int nt, int post, int box_dim,
+                          int rot_col, const float* ref_boxes, const int* ref_labels, const int* ref_off, int R, int ref_dim,
+                          int ref_rot, int convention, int metric, int height, int same_class, float* best_iou, int* best_ref,
+                          int* status, void* stream);
+int al3d_box_iou_best_launch_f32(const float* boxes, const int* labels, const int* counts, int B, int nt, int post, int box_dim,
+                                 int rot_col, const float* ref_boxes, const int* ref_labels, const int* ref_off, int R,
+                                 int ref_dim, int ref_rot, int convention, int metric, int height, int same_class,
+                                 float* best_iou, int* best_ref, int* status, int chunk, int ref_tile, int threads, int reject,
+                                 void* stream);
+/* (c) Stand-alone greedy NMS (iou3d_nms_utils.py:75-107, iou3d_utils.py:23-68 with iou3d_nms_kernel.cu:282-311,327-373 and
+ * iou3d_nms.cpp's walk over the mask).  boxes [N, box_dim], scores [N].  Order: the sort word of csrc/al3d_sort_key.h --
+ * descending score, NaN scores last, equal scores by the lower index; the best pre_max enter (<= 0: all).  A candidate is
+ * dropped when its IoU (AL3D_IOU_IOU of the footprints) with an earlier kept one is > thresh, strictly
+ * (iou3d_nms_kernel.cu:304,365); the walk stops at post_max survivors (<= 0: no limit).  mode AL3D_NMS_NORMAL: the
+ * axis-aligned IoU of x +- s0/2, y +- s1/2, the angle ignored (iou3d_nms_kernel.cu:314-325).  keep [keep_cap] i32: indices
+ * into the input in descending score order, *count (device int) their number; keep_cap >= min(candidates, post_max).
+ * Any N goes into the ordering; more than AL3D_NMS_MAX_CANDIDATES candidates after pre_max is AL3D_EINVAL (the mask is
+ * 4096 x 4096 bits = 2 MB of the workspace).  workspace: al3d_nms_boxes_workspace_bytes(N) bytes (-1 for a bad N).
+ * DEVIATION: suppression uses the exact intersection.  The reference's check_in_box2d accepts corners within MARGIN = 1e-2 m
+ * of a box, so pairs near the threshold can differ from the CUDA extension.  _launch: sort_threads 256 / 1024, mask_threads
+ * 64 / 128 / 256. */
+#define AL3D_NMS_ROTATED 0
+#define AL3D_NMS_NORMAL 1
+#define AL3D_NMS_MAX_CANDIDATES 4096
+int64_t al3d_nms_boxes_workspace_bytes(int64_t N);
+int al3d_nms_boxes_f32(const float* boxes, const float* scores, int64_t N, int box_dim, int rot_col, int layout, int convention,
+                       int mode, float thresh, int pre_max, int post_max, int* keep, int64_t keep_cap, int* count,
+                       void* workspace, void* stream);
+int al3d_nms_boxes_launch_f32(const float* boxes, const float* scores, int64_t N, int box_dim, int rot_col, int layout,
+                              int convention, int mode, float thresh, int pre_max, int post_max, int* keep, int64_t keep_cap,
+                              int* count, void* workspace, int sort_threads, int mask_threads, int reject, void* stream);
+
 /* ---------------------------------------------------------------- runtime
  * A HIP stream restricted to n_cus compute units starting at first_cu (hipExtStreamCreateWithCUMask); the
  * reference has no analogue (its loader workers are host processes, det3d/datasets/loader/build_loader.py:23-59):

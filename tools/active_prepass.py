@@ -6,13 +6,18 @@
         --out tools/diff_category_average.json
     python tools/active_prepass.py --config examples/active/cbgs_cald.py --checkpoint latest.pth --mode cald \\
         --view 1 0 0.0 1.0 --out data/buffers/cald_ent_sorted_idx.json --jsdiv idx_to_jsdiv.pkl
+    python tools/active_prepass.py --config examples/active/estimator/cbgs_partial.py --checkpoint latest.pth \\
+        --iou-targets work_dirs/iou_targets.npz
     torchrun --nproc-per-node 8 tools/active_prepass.py ...                 # every rank sweeps a contiguous shard
 
 ``ppal`` replaces the reference's tools/ppal_pred_list.py + tools/ppal_unc.py: one sweep, the detections matched to the
 ``gt_boxes`` / ``gt_names`` of ``cfg.selector.infos_origin`` (``ref_scores`` = -1.0), class weights from the labelled
 frames.  ``cald`` replaces tools/cald_pred_list.py + tools/cald_ent.py: a plain sweep whose detections are the reference
 boxes, a second sweep over the augmented ``--view`` (flip_x flip_y rot scale) matched against them.  The labelled frames
-are the last round of ``cfg.selector.buffer_file``.  The pool and the loaders are those of tools/active_select.py
+are the last round of ``cfg.selector.buffer_file``.  ``--iou-targets`` writes what the reference's Estimator is trained
+against (det3d/models/detectors/estimator.py:98-115): ``off [N+1]`` and per detection ``best_iou`` (3-D IoU with the best
+ground-truth box of ``infos_origin``), ``best_ref``, ``scores``, ``labels`` -- for every detection, where the reference
+keeps only the boxes that contain a point (estimator.py:491).  The pool and the loaders are those of tools/active_select.py
 (``--synthetic-scenes`` generates a pool; otherwise the infos' sweep files are read from ``cfg.data_root``).
 """
 import argparse
@@ -30,7 +35,11 @@ def parse_args():
     p = argparse.ArgumentParser(description="PPAL / CALD pre-pass")
     p.add_argument("--config", required=True)
     p.add_argument("--checkpoint", default=None)
-    p.add_argument("--mode", choices=["ppal", "cald"], required=True)
+    p.add_argument("--mode", choices=["ppal", "cald"], default=None)
+    p.add_argument("--iou-targets", default=None, metavar="OUT.npz",
+                   help="write the Estimator's training targets: every detection's best IoU against the ground truth")
+    p.add_argument("--iou-metric", default="iou3d")
+    p.add_argument("--iou-same-class", action="store_true")
     p.add_argument("--out", default=None, help="ppal: class_weight_file; cald: buffer_path (default: the selector's own)")
     p.add_argument("--jsdiv", default=None, help="cald: jsdiv_path (.pkl or .json)")
     p.add_argument("--view", nargs=4, type=float, default=[1, 0, 0.0, 1.0], metavar=("FLIP_X", "FLIP_Y", "ROT", "SCALE"))
@@ -44,6 +53,8 @@ def parse_args():
 
 def main():
     args = parse_args()
+    if args.mode is None and args.iou_targets is None:
+        raise SystemExit("active_prepass: give --mode ppal | cald and / or --iou-targets OUT.npz")
     from al3d import synthetic
     from al3d.datasets import DeviceSweepLoader, FileSweepLoader, PoolFrames, generate_task_anchors
     from al3d.models import build_detector
@@ -101,11 +112,15 @@ def main():
                                  threads=int(os.environ.get("AL3D_READER_THREADS", "8")), with_points=with_points)
     loader.sampler = mine
 
+    if args.iou_targets:
+        t = P.run_iou_targets(model, loader, dev, infos, args.iou_targets, metric=args.iou_metric,
+                              same_class=args.iou_same_class)
+        logger.info("IoU targets of %d detections in %d frames -> %s", len(t["best_iou"]), n, args.iou_targets)
     if args.mode == "ppal":
         out = args.out or sel_cfg.get("class_weight_file", "tools/diff_category_average.json")
         weights = P.run_ppal_prepass(model, loader, dev, infos, labelled, out, range_filter=args.range_filter)
         logger.info("class weights of %d labelled frames -> %s: %s", len(labelled), out, weights)
-    else:
+    elif args.mode == "cald":
         out = args.out or sel_cfg.get("buffer_path", "cald_ent_sorted_idx.json")
         jsdiv = args.jsdiv or sel_cfg.get("jsdiv_path", "idx_to_jsdiv.pkl")
         view = (bool(args.view[0]), bool(args.view[1]), float(args.view[2]), float(args.view[3]))
