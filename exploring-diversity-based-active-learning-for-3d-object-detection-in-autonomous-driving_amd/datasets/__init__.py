@@ -4,7 +4,8 @@ from .file_loader import FileSweepLoader, SweepFileReader
 from .camera_files import CameraLidarFileLoader, ImageAugTest
 from .pipelines import (PIPELINES, Compose, LoadPointCloudFromFile, LoadPointCloudAnnotations, Preprocess,
                         Voxelization, AssignTarget, Reformat, SweepDataset, collate_device)
+from .create_gt_database import create_groundtruth_database, SweepPointsLoader, GtDatabaseWriter
 
-__all__ = ["create_anchors_3d_range", "generate_task_anchors", "PoolFrames", "DeviceSweepLoader", "CameraLidarSweepLoader", "FileSweepLoader", "SweepFileReader", "CameraLidarFileLoader", "ImageAugTest", "PIPELINES",
+__all__ = ["create_groundtruth_database", "SweepPointsLoader", "GtDatabaseWriter", "create_anchors_3d_range", "generate_task_anchors", "PoolFrames", "DeviceSweepLoader", "CameraLidarSweepLoader", "FileSweepLoader", "SweepFileReader", "CameraLidarFileLoader", "ImageAugTest", "PIPELINES",
            "Compose", "LoadPointCloudFromFile", "LoadPointCloudAnnotations", "Preprocess", "Voxelization",
            "AssignTarget", "Reformat", "SweepDataset", "collate_device"]

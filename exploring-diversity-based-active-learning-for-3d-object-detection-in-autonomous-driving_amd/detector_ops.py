@@ -1411,3 +1411,39 @@ def center_decode_nms(hout, task_ncls, chan_off, *, swapped, max_num, norm_bbox,
              float(nms_thr), int(pre_max_size), post, limit, 1 if merge else 0, _ptr(boxes), _ptr(scores), _ptr(labels),
              _ptr(counts), _ptr(ws), _stream())
     return boxes, scores, labels, counts
+
+
+_BOX_CORNERS = (0, 1, 3, 2, 4, 5, 7, 6)        # corners_nd's order of the unit cube's corners (z fastest, then swapped pairs)
+_BOX_FACES = ((0, 1, 2, 3), (7, 6, 5, 4), (0, 3, 7, 4), (1, 5, 6, 2), (0, 4, 5, 1), (3, 2, 6, 7))   # normals point inside
+
+
+def box_planes(boxes):
+    """The six inward planes ``(n0, n1, n2, d)`` of every box, ``[R, 6, 4]`` float32, for ``al3d_points_in_boxes_*``.
+
+    Host numpy on purpose: a frame has tens of boxes, and the SAME float32 calls as the reference keep ``sinf`` / ``cosf``
+    differences and summation orders out of the membership test -- ``corners_nd`` (box_np_ops.py:269-305),
+    ``rotation_3d_in_axis(axis=2)`` with its einsum (:360-396), ``+= centers`` (:474), ``corner_to_surfaces_3d``
+    (:1111-1131) and the formulas of ``surface_equ_3d_jitv2`` (geometry.py:380-405).  ``boxes [R, >= 7]`` float32 numpy:
+    centre, three sizes, ..., the angle in the LAST column (``points_in_rbbox``, box_np_ops.py:1102-1108)."""
+    import numpy as np
+    boxes = np.asarray(boxes)
+    if boxes.dtype != np.float32 or boxes.ndim != 2 or boxes.shape[1] < 7:
+        raise lib.Al3dError(f"box_planes: boxes [R, >= 7] float32 expected, got {boxes.dtype} {boxes.shape}")
+    centers, dims, angles = boxes[:, :3], boxes[:, 3:6], boxes[:, -1]
+    unit = np.stack(np.unravel_index(np.arange(8), [2, 2, 2]), axis=1).astype(np.float32)[list(_BOX_CORNERS)]
+    unit = unit - np.array((0.5, 0.5, 0.5), dtype=np.float32)
+    corners = dims.reshape([-1, 1, 3]) * unit.reshape([1, 8, 3])
+    s, c = np.sin(angles), np.cos(angles)
+    one, zero = np.ones_like(c), np.zeros_like(c)
+    rot_t = np.stack([[c, -s, zero], [s, c, zero], [zero, zero, one]])
+    corners = np.einsum("aij,jka->aik", corners, rot_t)
+    corners += centers.reshape([-1, 1, 3])
+    faces = corners[:, np.array(_BOX_FACES)]                      # [R, 6, 4, 3]
+    a, b = faces[:, :, 0] - faces[:, :, 1], faces[:, :, 1] - faces[:, :, 2]
+    planes = np.empty((boxes.shape[0], 6, 4), dtype=np.float32)
+    planes[..., 0] = a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1]
+    planes[..., 1] = a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2]
+    planes[..., 2] = a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]
+    p0 = faces[:, :, 0]
+    planes[..., 3] = -p0[..., 0] * planes[..., 0] - p0[..., 1] * planes[..., 1] - p0[..., 2] * planes[..., 2]
+    return planes

@@ -483,3 +483,134 @@ def greedy_kcenter(D, seeded, first, box_cost, cost_f, start_cost, budget_int, s
              _stream())
     cnt, status = meta.tolist()
     return int(status), out_idx[:cnt].tolist()
+
+
+# AL3D_PIB_* of include/al3d.h
+PIB_BAD_POINT_OFF, PIB_BAD_BOX_OFF, PIB_FRAME_TOO_LARGE, PIB_BAD_WORKSPACE, PIB_BAD_ROWS = 1, 2, 4, 8, 16
+PIB_GROUPS, PIB_THREADS, PIB_TILE = 32, 256, 64
+
+
+def pib_status_check(status, who="points_in_boxes"):
+    """Raise for the AL3D_PIB_* bits of a status word that is on the host already."""
+    st = int(status)
+    if st & PIB_BAD_POINT_OFF:
+        raise lib.Al3dError(f"{who}: point_off is not ascending inside [0, number of points]")
+    if st & PIB_BAD_BOX_OFF:
+        raise lib.Al3dError(f"{who}: box_off is not ascending inside [0, number of boxes]")
+    if st & PIB_FRAME_TOO_LARGE:
+        raise lib.Al3dError(f"{who}: a frame has 2^31 points or more")
+    if st:
+        raise lib.Al3dError(f"{who}: status {st} (workspace or offsets do not belong to this call)")
+
+
+def _pib_planes(boxes, planes, device):
+    """``[R, 6, 4]`` device planes: the caller's, or ``detector_ops.box_planes`` of host boxes (one small upload)."""
+    if planes is None:
+        from .detector_ops import box_planes
+        if isinstance(boxes, torch.Tensor):
+            boxes = boxes.detach().cpu().numpy()
+        planes = torch.from_numpy(box_planes(boxes)).to(device)
+    planes = _dev(planes, torch.float32, "planes")
+    if planes.dim() != 3 or planes.shape[1:] != (6, 4):
+        raise lib.Al3dError("points_in_boxes: planes [R, 6, 4] expected")
+    return planes
+
+
+def points_in_boxes_count(points, point_off, planes, box_off, launch=None):
+    """``al3d_points_in_boxes_count_f32``: -> ``(box_count [R] i32, workspace, status)`` on the device, nothing read back.
+    ``launch = (groups, threads, tile)`` is for the tests and the benchmark."""
+    points = _dev(points, torch.float32, "points")
+    point_off = _dev(point_off, torch.int64, "point_off")
+    box_off = _dev(box_off, torch.int32, "box_off")
+    planes = _pib_planes(None, planes, points.device)
+    if points.dim() != 2 or points.shape[1] < 3 or point_off.dim() != 1 or point_off.numel() < 1 or \
+            box_off.shape != point_off.shape:
+        raise lib.Al3dError("points_in_boxes: points [P, >= 3], point_off [B+1] i64, box_off [B+1] i32 expected")
+    g, t, tile = (PIB_GROUPS, PIB_THREADS, PIB_TILE) if launch is None else (int(v) for v in launch)
+    P, F, B, R = points.shape[0], points.shape[1], point_off.numel() - 1, planes.shape[0]
+    dev = points.device
+    nbytes = int(lib.load().al3d_points_in_boxes_workspace_bytes(R, g, t))
+    if nbytes < 0:
+        raise lib.Al3dError(f"points_in_boxes: bad launch shape {(g, t, tile)} or box count {R}")
+    ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+    counts = torch.empty((R,), dtype=torch.int32, device=dev)
+    status = torch.empty((1,), dtype=torch.int32, device=dev)
+    lib.call("al3d_points_in_boxes_count_launch_f32", _ptr(points) if P else None, P, F, _ptr(point_off), B,
+             _ptr(planes) if R else None, _ptr(box_off), R, _ptr(counts) if R else None, _ptr(ws), _ptr(status), g, t, tile,
+             _stream())
+    return counts, ws, status
+
+
+def points_in_boxes_gather(points, point_off, planes, box_off, out_off, centres, workspace, total, num_features, launch=None):
+    """``al3d_points_in_boxes_gather_f32`` after ``points_in_boxes_count`` with the same ``launch`` groups and threads:
+    -> ``(rows [total, num_features] f32, index [total] i64, status)`` on the device."""
+    points = _dev(points, torch.float32, "points")
+    point_off = _dev(point_off, torch.int64, "point_off")
+    box_off = _dev(box_off, torch.int32, "box_off")
+    planes = _pib_planes(None, planes, points.device)
+    out_off = _dev(out_off, torch.int64, "out_off")
+    centres = _dev(centres, torch.float32, "centres")
+    P, F, B, R = points.shape[0], points.shape[1], point_off.numel() - 1, planes.shape[0]
+    if out_off.shape != (R + 1,) or centres.shape != (R, 3) or not 3 <= int(num_features) <= F:
+        raise lib.Al3dError("points_in_boxes: out_off [R+1], centres [R, 3] and 3 <= num_features <= F expected")
+    g, t, tile = (PIB_GROUPS, PIB_THREADS, PIB_TILE) if launch is None else (int(v) for v in launch)
+    dev = points.device
+    T = int(total)
+    rows = torch.empty((T, int(num_features)), dtype=torch.float32, device=dev)
+    index = torch.empty((T,), dtype=torch.int64, device=dev)
+    status = torch.empty((1,), dtype=torch.int32, device=dev)
+    lib.call("al3d_points_in_boxes_gather_launch_f32", _ptr(points) if P else None, P, F, _ptr(point_off), B,
+             _ptr(planes) if R else None, _ptr(box_off), R, _ptr(out_off), _ptr(centres) if R else None, _ptr(workspace),
+             _ptr(rows) if T else None, int(num_features), _ptr(index) if T else None, T, _ptr(status), g, t, tile, _stream())
+    return rows, index, status
+
+
+def points_in_boxes(points, point_off, boxes, box_off, num_features, planes=None, launch=None, check=True):
+    """Every box's points, compacted (the device half of ``create_groundtruth_database``; include/al3d.h, "points in boxes").
+
+    ``points [P, F]`` f32 with the frames back to back, ``point_off [B+1]`` i64, ``boxes [R, >= 7]`` f32 (host numpy or a
+    tensor: centre, sizes, ..., the angle LAST) with the frames' boxes back to back, ``box_off [B+1]`` i32.  Returns
+    ``(rows [T, num_features] f32, index [T] i64, counts [R] i32, offsets [R+1] i64)``: box r's rows are
+    ``rows[offsets[r]:offsets[r+1]]``, its points in ascending point index with xyz minus the box centre, ``index`` the row
+    of ``points`` each came from.  Flow: count, ONE host read (the total, with the count's status word), gather; with
+    ``check=True`` the gather's status word is read back afterwards (it can only be set by a workspace or offsets that are
+    not this call's own).  ``planes`` overrides ``detector_ops.box_planes(boxes)``; ``launch = (groups, threads, tile)`` is
+    for the tests and the benchmark."""
+    points = _dev(points, torch.float32, "points")
+    dev = points.device
+    if isinstance(boxes, torch.Tensor):
+        centres = boxes[:, :3].to(device=dev, dtype=torch.float32).contiguous()
+    else:
+        import numpy as np
+        centres = torch.from_numpy(np.ascontiguousarray(np.asarray(boxes)[:, :3], dtype=np.float32)).to(dev)
+    planes = _pib_planes(boxes, planes, dev)
+    R = planes.shape[0]
+    if centres.shape != (R, 3):
+        raise lib.Al3dError("points_in_boxes: boxes [R, >= 7] and planes [R, 6, 4] expected")
+    counts, ws, st_count = points_in_boxes_count(points, point_off, planes, box_off, launch)
+    offsets = torch.zeros((R + 1,), dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, out=offsets[1:])
+    total, st = torch.stack([offsets[R], st_count[0].to(torch.int64)]).tolist()       # the one host read
+    pib_status_check(st)
+    rows, index, st_gather = points_in_boxes_gather(points, point_off, planes, box_off, offsets, centres, ws, total,
+                                                    num_features, launch)
+    if check:
+        pib_status_check(st_gather.item())
+    return rows, index, counts, offsets
+
+
+def points_in_boxes_mask(points, planes, launch=None):
+    """``al3d_points_in_boxes_mask_u8``: ``points [P, F]`` f32, ``planes [R, 6, 4]`` f32 -> ``[P, R]`` uint8, the
+    ``points_in_rbbox`` matrix of one frame.  ``launch = (threads, tile)``."""
+    points = _dev(points, torch.float32, "points")
+    planes = _pib_planes(None, planes, points.device)
+    if points.dim() != 2 or points.shape[1] < 3:
+        raise lib.Al3dError("points_in_boxes_mask: points [P, >= 3] expected")
+    P, F, R = points.shape[0], points.shape[1], planes.shape[0]
+    out = torch.empty((P, R), dtype=torch.uint8, device=points.device)
+    args = (_ptr(points) if P else None, P, F, _ptr(planes) if R else None, R, _ptr(out) if P * R else None)
+    if launch is None:
+        lib.call("al3d_points_in_boxes_mask_u8", *args, _stream())
+    else:
+        lib.call("al3d_points_in_boxes_mask_launch_u8", *args, *(int(v) for v in launch), _stream())
+    return out

@@ -1308,6 +1308,59 @@ int al3d_nms_boxes_launch_f32(const float* boxes, const float* scores, int64_t N
                               int convention, int mode, float thresh, int pre_max, int post_max, int* keep, int64_t keep_cap,
                               int* count, void* workspace, int sort_threads, int mask_threads, int reject, void* stream);
 
+/* ---------------------------------------------------------------- points in boxes: the ground-truth database builder
+ * Replace the per-frame numpy / numba loop of det3d/datasets/utils/create_gt_database.py:113-120 (points_in_rbbox, then per
+ * object `points[mask]`, `-= centre`, `[:, :5]`) for a batch of frames.  Input: points [P, F] f32 (F >= 3; x, y, z first),
+ * the frames back to back, point_off [B+1] i64; planes [R, 6, 4] f32, (n0, n1, n2, d) per plane, the frames' boxes back to
+ * back, box_off [B+1] i32 ascending inside [0, R].  The planes are built on the host by detector_ops.box_planes with the
+ * reference's own float32 calls (box_np_ops.py:1102-1108, geometry.py:380-405), 16-byte aligned.
+ * Rule (geometry.py:290-303, literally): a point is inside a box iff for all six planes !(sign >= 0),
+ * sign = ((x*n0 + y*n1) + z*n2) + d, every product and sum rounded to float32, no fused multiply-add.  So a NaN sign counts
+ * as inside and a zero-size box (n = d = 0) holds nothing.
+ * Every output is bit-identical from run to run and for every launch shape; no size is limited beyond the index types
+ * (B < 65536, R < 2^31, a frame's points < 2^31).  *status (device int, written by every entry that takes it): a frame
+ * whose point_off / box_off pair is not ascending inside [0, P] / [0, R] (or that has 2^31 points) sets the bit, counts as
+ * empty and nothing of it is read or written.
+ *
+ * (a) al3d_points_in_boxes_count_f32 (create_gt_database.py:113 + :135 `num_points_in_gt`): box_count [R] i32 = members of
+ *     every box; workspace (al3d_points_in_boxes_workspace_bytes(R, groups, threads), -1 for bad arguments; the plain entry
+ *     uses AL3D_PIB_GROUPS, AL3D_PIB_THREADS) receives the per-(wave slot, box) partial counts, scanned, which (b) needs.
+ *     _launch: groups (workgroups per frame) in [1, 1024], threads 64 / 128 / 256, tile (boxes in LDS at a time) in [1, 64]. */
+#define AL3D_PIB_BAD_POINT_OFF 1
+#define AL3D_PIB_BAD_BOX_OFF 2
+#define AL3D_PIB_FRAME_TOO_LARGE 4
+#define AL3D_PIB_BAD_WORKSPACE 8
+#define AL3D_PIB_BAD_ROWS 16
+#define AL3D_PIB_GROUPS 32
+#define AL3D_PIB_THREADS 256
+int64_t al3d_points_in_boxes_workspace_bytes(int64_t R, int groups, int threads);
+int al3d_points_in_boxes_count_f32(const float* points, int64_t P, int F, const int64_t* point_off, int B, const float* planes,
+                                   const int* box_off, int R, int* box_count, void* workspace, int* status, void* stream);
+int al3d_points_in_boxes_count_launch_f32(const float* points, int64_t P, int F, const int64_t* point_off, int B,
+                                          const float* planes, const int* box_off, int R, int* box_count, void* workspace,
+                                          int* status, int groups, int threads, int tile, void* stream);
+/* (b) al3d_points_in_boxes_gather_f32 (create_gt_database.py:117-120): out_off [R+1] i64 = the exclusive sum of box_count,
+ *     centres [R, 3] f32, workspace as (a) left it for the SAME points, offsets, planes, groups and threads (anything else is
+ *     AL3D_PIB_BAD_WORKSPACE and writes nothing).  out [T, F_out] f32, 3 <= F_out <= F: box r's rows are [out_off[r],
+ *     out_off[r+1]), its points in ascending point index, x, y, z minus the centre in float32 and the other columns copied;
+ *     out_index [T] i64 = the row of `points` each output row came from.  A row outside [0, T) is not written and sets
+ *     AL3D_PIB_BAD_ROWS (out_off does not belong to these counts). */
+int al3d_points_in_boxes_gather_f32(const float* points, int64_t P, int F, const int64_t* point_off, int B, const float* planes,
+                                    const int* box_off, int R, const int64_t* out_off, const float* centres,
+                                    const void* workspace, float* out, int F_out, int64_t* out_index, int64_t T, int* status,
+                                    void* stream);
+int al3d_points_in_boxes_gather_launch_f32(const float* points, int64_t P, int F, const int64_t* point_off, int B,
+                                           const float* planes, const int* box_off, int R, const int64_t* out_off,
+                                           const float* centres, const void* workspace, float* out, int F_out,
+                                           int64_t* out_index, int64_t T, int* status, int groups, int threads, int tile,
+                                           void* stream);
+/* (c) al3d_points_in_boxes_mask_u8: the [P, R] matrix of box_np_ops.points_in_rbbox (box_np_ops.py:1102-1108 over
+ *     geometry.py:243-304) for one frame, one byte (0 / 1) per pair.  _launch: threads 64 / 128 / 256, tile in [1, 64]. */
+int al3d_points_in_boxes_mask_u8(const float* points, int64_t P, int F, const float* planes, int R, unsigned char* out,
+                                 void* stream);
+int al3d_points_in_boxes_mask_launch_u8(const float* points, int64_t P, int F, const float* planes, int R, unsigned char* out,
+                                        int threads, int tile, void* stream);
+
 /* ---------------------------------------------------------------- runtime
  * A HIP stream restricted to n_cus compute units starting at first_cu (hipExtStreamCreateWithCUMask); the
  * reference has no analogue (its loader workers are host processes, det3d/datasets/loader/build_loader.py:23-59):
