@@ -11,8 +11,8 @@
 //
 // Whoever changes the split or the product order changes it here, for every kernel at once.
 #pragma once
+#include "conv2d_tile.h"      // f32x16, mfma32_crow
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
@@ -78,7 +78,7 @@ __device__ __forceinline__ B6Frag b6_frag(const unsigned char (&planes)[3][N], i
 }
 
 // C fragment of v_mfma_f32_32x32x16: lane (fr, fh) holds column fr; register r holds this row of the tile
-__device__ __forceinline__ int b6_crow(int r, int fh) { return (r & 3) + 8 * (r >> 2) + 4 * fh; }
+__device__ __forceinline__ int b6_crow(int r, int fh) { return mfma32_crow(r, fh); }      // conv2d_tile.h
 
 // ---- the staged 128 x 128 x 16 tile pipeline (256 threads: four waves of 64 x 64, wave w = (wm, wn) = (w & 1, w >> 1))
 // acc[i][j] += A B over nsteps 16-channel steps, A and B rows staged through double-buffered LDS

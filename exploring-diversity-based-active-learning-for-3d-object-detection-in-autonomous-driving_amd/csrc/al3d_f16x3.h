@@ -31,8 +31,8 @@
 //
 // Whoever changes the split, the lift or the product order changes it here, for every kernel at once.
 #pragma once
+#include "conv2d_tile.h"      // f32x16, mfma32_crow
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));      // the same typedef as al3d_bf16x6.h's (both may be included)
 typedef float f32x4 __attribute__((ext_vector_type(4)));        // native vector: inline-asm register operands
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -195,7 +195,7 @@ __device__ __forceinline__ void f3_mac3(f16x8 ah, f16x8 al, f16x8 wh, f16x8 wl, 
 }
 
 // C fragment of v_mfma_f32_32x32x16: lane (fr, fh) holds column fr; register r holds this row of the tile
-__device__ __forceinline__ int f3_crow(int r, int fh) { return (r & 3) + 8 * (r >> 2) + 4 * fh; }
+__device__ __forceinline__ int f3_crow(int r, int fh) { return mfma32_crow(r, fh); }      // conv2d_tile.h
 
 // counted wait for this wave's outstanding global loads / LDS-DMA requests
 template <int N> __device__ __forceinline__ void f3_wait_vm()

@@ -3,9 +3,11 @@
 //
 // Same role, layouts and tiling as conv2d_mfma.hip (NHWC f32 activations in HBM; 128 px x 128
 // ch tile; 4 waves 2x2; double-buffered LDS); activations are split while they are staged
-// (registers -> LDS), weights are pre-split once into [3][Cout][taps][Cin] bf16.
+// (registers -> LDS), weights are pre-split once into [3][Cout][taps][Cin] bf16.  The pixel-tile side (parameter block, tile
+// decode, input pixel, epilogues, entry-point checks) is conv2d_tile.h's.
 #include "al3d_common.h"
 #include "al3d_bf16x6.h"
+#include "conv2d_tile.h"
 
 #define C6_BM 128
 #define C6_BN 128
@@ -13,15 +15,8 @@
 #define C6_TH 8
 #define C6_TW 16
 
-struct Conv6Params {
-    const float* in;        // [B, H, W, Cin] f32
+struct Conv6Params : ConvGeom {
     const __bf16* wgt;      // [3][Cout][taps][Cin] bf16 planes (hi, mid, lo)
-    const float* scale;
-    const float* shift;
-    float* out;
-    int B, H, W, Cin, Cout, OH, OW, ldc, coff;
-    int ksize, stride, pad, relu;
-    int tiles_x, tiles_y;
     int64_t plane;          // elements per weight plane = Cout * taps * Cin
 };
 
@@ -32,12 +27,9 @@ __global__ __launch_bounds__(256, 2) void conv2d_bf16x6_kernel(Conv6Params p)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave & 1, wn = wave >> 1;
-    int tile = blockIdx.x;
-    const int tx_ = tile % p.tiles_x; tile /= p.tiles_x;
-    const int ty_ = tile % p.tiles_y; tile /= p.tiles_y;
-    const int b = tile;
+    int tx_, ty_, b;
+    conv_tile_decode(blockIdx.x, p.tiles_x, p.tiles_y, tx_, ty_, b);
     const int n0 = blockIdx.y * C6_BN;
-    const int MH = MODE == 0 ? p.OH : p.H, MW = MODE == 0 ? p.OW : p.W;
     const int taps = MODE == 0 ? p.ksize * p.ksize : 1;
     const int tap0 = MODE == 0 ? 0 : blockIdx.z;
     const int wtaps = MODE == 0 ? taps : 4;
@@ -53,12 +45,8 @@ __global__ __launch_bounds__(256, 2) void conv2d_bf16x6_kernel(Conv6Params p)
             const int m = row + 64 * i;
             const int py = ty_ * C6_TH + m / C6_TW, px = tx_ * C6_TW + m % C6_TW;
             int iy, ix;
-            if (MODE == 0) { iy = py * p.stride - p.pad + ky; ix = px * p.stride - p.pad + kx; }
-            else { iy = py; ix = px; }
-            const bool ok = py < MH && px < MW && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-            ra[i] = ok ? *reinterpret_cast<const float4*>(
-                             p.in + (((int64_t)b * p.H + iy) * p.W + ix) * p.Cin + c0 + 4 * q)
-                       : make_float4(0.f, 0.f, 0.f, 0.f);
+            const bool ok = conv_tap_pixel<MODE>(p, py, px, ky, kx, iy, ix);
+            ra[i] = conv_load4(p, ok, b, iy, ix, c0 + 4 * q);
         }
     };
     auto load_b = [&](int step, int row, int q, uint4 (&rb)[3]) {
@@ -73,28 +61,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_bf16x6_kernel(Conv6Params p)
     f32x16 acc[2][2];
     b6_tile_pipeline(taps * kchunks, load_a, load_b, acc);
 
-    const int fr = lane & 31, fh = lane >> 5;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int n = n0 + wn * 64 + j * 32 + fr;
-        if (n >= p.Cout) continue;
-        const float sc = p.scale ? p.scale[n] : 1.0f;
-        const float sh = p.shift ? p.shift[n] : 0.0f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = wm * 64 + i * 32 + b6_crow(r, fh);
-                const int y = ty_ * C6_TH + m / C6_TW, x = tx_ * C6_TW + m % C6_TW;
-                if (y >= MH || x >= MW) continue;
-                float v = acc[i][j][r] * sc + sh;
-                if (p.relu) v = v <= 0.f ? 0.f : v;                   // NaN propagates, like torch.relu
-                int oy = y, ox = x;
-                if (MODE == 1) { oy = 2 * y + (tap0 >> 1); ox = 2 * x + (tap0 & 1); }
-                p.out[(((int64_t)b * p.OH + oy) * p.OW + ox) * p.ldc + p.coff + n] = v;
-            }
-        }
-    }
+    conv_store_patch<MODE, C6_TH, C6_TW, 2, 2, true, false>(p, acc, b, ty_, tx_, wm, n0 + wn * 64, tap0, lane);
 }
 
 // ------------------------------------------------------------------ 3x3 / stride 1 / pad 1
@@ -132,10 +99,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16x6_halo_kernel(Conv6Params
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave & 1, wn = wave >> 1;
     const int fr = lane & 31, fh = lane >> 5;
-    int tile = blockIdx.x;
-    const int tx_ = tile % p.tiles_x; tile /= p.tiles_x;
-    const int ty_ = tile % p.tiles_y; tile /= p.tiles_y;
-    const int b = tile;
+    int tx_, ty_, b;
+    conv_tile_decode(blockIdx.x, p.tiles_x, p.tiles_y, tx_, ty_, b);
     const int n0 = blockIdx.y * C6_BN;
     const int y0 = ty_ * H3_TH - 1, x0 = tx_ * H3_TW - 1;       // image coords of halo (0,0)
     const int nchunks = p.Cin / C6_BK;
@@ -149,11 +114,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16x6_halo_kernel(Conv6Params
         for (int i = 0; i < 4; ++i) {
             const int piece = tid + 256 * i;
             const int hp = piece >> 2, q = piece & 3;
-            const int iy = y0 + hp / H3_HW, ix = x0 + hp % H3_HW;
-            const bool ok = hp < H3_HP && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-            rh[i] = ok ? *reinterpret_cast<const float4*>(
-                             p.in + (((int64_t)b * p.H + iy) * p.W + ix) * p.Cin + c0 + 4 * q)
-                       : make_float4(0.f, 0.f, 0.f, 0.f);
+            int iy, ix;
+            const bool ok = conv_halo_pixel<H3_HW>(p, y0, x0, hp, hp < H3_HP, iy, ix);
+            rh[i] = conv_load4(p, ok, b, iy, ix, c0 + 4 * q);
         }
     };
     auto store_halo = [&]() {
@@ -182,12 +145,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16x6_halo_kernel(Conv6Params
     };
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    conv_acc_clear(acc);
 
     const int total = 9 * nchunks;                    // steps; step s = chunk * 9 + tap, B(s) lives in buffer tap % 3
     load_halo(0);
@@ -246,25 +204,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16x6_halo_kernel(Conv6Params
         }
     }
 
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int n = n0 + wn * 64 + j * 32 + fr;
-        if (n >= p.Cout) continue;
-        const float sc = p.scale ? p.scale[n] : 1.0f;
-        const float sh = p.shift ? p.shift[n] : 0.0f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int y = ty_ * H3_TH + 2 * wm + i;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int x = tx_ * H3_TW + b6_crow(r, fh);
-                if (y >= p.OH || x >= p.OW) continue;
-                float v = acc[i][j][r] * sc + sh;
-                if (p.relu) v = v <= 0.f ? 0.f : v;                   // NaN propagates, like torch.relu
-                p.out[(((int64_t)b * p.OH + y) * p.OW + x) * p.ldc + p.coff + n] = v;
-            }
-        }
-    }
+    conv_store_rows<H3_TH, H3_TW, 2, 2, true>(p, acc, b, ty_, tx_, 2 * wm, n0 + wn * 64, lane);
 }
 
 // one-off weight split: f32 [count] -> bf16 [3][count]
@@ -306,45 +246,24 @@ extern "C" int al3d_merge_bf16x3(const void* planes_bf16x3, int64_t count, float
     return AL3D_OK;
 }
 
-static int conv6_check(const Conv6Params& p, const char* name)
-{
-    AL3D_REQUIRE(p.in && p.wgt && p.out, "%s: null pointer", name);
-    AL3D_REQUIRE(p.B >= 1 && p.H >= 1 && p.W >= 1 && p.Cin >= 1 && p.Cout >= 1, "%s: bad shape", name);
-    AL3D_REQUIRE(p.Cin % C6_BK == 0, "%s: Cin=%d must be a multiple of %d", name, p.Cin, C6_BK);
-    AL3D_REQUIRE(p.coff >= 0 && p.coff + p.Cout <= p.ldc, "%s: channel window [%d,%d) exceeds ldc=%d",
-                 name, p.coff, p.coff + p.Cout, p.ldc);
-    AL3D_REQUIRE(((uintptr_t)p.in & 15) == 0 && ((uintptr_t)p.wgt & 15) == 0,
-                 "%s: in/wgt must be 16-byte aligned", name);
-    return AL3D_OK;
-}
-
 extern "C" int al3d_conv2d_nhwc_bf16x6(const float* in, const void* wgt_bf16x3, const float* scale,
                                        const float* shift, float* out, int B, int H, int W, int Cin,
                                        int Cout, int ksize, int stride, int pad, int ldc, int coff,
                                        int relu, void* stream)
 {
+    const bool halo = ksize == 3 && stride == 1 && pad == 1;     // halo-staged fast path
     Conv6Params p;
-    p.in = in; p.wgt = (const __bf16*)wgt_bf16x3; p.scale = scale; p.shift = shift; p.out = out;
-    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
-    p.ksize = ksize; p.stride = stride; p.pad = pad; p.ldc = ldc; p.coff = coff; p.relu = relu;
-    AL3D_REQUIRE(ksize >= 1 && ksize <= 7 && stride >= 1 && pad >= 0, "al3d_conv2d_nhwc_bf16x6: bad geometry");
-    p.OH = (H + 2 * pad - ksize) / stride + 1;
-    p.OW = (W + 2 * pad - ksize) / stride + 1;
-    AL3D_REQUIRE(p.OH >= 1 && p.OW >= 1, "al3d_conv2d_nhwc_bf16x6: empty output");
+    p.wgt = (const __bf16*)wgt_bf16x3;
     p.plane = (int64_t)Cout * ksize * ksize * Cin;
-    int rc = conv6_check(p, "al3d_conv2d_nhwc_bf16x6");
+    int rc = conv_geom_build(p, "al3d_conv2d_nhwc_bf16x6", false, halo ? H3_TH : C6_TH, halo ? H3_TW : C6_TW, C6_BK, false, in,
+                             wgt_bf16x3, scale, shift, out, B, H, W, Cin, Cout, ksize, stride, pad, ldc, coff, relu);
     if (rc) return rc;
-    if (ksize == 3 && stride == 1 && pad == 1) {     // halo-staged fast path
-        p.tiles_x = (int)al3d_cdiv(p.OW, H3_TW);
-        p.tiles_y = (int)al3d_cdiv(p.OH, H3_TH);
-        dim3 grid((unsigned)(p.tiles_x * p.tiles_y * B), (unsigned)al3d_cdiv(Cout, C6_BN), 1);
+    dim3 grid((unsigned)(p.tiles_x * p.tiles_y * B), (unsigned)al3d_cdiv(Cout, C6_BN), 1);
+    if (halo) {
         hipLaunchKernelGGL(conv3x3_bf16x6_halo_kernel, grid, dim3(256), 0, (hipStream_t)stream, p);
         AL3D_CHECK_LAUNCH("conv3x3_bf16x6_halo_kernel");
         return AL3D_OK;
     }
-    p.tiles_x = (int)al3d_cdiv(p.OW, C6_TW);
-    p.tiles_y = (int)al3d_cdiv(p.OH, C6_TH);
-    dim3 grid((unsigned)(p.tiles_x * p.tiles_y * B), (unsigned)al3d_cdiv(Cout, C6_BN), 1);
     hipLaunchKernelGGL(conv2d_bf16x6_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, p);
     AL3D_CHECK_LAUNCH("conv2d_bf16x6_kernel<conv>");
     return AL3D_OK;
@@ -355,15 +274,11 @@ extern "C" int al3d_deconv2x2_nhwc_bf16x6(const float* in, const void* wgt_bf16x
                                           int Cout, int ldc, int coff, int relu, void* stream)
 {
     Conv6Params p;
-    p.in = in; p.wgt = (const __bf16*)wgt_bf16x3; p.scale = scale; p.shift = shift; p.out = out;
-    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
-    p.ksize = 2; p.stride = 2; p.pad = 0; p.ldc = ldc; p.coff = coff; p.relu = relu;
-    p.OH = 2 * H; p.OW = 2 * W;
+    p.wgt = (const __bf16*)wgt_bf16x3;
     p.plane = (int64_t)Cout * 4 * Cin;
-    int rc = conv6_check(p, "al3d_deconv2x2_nhwc_bf16x6");
+    int rc = conv_geom_build(p, "al3d_deconv2x2_nhwc_bf16x6", true, C6_TH, C6_TW, C6_BK, false, in, wgt_bf16x3, scale, shift, out,
+                             B, H, W, Cin, Cout, 2, 2, 0, ldc, coff, relu);
     if (rc) return rc;
-    p.tiles_x = (int)al3d_cdiv(W, C6_TW);
-    p.tiles_y = (int)al3d_cdiv(H, C6_TH);
     dim3 grid((unsigned)(p.tiles_x * p.tiles_y * B), (unsigned)al3d_cdiv(Cout, C6_BN), 4);
     hipLaunchKernelGGL(conv2d_bf16x6_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, p);
     AL3D_CHECK_LAUNCH("conv2d_bf16x6_kernel<deconv>");

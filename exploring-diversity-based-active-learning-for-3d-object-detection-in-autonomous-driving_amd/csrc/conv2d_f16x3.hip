@@ -3,7 +3,8 @@
 //
 // Same role, layouts and tiling as conv2d_bf16x6.hip: NHWC f32 activations in HBM, split while
 // they are staged; weights pre-split into [2][Cout][taps][Cin] f16.  Half the MFMAs, 4 instead
-// of 6 fragment reads per step, 2/3 of the LDS.
+// of 6 fragment reads per step, 2/3 of the LDS.  The pixel-tile side (parameter block, tile decode, input pixel, the
+// untransposed epilogues, entry-point checks) is conv2d_tile.h's.
 //
 // Kernels in this file (all bit-identical to one another on the same layer):
 //   conv3x3_f16x3_frag_kernel     3x3/s1/p1, halo in LDS, weights streamed in fragment order   (default)
@@ -12,6 +13,7 @@
 //   conv2d_f16x3_kernel           any geometry, both tiles through LDS                         (short launches, deconv)
 #include "al3d_common.h"
 #include "sp_rows.h"
+#include "conv2d_tile.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -53,15 +55,8 @@ static const F3Knobs& f3_knobs()
     return knobs;
 }
 
-struct ConvF3Params {
-    const float* in;        // [B, H, W, Cin] f32
+struct ConvF3Params : ConvGeom {          // scale = BN scale * 2^-s, required
     const _Float16* wgt;    // [2][Cout][taps][Cin] f16 planes (wh, wl)
-    const float* scale;     // BN scale * 2^-s
-    const float* shift;
-    float* out;
-    int B, H, W, Cin, Cout, OH, OW, ldc, coff;
-    int ksize, stride, pad, relu;
-    int tiles_x, tiles_y;
     int nblocks, ntiles;    // 128-channel column blocks; pixel tiles (tiles_x * tiles_y * B)
     int64_t plane;          // elements per weight plane = Cout * taps * Cin
     float* gap;             // optional [B][gap_parts][ldc]: per-workgroup channel sums of the stored values (fused GAP)
@@ -83,18 +78,6 @@ static inline unsigned f3_grid(const ConvF3Params& p)
 
 #define F3_IC(v) std::integral_constant<int, v>{}
 
-static int convf3_check(const ConvF3Params& p, const char* name)
-{
-    AL3D_REQUIRE(p.in && p.wgt && p.out && p.scale, "%s: null pointer (scale carries the weight exponent and is required)", name);
-    AL3D_REQUIRE(p.B >= 1 && p.H >= 1 && p.W >= 1 && p.Cin >= 1 && p.Cout >= 1, "%s: bad shape", name);
-    AL3D_REQUIRE(p.Cin % F3_BK == 0, "%s: Cin=%d must be a multiple of %d", name, p.Cin, F3_BK);
-    AL3D_REQUIRE(p.coff >= 0 && p.coff + p.Cout <= p.ldc, "%s: channel window [%d,%d) exceeds ldc=%d",
-                 name, p.coff, p.coff + p.Cout, p.ldc);
-    AL3D_REQUIRE(((uintptr_t)p.in & 15) == 0 && ((uintptr_t)p.wgt & 15) == 0,
-                 "%s: in/wgt must be 16-byte aligned", name);
-    return AL3D_OK;
-}
-
 template <int MODE>
 __global__ __launch_bounds__(256, 2) void conv2d_f16x3_kernel(ConvF3Params p)
 {
@@ -105,11 +88,9 @@ __global__ __launch_bounds__(256, 2) void conv2d_f16x3_kernel(ConvF3Params p)
     const int wm = wave & 1, wn = wave >> 1;
     int tile, nblk;
     if (!f3_tile_of_block(p.ntiles, p.nblocks, p.xmap, tile, nblk)) return;     // padding block of the last group (uniform)
-    const int tx_ = tile % p.tiles_x; tile /= p.tiles_x;
-    const int ty_ = tile % p.tiles_y; tile /= p.tiles_y;
-    const int b = tile;
+    int tx_, ty_, b;
+    conv_tile_decode(tile, p.tiles_x, p.tiles_y, tx_, ty_, b);
     const int n0 = nblk * F3_BN;
-    const int MH = MODE == 0 ? p.OH : p.H, MW = MODE == 0 ? p.OW : p.W;
     const int taps = MODE == 0 ? p.ksize * p.ksize : 1;
     const int tap0 = MODE == 0 ? 0 : blockIdx.z;
     const int wtaps = MODE == 0 ? taps : 4;
@@ -134,12 +115,8 @@ __global__ __launch_bounds__(256, 2) void conv2d_f16x3_kernel(ConvF3Params p)
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             int iy, ix;
-            if (MODE == 0) { iy = py[i] * p.stride - p.pad + ky; ix = px[i] * p.stride - p.pad + kx; }
-            else { iy = py[i]; ix = px[i]; }
-            const bool ok = py[i] < MH && px[i] < MW && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-            ra[i] = ok ? *reinterpret_cast<const float4*>(
-                             p.in + (((int64_t)b * p.H + iy) * p.W + ix) * p.Cin + c0 + 4 * aq)
-                       : make_float4(0.f, 0.f, 0.f, 0.f);
+            const bool ok = conv_tap_pixel<MODE>(p, py[i], px[i], ky, kx, iy, ix);
+            ra[i] = conv_load4(p, ok, b, iy, ix, c0 + 4 * aq);
         }
         const int n = n0 + br;
 #pragma unroll
@@ -163,12 +140,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_f16x3_kernel(ConvF3Params p)
     };
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    conv_acc_clear(acc);
 
     load_step(0);
     store_step(0);
@@ -195,50 +167,15 @@ __global__ __launch_bounds__(256, 2) void conv2d_f16x3_kernel(ConvF3Params p)
         __syncthreads();
     }
 
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int n = n0 + wn * 64 + j * 32 + fr;
-        if (n >= p.Cout) continue;
-        const float sc = p.scale[n];
-        const float sh = p.shift ? p.shift[n] : 0.0f;
-        float gsum = 0.f;                                             // this lane's column: sum of the values it stores
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = wm * 64 + i * 32 + f3_crow(r, fh);
-                const int y = ty_ * F3_TH + m / F3_TW, x = tx_ * F3_TW + m % F3_TW;
-                if (y >= MH || x >= MW) continue;
-                float v = acc[i][j][r] * sc + sh;
-                if (p.relu) v = v <= 0.f ? 0.f : v;                   // NaN propagates, like torch.relu
-                int oy = y, ox = x;
-                if (MODE == 1) { oy = 2 * y + (tap0 >> 1); ox = 2 * x + (tap0 & 1); }
-                p.out[(((int64_t)b * p.OH + oy) * p.OW + ox) * p.ldc + p.coff + n] = v;
-                gsum += v;
-            }
-        }
-        if (p.gap) {
-            // fused global average pooling: one partial per (workgroup, wave row) and channel, fixed order
-            // (rows of the lane, then the other half of the fragment), reduced by gap_parts_reduce_kernel
-            gsum += __shfl_xor(gsum, 32);
-            if (fh == 0) {
-                const int part = (((ty_ * p.tiles_x + tx_) * (MODE == 1 ? 4 : 1) + tap0) << 1) + wm;
-                p.gap[((int64_t)b * p.gap_parts + part) * p.ldc + p.coff + n] = gsum;
-            }
-        }
-    }
+    // epilogue with the fused GAP partials (conv2d_tile.h)
+    conv_store_patch<MODE, F3_TH, F3_TW, 2, 2, false, true>(p, acc, b, ty_, tx_, wm, n0 + wn * 64, tap0, lane, p.gap, p.gap_parts);
 }
 
 // out[b][c] = (sum over the parts, ascending) / count
 __global__ __launch_bounds__(64) void gap_parts_reduce_kernel(const float* __restrict__ gap, int parts, int C, float count,
                                                                float* __restrict__ out)
 {
-    const int b = blockIdx.y, c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    float s = 0.f;
-#pragma unroll 16
-    for (int q = 0; q < parts; ++q) s += gap[((int64_t)b * parts + q) * C + c];
-    out[(int64_t)b * C + c] = s / count;
+    gap_cols_reduce(gap, parts, C, count, out);
 }
 
 // ------------------------------------------------------------------ 3x3 / stride 1 / pad 1
@@ -285,9 +222,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_halo_kernel(ConvF3Params
     const int fr = lane & 31, fh = lane >> 5;
     int tile, nblk;
     if (!f3_tile_of_block(p.ntiles, p.nblocks, p.xmap, tile, nblk)) return;     // padding block of the last group (uniform)
-    const int tx_ = tile % p.tiles_x; tile /= p.tiles_x;
-    const int ty_ = tile % p.tiles_y; tile /= p.tiles_y;
-    const int b = tile;
+    int tx_, ty_, b;
+    conv_tile_decode(tile, p.tiles_x, p.tiles_y, tx_, ty_, b);
     const int n0 = nblk * F3_BN;
     const int y0 = ty_ * G3_TH - 1, x0 = tx_ * G3_TW - 1;       // image coords of halo (0,0)
     const int nchunks = p.Cin / F3_BK;
@@ -302,10 +238,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_halo_kernel(ConvF3Params
             const int i = 2 * half + k;
             const int piece = tid + 256 * i;
             const int hp = piece >> 2, q = piece & 3;
-            const int iy = y0 + hp / G3_HW, ix = x0 + hp % G3_HW;
-            const bool ok = hp < G3_HP && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-            const float* src = p.in + (((int64_t)b * p.H + iy) * p.W + ix) * p.Cin + chunk * F3_BK + 4 * q;
-            rh[k] = *reinterpret_cast<const float4*>(ok ? src : zero);
+            int iy, ix;
+            const bool ok = conv_halo_pixel<G3_HW>(p, y0, x0, hp, hp < G3_HP, iy, ix);
+            rh[k] = conv_load4(p, ok, b, iy, ix, chunk * F3_BK + 4 * q, zero);
         }
     };
     auto store_halo = [&](int buf, int half) {
@@ -346,12 +281,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_halo_kernel(ConvF3Params
     };
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    conv_acc_clear(acc);
 
     const int a_off = ((2 * wm) * G3_HW + fr) * F3_LDB + 16 * fh;
     const int b_off = (wn * 64 + fr) * G3_BROW + 16 * (fh ^ ((fr >> 3) & 1));   // +32 rows keeps bit 3
@@ -445,25 +375,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_halo_kernel(ConvF3Params
         chunk_body(F3_IC(1), chunk0 + 1);
     }
 
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int n = n0 + wn * 64 + j * 32 + fr;
-        if (n >= p.Cout) continue;
-        const float sc = p.scale[n];
-        const float sh = p.shift ? p.shift[n] : 0.0f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int y = ty_ * G3_TH + 2 * wm + i;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int x = tx_ * G3_TW + f3_crow(r, fh);
-                if (y >= p.OH || x >= p.OW) continue;
-                float v = acc[i][j][r] * sc + sh;
-                if (p.relu) v = v <= 0.f ? 0.f : v;                   // NaN propagates, like torch.relu
-                p.out[(((int64_t)b * p.OH + y) * p.OW + x) * p.ldc + p.coff + n] = v;
-            }
-        }
-    }
+    conv_store_rows<G3_TH, G3_TW, 2, 2, false>(p, acc, b, ty_, tx_, 2 * wm, n0 + wn * 64, lane);
 }
 
 // ------------------------------------------------------------------ 3x3 / stride 1 / pad 1, weights from L2
@@ -505,9 +417,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_frag_kernel(ConvF3Params
     const int fr = lane & 31, fh = lane >> 5;
     int tile, nblk;
     if (!f3_tile_of_block(p.ntiles, p.nblocks, p.xmap, tile, nblk)) return;     // padding block of the last group (uniform)
-    const int tx_ = tile % p.tiles_x; tile /= p.tiles_x;
-    const int ty_ = tile % p.tiles_y; tile /= p.tiles_y;
-    const int b = tile;
+    int tx_, ty_, b;
+    conv_tile_decode(tile, p.tiles_x, p.tiles_y, tx_, ty_, b);
     const int n0 = nblk * F3_BN;
     const int y0 = ty_ * G3_TH - 1, x0 = tx_ * G3_TW - 1;       // image coords of halo (0,0)
     const int nchunks = p.Cin / F3_BK;
@@ -527,8 +438,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_frag_kernel(ConvF3Params
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int hp = (tid + 256 * k) >> 2;
-            const int iy = y0 + hp / G3_HW, ix = x0 + hp % G3_HW;
-            const bool ok = hp < G3_HP && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
+            int iy, ix;
+            const bool ok = conv_halo_pixel<G3_HW>(p, y0, x0, hp, hp < G3_HP, iy, ix);
             const int* src = p.bev + (((int64_t)b * p.H + iy) * p.W + ix) * 2;
             hrow[k] = ok ? *reinterpret_cast<const int2*>(src) : make_int2(-1, -1);
             if (hrow[k].x >= 0 || hrow[k].y >= 0) mine |= 1u << (hp / G3_HW);
@@ -552,10 +463,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_frag_kernel(ConvF3Params
                 const float2 a1 = *reinterpret_cast<const float2*>(r.y >= 0 ? s1 : zero);
                 rh[(HALO_FAR ? 2 * half : 0) + k] = make_float4(a0.x, a1.x, a0.y, a1.y);
             } else {
-                const int iy = y0 + hp / G3_HW, ix = x0 + hp % G3_HW;
-                const bool ok = hp < G3_HP && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-                const float* src = p.in + (((int64_t)b * p.H + iy) * p.W + ix) * p.Cin + chunk * F3_BK + 4 * q;
-                rh[(HALO_FAR ? 2 * half : 0) + k] = *reinterpret_cast<const float4*>(ok ? src : zero);
+                int iy, ix;
+                const bool ok = conv_halo_pixel<G3_HW>(p, y0, x0, hp, hp < G3_HP, iy, ix);
+                rh[(HALO_FAR ? 2 * half : 0) + k] = conv_load4(p, ok, b, iy, ix, chunk * F3_BK + 4 * q, zero);
             }
         }
     };
@@ -597,12 +507,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_frag_kernel(ConvF3Params
     };
 
     f32x16 acc[NI][NJ];
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    conv_acc_clear(acc);
 
     const int a_off = (row0 * G3_HW + fr) * F3_LDB + 16 * fh;
     f16x8 fa[2][2][NI];                               // [set][plane][tile]
@@ -706,6 +611,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_frag_kernel(ConvF3Params
     }
 
     if constexpr (IO != 1) {
+        // Private to this kernel (not conv2d_tile.h's row epilogue): the scratch is the halo storage and IO = 2 writes pair pixels.
         // Each image row of the wave's tile (32 pixels x 64 channels) goes through a wave-private scratch in the halo
         // storage so that a lane holds 8 consecutive channels of a pixel and stores 32 contiguous bytes with two
         // 16-byte stores (-3 % against one dword per lane and C register straight from the fragment layout; IO = 1
@@ -756,24 +662,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_frag_kernel(ConvF3Params
         }
         return;
     }
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int n = n0 + ch0 + j * 32 + fr;
-        const float sc = p.scale[n];
-        const float sh = p.shift ? p.shift[n] : 0.0f;
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            const int y = ty_ * G3_TH + row0 + i;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int x = tx_ * G3_TW + f3_crow(r, fh);
-                if (y >= p.OH || x >= p.OW) continue;
-                float v = acc[i][j][r] * sc + sh;
-                if (p.relu) v = v <= 0.f ? 0.f : v;                   // NaN propagates, like torch.relu
-                p.out[(((int64_t)b * p.OH + y) * p.OW + x) * p.ldc + p.coff + n] = v;
-            }
-        }
-    }
+    conv_store_rows<G3_TH, G3_TW, NI, NJ, false, false>(p, acc, b, ty_, tx_, row0, n0 + ch0, lane);     // Cout % 128 == 0: no channel test
 }
 
 // ------------------------------------------------------------------ 3x3 / stride 1 / pad 1 on v_mfma_f32_16x16x32_f16
@@ -801,9 +690,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_frag16_kernel(ConvF3Para
     const int lr = lane & 15, lq = lane >> 4;
     int tile, nblk;
     if (!f3_tile_of_block(p.ntiles, p.nblocks, p.xmap, tile, nblk)) return;     // padding block of the last group (uniform)
-    const int tx_ = tile % p.tiles_x; tile /= p.tiles_x;
-    const int ty_ = tile % p.tiles_y; tile /= p.tiles_y;
-    const int b = tile;
+    int tx_, ty_, b;
+    conv_tile_decode(tile, p.tiles_x, p.tiles_y, tx_, ty_, b);
     const int n0 = nblk * F3_BN;
     const int y0 = ty_ * G3_TH - 1, x0 = tx_ * G3_TW - 1;       // image coords of halo (0,0)
     const int npairs = p.Cin / 32;
@@ -818,10 +706,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_frag16_kernel(ConvF3Para
             const int piece = tid + 256 * (2 * quarter + k);
             const int c = piece >= 816 ? 1 : 0, rem = piece - 816 * c;
             const int hp = rem >> 2, q = rem & 3;
-            const int iy = y0 + hp / G3_HW, ix = x0 + hp % G3_HW;
-            const bool ok = piece < 1632 && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-            const float* src = p.in + (((int64_t)b * p.H + iy) * p.W + ix) * p.Cin + (2 * pair + c) * F3_BK + 4 * q;
-            rh[k] = *reinterpret_cast<const float4*>(ok ? src : zero);
+            int iy, ix;
+            const bool ok = conv_halo_pixel<G3_HW>(p, y0, x0, hp, piece < 1632, iy, ix);
+            rh[k] = conv_load4(p, ok, b, iy, ix, (2 * pair + c) * F3_BK + 4 * q, zero);
         }
     };
     auto store_halo = [&](int buf, int quarter) {
@@ -928,7 +815,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f16x3_frag16_kernel(ConvF3Para
         pair_body(F3_IC(1), pair0 + 1);
     }
 
-    // C fragment of a 16 x 16 tile: lane (lr, lq) holds column lr, rows 4*lq .. 4*lq + 3
+    // C fragment of a 16 x 16 tile: lane (lr, lq) holds column lr, rows 4*lq .. 4*lq + 3 (its own epilogue: conv2d_tile.h's are
+    // written over 32 x 32 fragments)
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int n = n0 + wn * 64 + j * 16 + lr;
@@ -966,11 +854,9 @@ __global__ __launch_bounds__(256, 2) void conv2d_f16x3_bstream_kernel(ConvF3Para
     const int wm = wave & 1, wn = wave >> 1;
     int tile, nblk;
     if (!f3_tile_of_block(p.ntiles, p.nblocks, p.xmap, tile, nblk)) return;     // padding block of the last group (uniform)
-    const int tx_ = tile % p.tiles_x; tile /= p.tiles_x;
-    const int ty_ = tile % p.tiles_y; tile /= p.tiles_y;
-    const int b = tile;
+    int tx_, ty_, b;
+    conv_tile_decode(tile, p.tiles_x, p.tiles_y, tx_, ty_, b);
     const int n0 = nblk * F3_BN;
-    const int MH = MODE == 0 ? p.OH : p.H, MW = MODE == 0 ? p.OW : p.W;
     const int taps = MODE == 0 ? p.ksize * p.ksize : 1;
     const int tap0 = MODE == 0 ? 0 : blockIdx.z;
     const int wtaps = MODE == 0 ? taps : 4;
@@ -994,11 +880,8 @@ __global__ __launch_bounds__(256, 2) void conv2d_f16x3_bstream_kernel(ConvF3Para
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             int iy, ix;
-            if (MODE == 0) { iy = py[i] * p.stride - p.pad + ky; ix = px[i] * p.stride - p.pad + kx; }
-            else { iy = py[i]; ix = px[i]; }
-            const bool ok = py[i] < MH && px[i] < MW && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-            const float* src = p.in + (((int64_t)b * p.H + iy) * p.W + ix) * p.Cin + lchunk * F3_BK + 4 * aq;
-            ra[i] = *reinterpret_cast<const float4*>(ok ? src : zero);
+            const bool ok = conv_tap_pixel<MODE>(p, py[i], px[i], ky, kx, iy, ix);
+            ra[i] = conv_load4(p, ok, b, iy, ix, lchunk * F3_BK + 4 * aq, zero);
         }
         if (ltap * kchunks + lchunk + 1 < total) { if (++lchunk == kchunks) { lchunk = 0; ++ltap; } }
     };
@@ -1037,12 +920,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_f16x3_bstream_kernel(ConvF3Para
     };
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    conv_acc_clear(acc);
 
     const int fr = lane & 31, fh = lane >> 5;
     const int a_off = (wm * 64 + fr) * F3_LDB + 16 * fh;
@@ -1085,27 +963,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_f16x3_bstream_kernel(ConvF3Para
         step(F3_IC(3), s0 + 3); step(F3_IC(4), s0 + 4); step(F3_IC(5), s0 + 5);
     }
 
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int n = n0 + wn * 64 + j * 32 + fr;
-        if (n >= p.Cout) continue;
-        const float sc = p.scale[n];
-        const float sh = p.shift ? p.shift[n] : 0.0f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = wm * 64 + i * 32 + f3_crow(r, fh);
-                const int y = ty_ * F3_TH + m / F3_TW, x = tx_ * F3_TW + m % F3_TW;
-                if (y >= MH || x >= MW) continue;
-                float v = acc[i][j][r] * sc + sh;
-                if (p.relu) v = v <= 0.f ? 0.f : v;                   // NaN propagates, like torch.relu
-                int oy = y, ox = x;
-                if (MODE == 1) { oy = 2 * y + (tap0 >> 1); ox = 2 * x + (tap0 & 1); }
-                p.out[(((int64_t)b * p.OH + oy) * p.OW + ox) * p.ldc + p.coff + n] = v;
-            }
-        }
-    }
+    conv_store_patch<MODE, F3_TH, F3_TW, 2, 2, false, false>(p, acc, b, ty_, tx_, wm, n0 + wn * 64, tap0, lane);
 }
 
 // planes [2][Cout][taps][Cin] -> [2][ceil(Cout/128)*4][taps][Cin/16][64][8], zero rows beyond Cout
@@ -1147,7 +1005,7 @@ extern "C" int al3d_pack_f16x3_bstream(const void* planes_f16x2, int Cout, int t
 // ------------------------------------------------------------------ host side: one parameter builder for every launch
 // What a kernel family asks of a launch: its workgroup's pixel tile, whether the kernel strides over two weight planes
 // (the fragment-ordered and LDS-image formats of the generic kernels interleave them: plane = 0), and the checks it
-// adds to convf3_check
+// adds to conv_geom_check
 struct ConvF3Family {
     int th, tw;
     bool planes;         // p.plane = Cout * taps * Cin
@@ -1169,29 +1027,22 @@ static int convf3_launch(const char* name, const char* kernel, const ConvF3Famil
 {
     ConvF3Params p;
     p.gap = gap; p.gap_parts = gap_parts; p.io = io;
-    p.in = in; p.wgt = (const _Float16*)wgt; p.scale = scale; p.shift = shift; p.out = out;
-    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
-    p.ksize = ksize; p.stride = stride; p.pad = pad; p.ldc = ldc; p.coff = coff; p.relu = relu;
+    p.wgt = (const _Float16*)wgt;
     if (fam.dma) {
         AL3D_REQUIRE(io >= 0 && io < 4 && (!(io & 2) || (Cout % 8 == 0 && ldc % 8 == 0 && coff % 8 == 0)),
                      "%s: bad io flags (pair output needs Cout, ldc, coff multiples of 8)", name);
         AL3D_REQUIRE(io == 0 || (f3_knobs().dma_pipe && f3_knobs().dma_stages == 3),
                      "%s: pair pixels need the shipped kernel shape (AL3D_DMA_PIPE=1, 3 stages)", name);
     }
-    AL3D_REQUIRE(ksize >= 1 && ksize <= 7 && stride >= 1 && pad >= 0, "%s: bad geometry", name);
-    p.OH = deconv ? 2 * H : (H + 2 * pad - ksize) / stride + 1;
-    p.OW = deconv ? 2 * W : (W + 2 * pad - ksize) / stride + 1;
-    AL3D_REQUIRE(deconv || (p.OH >= 1 && p.OW >= 1), "%s: empty output", name);
-    p.plane = fam.planes ? (int64_t)Cout * (deconv ? 4 : ksize * ksize) * Cin : 0;
-    int rc = convf3_check(p, name);
+    int rc = conv_geom_build(p, name, deconv, fam.th, fam.tw, F3_BK, true, in, wgt, scale, shift, out, B, H, W, Cin, Cout, ksize,
+                             stride, pad, ldc, coff, relu);
     if (rc) return rc;
+    p.plane = fam.planes ? (int64_t)Cout * (deconv ? 4 : ksize * ksize) * Cin : 0;
     AL3D_REQUIRE(!fam.cin_mult || (Cout % 128 == 0 && Cin % fam.cin_mult == 0),
                  "%s: needs Cout %% 128 == 0 and Cin %% %d == 0 (got %d, %d)", name, fam.cin_mult, Cout, Cin);
     AL3D_REQUIRE(!fam.dma || (int64_t)B * H * W * Cin < ((int64_t)1 << 31), "%s: input above 2^31 elements", name);
     AL3D_REQUIRE(!gap || gap_parts >= al3d_gap_parts_count(p.OH, p.OW, deconv),
                  "%s: gap_parts must be at least al3d_gap_parts_count(OH, OW, %d)", name, (int)deconv);
-    p.tiles_x = (int)al3d_cdiv(deconv ? W : p.OW, fam.tw);
-    p.tiles_y = (int)al3d_cdiv(deconv ? H : p.OH, fam.th);
     p.ntiles = p.tiles_x * p.tiles_y * B; p.nblocks = (int)al3d_cdiv(Cout, F3_BN);
     launch(p, deconv ? dim3(f3_grid(p), 1, 4) : dim3(f3_grid(p)));
     AL3D_CHECK_LAUNCH(kernel);
@@ -1498,11 +1349,9 @@ __global__ __launch_bounds__(256, NS <= 3 ? 3 : 2) void conv2d_f16x3_dma_kernel(
     const int wm = wave & 1, wn = wave >> 1;
     int tile, nblk;
     if (!f3_tile_of_block(p.ntiles, p.nblocks, p.xmap, tile, nblk)) return;     // padding block of the last group (uniform)
-    const int tx_ = tile % p.tiles_x; tile /= p.tiles_x;
-    const int ty_ = tile % p.tiles_y; tile /= p.tiles_y;
-    const int b = tile;
+    int tx_, ty_, b;
+    conv_tile_decode(tile, p.tiles_x, p.tiles_y, tx_, ty_, b);
     const int n0 = nblk * F3_BN;
-    const int MH = MODE == 0 ? p.OH : p.H, MW = MODE == 0 ? p.OW : p.W;
     const int taps = MODE == 0 ? p.ksize * p.ksize : 1;
     const int tap0 = MODE == 0 ? 0 : blockIdx.z;
     const int wtaps = MODE == 0 ? taps : 4;
@@ -1530,9 +1379,7 @@ __global__ __launch_bounds__(256, NS <= 3 ? 3 : 2) void conv2d_f16x3_dma_kernel(
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             int iy, ix;
-            if (MODE == 0) { iy = py[i] * p.stride - p.pad + ky; ix = px[i] * p.stride - p.pad + kx; }
-            else { iy = py[i]; ix = px[i]; }
-            const bool ok = py[i] < MH && px[i] < MW && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
+            const bool ok = conv_tap_pixel<MODE>(p, py[i], px[i], ky, kx, iy, ix);
             // 32-bit element index (the entry checks B*H*W*Cin < 2^31): keeps the select a pair of v_cndmask, no branch
             const unsigned idx = (unsigned)(((b * p.H + iy) * p.W + ix) * p.Cin + lchunk * F3_BK + cg[i]);
             const float* src = ok ? p.in + idx : g_dma_zero + cg[i];
@@ -1548,12 +1395,7 @@ __global__ __launch_bounds__(256, NS <= 3 ? 3 : 2) void conv2d_f16x3_dma_kernel(
     };
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    conv_acc_clear(acc);
 
     const int fr = lane & 31, fh = lane >> 5;
     const F3RingOffs off = f3_ring_offsets(wm, wn, fr, fh);            // fragment side
@@ -1581,36 +1423,8 @@ __global__ __launch_bounds__(256, NS <= 3 ? 3 : 2) void conv2d_f16x3_dma_kernel(
     }
     f3_wait_vm<0>();                                   // the tail's dummy requests must not outlive the workgroup's LDS
 
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int n = n0 + wn * 64 + j * 32 + fr;
-        if (n >= p.Cout) continue;
-        const float sc = p.scale[n];
-        const float sh = p.shift ? p.shift[n] : 0.0f;
-        float gsum = 0.f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = wm * 64 + i * 32 + f3_crow(r, fh);
-                const int y = ty_ * F3_TH + m / F3_TW, x = tx_ * F3_TW + m % F3_TW;
-                if (y >= MH || x >= MW) continue;
-                float v = acc[i][j][r] * sc + sh;
-                if (p.relu) v = v <= 0.f ? 0.f : v;                   // NaN propagates, like torch.relu
-                int oy = y, ox = x;
-                if (MODE == 1) { oy = 2 * y + (tap0 >> 1); ox = 2 * x + (tap0 & 1); }
-                p.out[(((int64_t)b * p.OH + oy) * p.OW + ox) * p.ldc + p.coff + n] = v;
-                gsum += v;
-            }
-        }
-        if (p.gap) {                                                  // as conv2d_f16x3_kernel
-            gsum += __shfl_xor(gsum, 32);
-            if (fh == 0) {
-                const int part = (((ty_ * p.tiles_x + tx_) * (MODE == 1 ? 4 : 1) + tap0) << 1) + wm;
-                p.gap[((int64_t)b * p.gap_parts + part) * p.ldc + p.coff + n] = gsum;
-            }
-        }
-    }
+    // same tiles and partials as conv2d_f16x3_kernel
+    conv_store_patch<MODE, F3_TH, F3_TW, 2, 2, false, true>(p, acc, b, ty_, tx_, wm, n0 + wn * 64, tap0, lane, p.gap, p.gap_parts);
 }
 
 // Software-pipelined form of the kernel above (the default): the loop is f3_ring_gemm (al3d_f16x3.h), all NS stages in
@@ -1624,11 +1438,9 @@ __global__ __launch_bounds__(256, 2) void conv2d_f16x3_dma2_kernel(ConvF3Params 
     const int wm = wave & 1, wn = wave >> 1;
     int tile, nblk;
     if (!f3_tile_of_block(p.ntiles, p.nblocks, p.xmap, tile, nblk)) return;     // padding block of the last group (uniform)
-    const int tx_ = tile % p.tiles_x; tile /= p.tiles_x;
-    const int ty_ = tile % p.tiles_y; tile /= p.tiles_y;
-    const int b = tile;
+    int tx_, ty_, b;
+    conv_tile_decode(tile, p.tiles_x, p.tiles_y, tx_, ty_, b);
     const int n0 = nblk * F3_BN;
-    const int MH = MODE == 0 ? p.OH : p.H, MW = MODE == 0 ? p.OW : p.W;
     const int taps = MODE == 0 ? p.ksize * p.ksize : 1;
     const int tap0 = MODE == 0 ? 0 : blockIdx.z;
     const int wtaps = MODE == 0 ? taps : 4;
@@ -1658,9 +1470,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_f16x3_dma2_kernel(ConvF3Params 
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 int iy, ix;
-                if (MODE == 0) { iy = py[i] * p.stride - p.pad + ky; ix = px[i] * p.stride - p.pad + kx; }
-                else { iy = py[i]; ix = px[i]; }
-                const bool ok = py[i] < MH && px[i] < MW && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
+                const bool ok = conv_tap_pixel<MODE>(p, py[i], px[i], ky, kx, iy, ix);
                 // 32-bit element index (the entry checks B*H*W*Cin < 2^31)
                 const unsigned idx = (unsigned)(((b * p.H + iy) * p.W + ix) * p.Cin + cg[i]);
                 abase[i] = reinterpret_cast<const char*>(ok ? p.in + idx : g_dma_zero + cg[i]);
@@ -1688,8 +1498,10 @@ __global__ __launch_bounds__(256, 2) void conv2d_f16x3_dma2_kernel(ConvF3Params 
     f3_ring_gemm<NS, (IO & SP_IO_IN_PAIR) != 0, f3_split>(smem_base, total, wm, wn, lane, issue, c00, c01, c10, c11);
     const int fr = lane & 31, fh = lane >> 5;
 
-    const f32x16* accp[2][2] = {{&c00, &c01}, {&c10, &c11}};
     if constexpr ((IO & 4) == 0) {
+        const f32x16* accp[2][2] = {{&c00, &c01}, {&c10, &c11}};
+        const int MH = MODE == 0 ? p.OH : p.H, MW = MODE == 0 ? p.OW : p.W;
+        // Private to this kernel: the transposition goes through the stage ring, the GAP sums are taken before the store test.
         // BN / ReLU / GAP sums in the C layout, then each 32-pixel x 64-channel half of the wave's tile goes through a
         // wave-private LDS scratch (the stage ring, free after the barrier) so that a lane holds consecutive channels of
         // a pixel and stores 16-byte pieces (IO & 4: the untransposed dword stores below, for layouts that are not
@@ -1769,37 +1581,8 @@ __global__ __launch_bounds__(256, 2) void conv2d_f16x3_dma2_kernel(ConvF3Params 
         }
         return;
     }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int n = n0 + wn * 64 + j * 32 + fr;
-        if (n >= p.Cout) continue;
-        const float sc = p.scale[n];
-        const float sh = p.shift ? p.shift[n] : 0.0f;
-        float gsum = 0.f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const f32x16& acc = *accp[i][j];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = wm * 64 + i * 32 + f3_crow(r, fh);
-                const int y = ty_ * F3_TH + m / F3_TW, x = tx_ * F3_TW + m % F3_TW;
-                if (y >= MH || x >= MW) continue;
-                float v = acc[r] * sc + sh;
-                if (p.relu) v = v <= 0.f ? 0.f : v;                   // NaN propagates, like torch.relu
-                int oy = y, ox = x;
-                if (MODE == 1) { oy = 2 * y + (tap0 >> 1); ox = 2 * x + (tap0 & 1); }
-                p.out[(((int64_t)b * p.OH + oy) * p.OW + ox) * p.ldc + p.coff + n] = v;
-                gsum += v;
-            }
-        }
-        if (p.gap) {                                                  // as conv2d_f16x3_kernel
-            gsum += __shfl_xor(gsum, 32);
-            if (fh == 0) {
-                const int part = (((ty_ * p.tiles_x + tx_) * (MODE == 1 ? 4 : 1) + tap0) << 1) + wm;
-                p.gap[((int64_t)b * p.gap_parts + part) * p.ldc + p.coff + n] = gsum;
-            }
-        }
-    }
+    const f32x16 acc[2][2] = {{c00, c01}, {c10, c11}};
+    conv_store_patch<MODE, F3_TH, F3_TW, 2, 2, false, true>(p, acc, b, ty_, tx_, wm, n0 + wn * 64, tap0, lane, p.gap, p.gap_parts);
 }
 
 // planes [2][Cout][taps][Cin] -> [ceil(Cout/128)][taps][Cin/16][2 planes][128 rows][2 chunks of 8 f16]; chunk c of

@@ -14,7 +14,9 @@
 // workgroup; 4 waves as 2x2, each wave 64x64 = 2x2 MFMA tiles (64 accumulator
 // VGPRs); K-chunks of 32 channels per tap, register-staged into double-buffered
 // LDS tiles padded to 36 floats per row (conflict-free ds_read_b128 fragments).
+// The pixel-tile side (parameter block, tile decode, input pixel, epilogue, entry-point checks) is conv2d_tile.h's.
 #include "al3d_common.h"
+#include "conv2d_tile.h"
 
 #define CV_BM 128
 #define CV_BN 128
@@ -23,18 +25,8 @@
 #define CV_TH 8
 #define CV_TW 16
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-struct ConvParams {
-    const float* in;      // [B, H, W, Cin]
+struct ConvParams : ConvGeom {
     const float* wgt;     // [Cout, taps, Cin]
-    const float* scale;   // [Cout] or null (=1)
-    const float* shift;   // [Cout] or null (=0)
-    float* out;           // [B, OH, OW, ldc] written at channel offset coff
-    int B, H, W, Cin, Cout, OH, OW, ldc, coff;
-    int ksize, stride, pad;  // conv mode
-    int relu;
-    int tiles_x, tiles_y;    // 8x16 patches per image (over the GEMM-M pixel grid)
 };
 
 // MODE 0: convolution (ksize x ksize, stride, pad).  MODE 1: ConvTranspose2d 2x2 stride 2
@@ -48,12 +40,9 @@ __global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(ConvParams p)
     const int wm = wave & 1, wn = wave >> 1;
 
     // which pixel patch / image
-    int tile = blockIdx.x;
-    const int tx_ = tile % p.tiles_x; tile /= p.tiles_x;
-    const int ty_ = tile % p.tiles_y; tile /= p.tiles_y;
-    const int b = tile;
+    int tx_, ty_, b;
+    conv_tile_decode(blockIdx.x, p.tiles_x, p.tiles_y, tx_, ty_, b);
     const int n0 = blockIdx.y * CV_BN;
-    const int MH = MODE == 0 ? p.OH : p.H, MW = MODE == 0 ? p.OW : p.W;  // GEMM-M pixel grid
     const int taps = MODE == 0 ? p.ksize * p.ksize : 1;
     const int tap0 = MODE == 0 ? 0 : blockIdx.z;  // deconv: fixed weight tap per launch slice
 
@@ -76,12 +65,8 @@ __global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(ConvParams p)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             int iy, ix;
-            if (MODE == 0) { iy = py[i] * p.stride - p.pad + ky; ix = px[i] * p.stride - p.pad + kx; }
-            else { iy = py[i]; ix = px[i]; }
-            const bool ok = py[i] < MH && px[i] < MW && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-            ra[i] = ok ? *reinterpret_cast<const float4*>(
-                             p.in + (((int64_t)b * p.H + iy) * p.W + ix) * p.Cin + c0 + 4 * sq)
-                       : make_float4(0.f, 0.f, 0.f, 0.f);
+            const bool ok = conv_tap_pixel<MODE>(p, py[i], px[i], ky, kx, iy, ix);
+            ra[i] = conv_load4(p, ok, b, iy, ix, c0 + 4 * sq);
             const int n = n0 + sr + 32 * i;
             rb[i] = n < p.Cout ? *reinterpret_cast<const float4*>(
                                      p.wgt + ((int64_t)n * (MODE == 0 ? taps : 4) + tap0 + tap) * p.Cin +
@@ -99,12 +84,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(ConvParams p)
     };
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    conv_acc_clear(acc);
 
     load_step(0);
     store_step(0);
@@ -135,41 +115,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(ConvParams p)
         __syncthreads();
     }
 
-    // epilogue: scale/shift (+ReLU), NHWC store.  C/D map: col = lane&31,
-    // row = (r&3) + 8*(r>>2) + 4*(lane>>5).
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int n = n0 + wn * 64 + j * 32 + fr;
-        if (n >= p.Cout) continue;
-        const float sc = p.scale ? p.scale[n] : 1.0f;
-        const float sh = p.shift ? p.shift[n] : 0.0f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-                const int y = ty_ * CV_TH + m / CV_TW, x = tx_ * CV_TW + m % CV_TW;
-                if (y >= MH || x >= MW) continue;
-                float v = acc[i][j][r] * sc + sh;
-                if (p.relu) v = v <= 0.f ? 0.f : v;                   // NaN propagates, like torch.relu
-                int oy = y, ox = x;
-                if (MODE == 1) { oy = 2 * y + (tap0 >> 1); ox = 2 * x + (tap0 & 1); }
-                p.out[(((int64_t)b * p.OH + oy) * p.OW + ox) * p.ldc + p.coff + n] = v;
-            }
-        }
-    }
-}
-
-static int conv_check(const ConvParams& p, const char* name)
-{
-    AL3D_REQUIRE(p.in && p.wgt && p.out, "%s: null pointer", name);
-    AL3D_REQUIRE(p.B >= 1 && p.H >= 1 && p.W >= 1 && p.Cin >= 1 && p.Cout >= 1, "%s: bad shape", name);
-    AL3D_REQUIRE(p.Cin % CV_BK == 0, "%s: Cin=%d must be a multiple of %d", name, p.Cin, CV_BK);
-    AL3D_REQUIRE(p.coff >= 0 && p.coff + p.Cout <= p.ldc, "%s: channel window [%d,%d) exceeds ldc=%d",
-                 name, p.coff, p.coff + p.Cout, p.ldc);
-    AL3D_REQUIRE(((uintptr_t)p.in & 15) == 0 && ((uintptr_t)p.wgt & 15) == 0,
-                 "%s: in/wgt must be 16-byte aligned", name);
-    return AL3D_OK;
+    conv_store_patch<MODE, CV_TH, CV_TW, 2, 2, true, false>(p, acc, b, ty_, tx_, wm, n0 + wn * 64, tap0, lane);
 }
 
 extern "C" int al3d_conv2d_nhwc_f32(const float* in, const float* wgt, const float* scale,
@@ -178,17 +124,10 @@ extern "C" int al3d_conv2d_nhwc_f32(const float* in, const float* wgt, const flo
                                     int relu, void* stream)
 {
     ConvParams p;
-    p.in = in; p.wgt = wgt; p.scale = scale; p.shift = shift; p.out = out;
-    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
-    p.ksize = ksize; p.stride = stride; p.pad = pad; p.ldc = ldc; p.coff = coff; p.relu = relu;
-    AL3D_REQUIRE(ksize >= 1 && ksize <= 7 && stride >= 1 && pad >= 0, "al3d_conv2d_nhwc_f32: bad geometry");
-    p.OH = (H + 2 * pad - ksize) / stride + 1;
-    p.OW = (W + 2 * pad - ksize) / stride + 1;
-    AL3D_REQUIRE(p.OH >= 1 && p.OW >= 1, "al3d_conv2d_nhwc_f32: empty output");
-    int rc = conv_check(p, "al3d_conv2d_nhwc_f32");
+    p.wgt = wgt;
+    int rc = conv_geom_build(p, "al3d_conv2d_nhwc_f32", false, CV_TH, CV_TW, CV_BK, false, in, wgt, scale, shift, out, B, H, W,
+                             Cin, Cout, ksize, stride, pad, ldc, coff, relu);
     if (rc) return rc;
-    p.tiles_x = (int)al3d_cdiv(p.OW, CV_TW);
-    p.tiles_y = (int)al3d_cdiv(p.OH, CV_TH);
     dim3 grid((unsigned)(p.tiles_x * p.tiles_y * B), (unsigned)al3d_cdiv(Cout, CV_BN), 1);
     hipLaunchKernelGGL(conv2d_mfma_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, p);
     AL3D_CHECK_LAUNCH("conv2d_mfma_kernel<conv>");
@@ -200,14 +139,10 @@ extern "C" int al3d_deconv2x2_nhwc_f32(const float* in, const float* wgt, const 
                                        int Cout, int ldc, int coff, int relu, void* stream)
 {
     ConvParams p;
-    p.in = in; p.wgt = wgt; p.scale = scale; p.shift = shift; p.out = out;
-    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
-    p.ksize = 2; p.stride = 2; p.pad = 0; p.ldc = ldc; p.coff = coff; p.relu = relu;
-    p.OH = 2 * H; p.OW = 2 * W;
-    int rc = conv_check(p, "al3d_deconv2x2_nhwc_f32");
+    p.wgt = wgt;
+    int rc = conv_geom_build(p, "al3d_deconv2x2_nhwc_f32", true, CV_TH, CV_TW, CV_BK, false, in, wgt, scale, shift, out, B, H, W,
+                             Cin, Cout, 2, 2, 0, ldc, coff, relu);
     if (rc) return rc;
-    p.tiles_x = (int)al3d_cdiv(W, CV_TW);
-    p.tiles_y = (int)al3d_cdiv(H, CV_TH);
     dim3 grid((unsigned)(p.tiles_x * p.tiles_y * B), (unsigned)al3d_cdiv(Cout, CV_BN), 4);
     hipLaunchKernelGGL(conv2d_mfma_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, p);
     AL3D_CHECK_LAUNCH("conv2d_mfma_kernel<deconv>");
@@ -254,16 +189,11 @@ __global__ __launch_bounds__(256) void gap_rows_vec4_kernel(const float* __restr
     reinterpret_cast<float4*>(rowmean + by * C)[lane] = make_float4(s.x / w, s.y / w, s.z / w, s.w / w);
 }
 
-// stage 2: out[b][c] = (sum_y rowmean[b][y][c]) / H, top to bottom
+// stage 2: out[b][c] = (sum_y rowmean[b][y][c]) / H, top to bottom (64-thread blocks: more of them in flight)
 __global__ __launch_bounds__(64) void gap_cols_kernel(const float* __restrict__ rowmean, int H, int C,
                                                        float* __restrict__ out)
 {
-    const int b = blockIdx.y, c = blockIdx.x * blockDim.x + threadIdx.x;   // 64-thread blocks: more of them in flight
-    if (c >= C) return;
-    float s = 0.f;
-#pragma unroll 16
-    for (int y = 0; y < H; ++y) s += rowmean[((int64_t)b * H + y) * C + c];   // loads run ahead, adds stay in order
-    out[(int64_t)b * C + c] = s / (float)H;
+    gap_cols_reduce(rowmean, H, C, (float)H, out);
 }
 
 extern "C" int64_t al3d_gap_workspace_bytes(int B, int H, int C) { return (int64_t)B * H * C * 4; }

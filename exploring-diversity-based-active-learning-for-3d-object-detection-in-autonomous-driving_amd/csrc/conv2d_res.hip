@@ -21,19 +21,15 @@
 // each operation rounded to f32 on its own (the file is built without contraction).
 #include "al3d_common.h"
 #include "al3d_f16x3.h"
+#include "conv2d_tile.h"
 
 #define R3_TH 4
 #define R3_TW 8
 
-struct ConvResParams {
-    const float* in;        // [B, H, W, Cin] f32
+struct ConvResParams : ConvGeom {         // 3x3 / s1 / p1: OH, OW = H, W; 4 x 8 pixel tiles; scale required
     const char* wgt;        // al3d_pack_f16x3_dma image: [ceil(Cout/128)][9][Cin/16] stages of 8 KB
-    const float* scale;
-    const float* shift;     // may be null
     const float* res;       // [B, H, W, ldr] f32
-    float* out;             // [B, H, W, ldc], written at coff
-    int B, H, W, Cin, Cout, ldr, ldc, coff, relu;
-    int tiles_x, tiles_y, ngroups;
+    int ldr, ngroups;
 };
 
 __device__ __attribute__((aligned(32))) float g_res_zero[8];       // stays zero: source of out-of-image pixels
@@ -45,10 +41,8 @@ __global__ __launch_bounds__(256) void conv3x3_res_f16x3_kernel(ConvResParams p)
     const int group = blockIdx.y * 4 + wave;              // this wave's NB channel tiles
     if (group >= p.ngroups) return;                       // wave-uniform; the kernel has no barrier
     const int fr = lane & 31, fh = lane >> 5;
-    int tile = blockIdx.x;
-    const int tx_ = tile % p.tiles_x; tile /= p.tiles_x;
-    const int ty_ = tile % p.tiles_y; tile /= p.tiles_y;
-    const int b = tile;
+    int tx_, ty_, b;
+    conv_tile_decode(blockIdx.x, p.tiles_x, p.tiles_y, tx_, ty_, b);
     const int py = ty_ * R3_TH + (fr >> 3), px = tx_ * R3_TW + (fr & 7);
     const bool live = py < p.H && px < p.W;
     const int kchunks = p.Cin >> 4;
@@ -66,7 +60,7 @@ __global__ __launch_bounds__(256) void conv3x3_res_f16x3_kernel(ConvResParams p)
     int ltap = 0, lchunk = 0;                             // cursor of the next step to request
     const float* arow = g_res_zero;
     bool aok = false;
-    auto set_tap = [&](int tap) {
+    auto set_tap = [&](int tap) {                         // (its own pixel test: stride and pad are constants here, not p's)
         const int ky = tap / 3, kx = tap - 3 * ky;
         const int iy = py + ky - 1, ix = px + kx - 1;
         aok = live && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
@@ -85,11 +79,8 @@ __global__ __launch_bounds__(256) void conv3x3_res_f16x3_kernel(ConvResParams p)
         if (++lchunk == kchunks) { lchunk = 0; if (++ltap < 9) set_tap(ltap); }
     };
 
-    f32x16 acc[NB];
-#pragma unroll
-    for (int j = 0; j < NB; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+    f32x16 acc[1][NB];
+    conv_acc_clear(acc);
 
     float4 a_cur[2], a_nxt[2];
     f16x8 wh_cur[NB], wl_cur[NB], wh_nxt[NB], wl_nxt[NB];
@@ -100,13 +91,14 @@ __global__ __launch_bounds__(256) void conv3x3_res_f16x3_kernel(ConvResParams p)
         f16x8 ah, al;
         f3_split8(a_cur[0], a_cur[1], ah, al);
 #pragma unroll
-        for (int j = 0; j < NB; ++j) f3_mac3(ah, al, wh_cur[j], wl_cur[j], f3_lift_down(wh_cur[j]), acc[j]);
+        for (int j = 0; j < NB; ++j) f3_mac3(ah, al, wh_cur[j], wl_cur[j], f3_lift_down(wh_cur[j]), acc[0][j]);
         a_cur[0] = a_nxt[0]; a_cur[1] = a_nxt[1];
 #pragma unroll
         for (int j = 0; j < NB; ++j) { wh_cur[j] = wh_nxt[j]; wl_cur[j] = wl_nxt[j]; }
     }
 
-    // C layout of the 32 x 32 product: lane column fr = channel, register r = pixel (r & 3) + 8 (r >> 2) + 4 fh
+    // C layout of the 32 x 32 product: lane column fr = channel, register r = pixel (r & 3) + 8 (r >> 2) + 4 fh.  Private to
+    // this kernel: the residual is added between the affine and the ReLU
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
         const int n = n_base + 32 * j + fr;
@@ -118,7 +110,7 @@ __global__ __launch_bounds__(256) void conv3x3_res_f16x3_kernel(ConvResParams p)
             const int y = ty_ * R3_TH + (m >> 3), x = tx_ * R3_TW + (m & 7);
             if (y >= p.H || x >= p.W) continue;
             const int64_t pix = ((int64_t)b * p.H + y) * p.W + x;
-            float v = acc[j][r] * sc + sh;
+            float v = acc[0][j][r] * sc + sh;
             v = v + p.res[pix * p.ldr + n];
             if (p.relu) v = v <= 0.f ? 0.f : v;                             // NaN propagates, like torch.relu
             p.out[pix * p.ldc + p.coff + n] = v;
@@ -131,19 +123,14 @@ extern "C" int al3d_conv3x3_res_nhwc_f16x3(const float* in, const void* wgt_imag
                                            int ldc, int coff, int relu, void* stream)
 {
     const char* name = "al3d_conv3x3_res_nhwc_f16x3";
-    AL3D_REQUIRE(in && wgt_image && out && scale, "%s: null pointer (scale carries the weight exponent and is required)", name);
+    ConvResParams p;
+    p.wgt = (const char*)wgt_image; p.res = res; p.ldr = ldr;
+    conv_geom_set(p, false, R3_TH, R3_TW, in, scale, shift, out, B, H, W, Cin, Cout, 3, 1, 1, ldc, coff, relu);
+    int rc = conv_geom_check(p, wgt_image, name, 16, true);
+    if (rc) return rc;
     AL3D_REQUIRE(res, "%s: null residual (the plain convolution is al3d_conv2d_nhwc_f16x3_dma)", name);
-    AL3D_REQUIRE(B >= 1 && H >= 1 && W >= 1 && Cin >= 1 && Cout >= 1, "%s: bad shape", name);
-    AL3D_REQUIRE(Cin % 16 == 0, "%s: Cin=%d must be a multiple of 16", name, Cin);
     AL3D_REQUIRE(Cout % 32 == 0, "%s: Cout=%d must be a multiple of 32", name, Cout);
     AL3D_REQUIRE(ldr >= Cout, "%s: residual row stride ldr=%d is below Cout=%d", name, ldr, Cout);
-    AL3D_REQUIRE(coff >= 0 && coff + Cout <= ldc, "%s: channel window [%d,%d) exceeds ldc=%d", name, coff, coff + Cout, ldc);
-    AL3D_REQUIRE(((uintptr_t)in & 15) == 0 && ((uintptr_t)wgt_image & 15) == 0, "%s: in/wgt must be 16-byte aligned", name);
-    ConvResParams p;
-    p.in = in; p.wgt = (const char*)wgt_image; p.scale = scale; p.shift = shift; p.res = res; p.out = out;
-    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.ldr = ldr; p.ldc = ldc; p.coff = coff; p.relu = relu;
-    p.tiles_x = (int)al3d_cdiv(W, R3_TW);
-    p.tiles_y = (int)al3d_cdiv(H, R3_TH);
     const int64_t ntiles = (int64_t)p.tiles_x * p.tiles_y * B;
     AL3D_REQUIRE(ntiles < ((int64_t)1 << 31), "%s: map above 2^31 pixel tiles", name);
     // two channel tiles per wave once that still leaves every SIMD of 256 CUs two waves

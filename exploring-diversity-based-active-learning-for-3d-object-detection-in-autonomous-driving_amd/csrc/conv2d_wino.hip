@@ -25,6 +25,7 @@
 // stays opt-in (AL3D_DENSE=wino).  gfx950 only.
 #include "al3d_common.h"
 #include "sp_rows.h"
+#include "conv2d_tile.h"
 #include <type_traits>
 
 #define WN_IC(v) std::integral_constant<int, v>{}
@@ -35,14 +36,9 @@
 #define WN_NS 3
 #define WN_XP 36                        // floats per (row a, j, tile) line of the output exchange: 32 channels + pad
 
-struct WinoParams {
-    const float* in;        // [B, H, W, Cin] f32
+struct WinoParams : ConvGeom {            // 3x3 / s1 / p1: OH, OW = H, W; 16 x 16 pixel tiles; scale = BN scale * 2^-s, required
     const _Float16* wgt;    // [2 planes][Cout/32][Cin/16][16 positions][64 lanes][8] f16 (al3d_pack_f16x3_wino)
-    const float* scale;     // BN scale * 2^-s
-    const float* shift;
-    float* out;             // [B, H, W, ldc]
-    int B, H, W, Cin, Cout, ldc, coff, relu;
-    int tiles_x, tiles_y, ntiles, nblocks;
+    int ntiles, nblocks;
 };
 
 __device__ __attribute__((aligned(64))) float g_wn_zero[16];
@@ -60,9 +56,8 @@ __global__ __launch_bounds__(256, 1) void conv3x3_f16x3_wino_kernel(WinoParams p
     const int fr = lane & 31, fh = lane >> 5;
     int tile, nblk;
     if (!f3_tile_of_block(p.ntiles, p.nblocks, false, tile, nblk)) return;
-    const int tx_ = tile % p.tiles_x; tile /= p.tiles_x;
-    const int ty_ = tile % p.tiles_y; tile /= p.tiles_y;
-    const int b = tile;
+    int tx_, ty_, b;
+    conv_tile_decode(tile, p.tiles_x, p.tiles_y, tx_, ty_, b);
     const int n0 = nblk * 64;
     const int y0 = ty_ * WN_T - 1, x0 = tx_ * WN_T - 1;
     const int nchunks = p.Cin >> 4;
@@ -75,11 +70,10 @@ __global__ __launch_bounds__(256, 1) void conv3x3_f16x3_wino_kernel(WinoParams p
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
         const int hp = 16 * (6 * wave + k) + (lane >> 2);
-        const int row = hp / WN_HW, col = hp - row * WN_HW;
-        const int iy = y0 + row, ix = x0 + col;
-        const int q = (lane & 3) ^ wn_swz(col);
-        const bool ok = hp < WN_HP && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-        hsrc[k] = reinterpret_cast<const char*>(ok ? p.in + (((int64_t)b * p.H + iy) * p.W + ix) * p.Cin + 4 * q : g_wn_zero + 4 * q);
+        int iy, ix;
+        const bool ok = conv_halo_pixel<WN_HW>(p, y0, x0, hp, hp < WN_HP, iy, ix);
+        const int q = (lane & 3) ^ wn_swz(ix - x0);
+        hsrc[k] = reinterpret_cast<const char*>(ok ? conv_in_ptr(p, b, iy, ix, 4 * q) : g_wn_zero + 4 * q);
         hinc[k] = ok ? 64u : 0u;
     }
     auto issue_halo = [&](int chunk) {
@@ -142,13 +136,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_f16x3_wino_kernel(WinoParams p
 
     f32x16 acc[4][2][2];                              // [position in the row][m tile][n tile]
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[q][i][j][r] = 0.f;
+    for (int q = 0; q < 4; ++q) conv_acc_clear(acc[q]);
 
     // The patch rows of a tile are read and transformed in two halves (the fragment's two 16-byte pieces = channels
     // 8 h .. 8 h + 3 and 8 h + 4 .. 8 h + 7): eight 16-byte reads and 32 live registers at a time instead of sixteen / 64.
@@ -245,7 +233,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_f16x3_wino_kernel(WinoParams p
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the tail's dummy requests must not outlive the workgroup's LDS
 
-    // ---- output transform.  Wave w holds row a = w of M (positions (w, 0..3)):  P_w[j] = sum_c M[w][c] A^T[j][c]
+    // ---- output transform (private to this kernel: no fragment is an output pixel before the exchange).  Wave w holds row a = w of M (positions (w, 0..3)):  P_w[j] = sum_c M[w][c] A^T[j][c]
     // in registers (A^T = [[1,1,1,0],[0,1,-1,-1]]), then Y[i][j] = sum_a A^T[i][a] P_a[j] across the waves through LDS,
     // one 32-channel half at a time: X[a][j][tile][32 + pad] floats = 72 KB in the halo ring's storage.
     if constexpr (ABL == 4 || ABL == 5) {                // dev ablation: no output transform / stores (one word keeps the products alive)
@@ -365,10 +353,9 @@ extern "C" int al3d_conv3x3_nhwc_f16x3_wino(const float* in, const void* wgt_win
     AL3D_REQUIRE(coff >= 0 && coff + Cout <= ldc && ldc % 8 == 0 && coff % 8 == 0, "al3d_conv3x3_nhwc_f16x3_wino: channel window");
     AL3D_REQUIRE((((uintptr_t)in | (uintptr_t)wgt_wino | (uintptr_t)out | (uintptr_t)scale | (uintptr_t)shift) & 15) == 0,
                  "al3d_conv3x3_nhwc_f16x3_wino: pointers must be 16-byte aligned");
-    WinoParams p;
-    p.in = in; p.wgt = (const _Float16*)wgt_wino; p.scale = scale; p.shift = shift; p.out = out;
-    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.ldc = ldc; p.coff = coff; p.relu = relu;
-    p.tiles_x = (int)al3d_cdiv(W, WN_T); p.tiles_y = (int)al3d_cdiv(H, WN_T);
+    WinoParams p;                                      // (this entry point's requirements and their texts are its own)
+    p.wgt = (const _Float16*)wgt_wino;
+    conv_geom_set(p, false, WN_T, WN_T, in, scale, shift, out, B, H, W, Cin, Cout, 3, 1, 1, ldc, coff, relu);
     p.ntiles = p.tiles_x * p.tiles_y * B; p.nblocks = Cout / 64;
     const dim3 grid((unsigned)(al3d_cdiv(p.ntiles, 8) * 8 * p.nblocks));
 #ifdef AL3D_WINO_ABLATE

@@ -7,8 +7,8 @@ the tree (not under gpurun_out/, which does not travel), then on the box:
 
     python tools/ab_so.py ab_tmp/lib_a.so ab_tmp/lib_b.so -- python tools/bench_splayers.py 32 al3d_sp_conv_wave2_bf16x6
 
-Each library is copied over csrc/libal3d_hip.so in turn (a, b, a, b) and the command is run as a
-child process; the last lines of its output are printed next to the variant name.  The first child that
+Each library is copied over csrc/libal3d_hip.so in turn (a, b, a, b; AB_ROUNDS=3 for a third round) and the command is
+run as a child process; the last lines of its output are printed next to the variant name.  The first child that
 fails ends the run (exit status = the child's).
 """
 import os
@@ -29,7 +29,7 @@ def main():
     keep = target + ".ab_keep"
     shutil.copy2(target, keep)
     try:
-        for rnd in range(2):
+        for rnd in range(int(os.environ.get("AB_ROUNDS", "2"))):
             for lib in libs:
                 shutil.copy2(lib, target)
                 out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True)
