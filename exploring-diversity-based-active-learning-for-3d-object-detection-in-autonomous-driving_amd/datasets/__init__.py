@@ -1,4 +1,5 @@
-from .anchors import create_anchors_3d_range, generate_task_anchors
+from .anchors import AnchorGeneratorRange, create_anchors_3d_range, generate_task_anchors
+from .target_assigner import NearestIouSimilarity, TargetAssigner
 from .pool import PoolFrames, DeviceSweepLoader, CameraLidarSweepLoader
 from .file_loader import FileSweepLoader, SweepFileReader
 from .camera_files import CameraLidarFileLoader, ImageAugTest
@@ -6,6 +7,6 @@ from .pipelines import (PIPELINES, Compose, LoadPointCloudFromFile, LoadPointClo
                         Voxelization, AssignTarget, Reformat, SweepDataset, collate_device)
 from .create_gt_database import create_groundtruth_database, SweepPointsLoader, GtDatabaseWriter
 
-__all__ = ["create_groundtruth_database", "SweepPointsLoader", "GtDatabaseWriter", "create_anchors_3d_range", "generate_task_anchors", "PoolFrames", "DeviceSweepLoader", "CameraLidarSweepLoader", "FileSweepLoader", "SweepFileReader", "CameraLidarFileLoader", "ImageAugTest", "PIPELINES",
+__all__ = ["AnchorGeneratorRange", "NearestIouSimilarity", "TargetAssigner", "create_groundtruth_database", "SweepPointsLoader", "GtDatabaseWriter", "create_anchors_3d_range", "generate_task_anchors", "PoolFrames", "DeviceSweepLoader", "CameraLidarSweepLoader", "FileSweepLoader", "SweepFileReader", "CameraLidarFileLoader", "ImageAugTest", "PIPELINES",
            "Compose", "LoadPointCloudFromFile", "LoadPointCloudAnnotations", "Preprocess", "Voxelization",
            "AssignTarget", "Reformat", "SweepDataset", "collate_device"]

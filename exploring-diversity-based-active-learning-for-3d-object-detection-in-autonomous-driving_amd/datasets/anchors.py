@@ -52,3 +52,37 @@ def generate_task_anchors(tasks, anchor_generators, feature_map_size):
         a = np.concatenate(per_cls, axis=-2)
         out.append(np.ascontiguousarray(a.reshape(-1, a.shape[-1])))
     return out
+
+
+class AnchorGeneratorRange:
+    """det3d/core/anchor/anchor_generator.py:64-118: one class's anchors over a range, with its two thresholds."""
+
+    def __init__(self, anchor_ranges, sizes=(1.6, 3.9, 1.56), rotations=(0, np.pi / 2), velocities=(0, 0), class_name=None,
+                 match_threshold=-1, unmatch_threshold=-1, dtype=np.float32):
+        self._anchor_ranges, self._sizes, self._rotations, self._velocities = anchor_ranges, sizes, rotations, velocities
+        self._class_name, self._match_threshold, self._unmatch_threshold = class_name, match_threshold, unmatch_threshold
+        self._dtype = dtype
+
+    class_name = property(lambda self: self._class_name)
+    match_threshold = property(lambda self: self._match_threshold)
+    unmatch_threshold = property(lambda self: self._unmatch_threshold)
+
+    @property
+    def num_anchors_per_localization(self):
+        return len(self._rotations) * np.array(self._sizes).reshape([-1, 3]).shape[0]
+
+    def generate(self, feature_map_size):
+        return create_anchors_3d_range(feature_map_size, self._anchor_ranges, self._sizes, self._rotations, self._velocities,
+                                       self._dtype)
+
+
+def build_anchor_generator(cfg):
+    """det3d/builder.py's ``anchor_generator_range`` branch: a config dict -> ``AnchorGeneratorRange``."""
+    if isinstance(cfg, AnchorGeneratorRange):
+        return cfg
+    if cfg.get("type", "anchor_generator_range") != "anchor_generator_range":
+        raise NotImplementedError(f"anchor generator {cfg.get('type')!r}: only anchor_generator_range is built")
+    return AnchorGeneratorRange(anchor_ranges=list(cfg["anchor_ranges"]), sizes=list(cfg["sizes"]),
+                                rotations=list(cfg["rotations"]), velocities=cfg.get("velocities"),
+                                class_name=cfg["class_name"], match_threshold=cfg["matched_threshold"],
+                                unmatch_threshold=cfg["unmatched_threshold"])

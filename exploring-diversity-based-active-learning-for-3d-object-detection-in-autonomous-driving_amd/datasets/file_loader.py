@@ -24,6 +24,10 @@ from .. import lib
 from ..detector_ops import build_voxelizer
 
 
+def _cfg_get(cfg, key):
+    return cfg[key] if isinstance(cfg, dict) else getattr(cfg, key)
+
+
 def usable_cores():
     """Cores this process may really use: affinity mask capped by the cgroup CPU quota."""
     n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
@@ -95,8 +99,16 @@ class FileSweepLoader:
     therefore not reproducible)."""
 
     def __init__(self, infos, voxel_cfg, anchors, batch_size=8, device="cuda", nsweeps=10, root=None, threads=8,
-                 indices=None, depth=2, min_distance=1.0, with_points=False, view=None):
+                 indices=None, depth=2, min_distance=1.0, with_points=False, view=None, with_targets=False, target_cfg=None):
         self.with_points = bool(with_points)   # also yield the padded point slots (``voxels``) for PillarFeatureNet
+        # also yield the training targets of every batch (``labels`` / ``reg_targets`` / ``reg_weights`` / ``gt_index`` per
+        # task, [B, A_t]...) from the infos' ``gt_boxes`` / ``gt_names``: one al3d_assign_targets_f32 launch per batch.
+        # ``target_cfg``: the config's ``assigner`` dict (box_coder, target_assigner, out_size_factor), as AssignTarget takes
+        self.with_targets = bool(with_targets)
+        if self.with_targets and target_cfg is None:
+            raise ValueError("with_targets=True needs target_cfg (the config's assigner dict)")
+        self._target_cfg = target_cfg
+        self._target_plan = None
         # (flip_x, flip_y, rot, scale): the merged points of every batch are augmented in place before they are voxelized
         # (selector_ops.points_view_, CALD's second sweep); None launches nothing
         self.view = view
@@ -229,9 +241,30 @@ class FileSweepLoader:
         }
         if self.with_points:
             ex["voxels"] = v["voxels"]
+        if self.with_targets:
+            ex.update(self._targets(st.ids))
         if "point2voxel" in v:              # dynamic voxelizer: each point's row, what DynamicPillarFeatureNet pools by
             ex["point2voxel"] = v["point2voxel"]
         return ex
+
+    def _targets(self, ids):
+        """AssignTarget's train branch for the batch's frames (preprocess.py:380-479) from their infos.  A box whose name is
+        in no task keeps its row and matches nothing (the reference's Preprocess removes it beforehand, ``gt_boxes_mask``);
+        ``gt_index`` counts the info's own rows."""
+        from ..detector_ops import assign_targets
+        if self._target_plan is None:
+            from .target_assigner import build_assign_plan
+            gs = np.asarray(self.voxelizer.grid_size)
+            fm = [*(gs[:2] // _cfg_get(self._target_cfg, "out_size_factor")), 1][::-1]
+            self._target_plan, _ = build_assign_plan(self._target_cfg, fm, self.device)
+        nd = self._target_plan.n_dim
+        boxes, names = [], []
+        for i in ids:
+            g = np.asarray(self.infos[i]["gt_boxes"], dtype=np.float32).reshape(-1, 9)
+            boxes.append(np.ascontiguousarray(g if nd == 9 else g[:, [0, 1, 2, 3, 4, 5, 8]]))
+            names.append(self.infos[i]["gt_names"])
+        out = assign_targets(self._target_plan, boxes, gt_names=names)
+        return {k: out[k] for k in ("labels", "reg_targets", "reg_weights", "gt_index")}
 
     def __iter__(self):
         nb = len(self)

@@ -12,8 +12,9 @@ put into ``res`` are device tensors:
   ``res["lidar"]["voxels"] = dict(voxels, coordinates, num_points, num_voxels, shape)``
   (preprocess.py:259-304) via ``al3d_voxelize_mean_f32``; additionally ``voxel_features`` (the mean
   VFE the detector's reader would compute, voxel_encoder.py:206-211).
-* ``AssignTarget(cfg=...)`` (val branch) -- the constant anchors per task
-  (preprocess.py:346-378,426-431), generated once and cached on the device.
+* ``AssignTarget(cfg=...)`` -- the constant anchors per task (preprocess.py:346-378,426-431), generated once and cached
+  on the device; in train mode also ``labels`` / ``reg_targets`` / ``reg_weights`` per task (:380-479) from
+  ``al3d_assign_targets_f32``.
 * ``Reformat`` -- the ``example`` dict the detector reads (formating.py).
 ``collate_device`` is the device analogue of ``collate_kitti`` (collate.py:90-150).
 """
@@ -136,6 +137,10 @@ class Voxelization:
 
 @PIPELINES.register_module
 class AssignTarget:
+    """preprocess.py:307-483.  Val: the constant anchors.  Train (``res["mode"] == "train"`` with ``gt_boxes`` /
+    ``gt_classes`` / ``gt_names`` in ``res["lidar"]["annotations"]``): the annotations are split by task (:380-424) and
+    ``labels`` / ``reg_targets`` / ``reg_weights`` per task come from one ``detector_ops.assign_targets`` launch."""
+
     def __init__(self, **kwargs):
         cfg = kwargs["cfg"]
         ta = _get(cfg, "target_assigner")
@@ -143,11 +148,18 @@ class AssignTarget:
         self.anchor_generators = _get(ta, "anchor_generators")
         self.out_size_factor = _get(cfg, "out_size_factor")
         self.device = kwargs.get("device", "cuda")
+        self._cfg = cfg
         self._cache = {}
+        self._plans = {}
+
+    def _plan(self, key):
+        """-> (AssignPlan, TargetAssigner per task) of a feature map; built when training first asks for it."""
+        if key not in self._plans:
+            from .target_assigner import build_assign_plan
+            self._plans[key] = build_assign_plan(self._cfg, key, self.device)
+        return self._plans[key]
 
     def __call__(self, res, info):
-        if res.get("mode", "val") == "train":
-            raise NotImplementedError("al3d implements the inference sweep, not training")
         grid = np.asarray(res["lidar"]["voxels"]["shape"])
         fm = [*(grid[:2] // self.out_size_factor), 1][::-1]          # [1, H, W]
         key = tuple(int(v) for v in fm)
@@ -155,7 +167,38 @@ class AssignTarget:
             self._cache[key] = [torch.as_tensor(a, dtype=torch.float32, device=self.device)
                                 for a in generate_task_anchors(self.tasks, self.anchor_generators, list(key))]
         res["lidar"]["targets"] = dict(anchors=self._cache[key])
+        ann = res["lidar"].get("annotations")
+        if res.get("mode", "val") == "train" and isinstance(ann, dict) and all(k in ann for k in ("gt_boxes", "gt_classes", "gt_names")):
+            self._train(res, key)
         return res, info
+
+    def _train(self, res, key):
+        from ..detector_ops import assign_targets
+        from ..ops.box_np_ops import limit_period
+        gt_dict = res["lidar"]["annotations"]
+        plan, tas = self._plan(key)
+        gt_classes, gt_names = np.asarray(gt_dict["gt_classes"]), np.asarray(gt_dict["gt_names"])
+        gt_boxes = np.asarray(gt_dict["gt_boxes"], dtype=np.float32)
+        task_boxes, task_classes, task_names, flag = [], [], [], 0
+        for ta in tas:                                            # :383-411, boxes regrouped by class inside the task
+            masks = [np.where(gt_classes == i + 1 + flag) for i in range(len(ta.classes))]
+            task_boxes.append(np.concatenate([gt_boxes[m] for m in masks], axis=0))
+            task_classes.append(np.concatenate([gt_classes[m] - flag for m in masks]))
+            task_names.append(np.concatenate([gt_names[m] for m in masks]))
+            flag += len(masks)
+        for b in task_boxes:                                      # :413-417
+            b[:, -1] = limit_period(b[:, -1], offset=0.5, period=np.pi * 2)
+        gt_dict["gt_classes"], gt_dict["gt_names"], gt_dict["gt_boxes"] = task_classes, task_names, task_boxes
+        # one frame, every task: the class index is the box's class position among all classes (its name inside its task)
+        cls, first = [], 0
+        for ta, names in zip(tas, task_names):
+            cls.append(np.array([first + ta.classes.index(str(n)) if str(n) in ta.classes else -1 for n in names],
+                                dtype=np.int32))
+            first += len(ta.classes)
+        out = assign_targets(plan, [np.concatenate(task_boxes, axis=0)], gt_class=[np.concatenate(cls)], limit_angle=False,
+                             with_index=False)
+        res["lidar"]["targets"].update(labels=[v[0] for v in out["labels"]], reg_targets=[v[0] for v in out["reg_targets"]],
+                                       reg_weights=[v[0] for v in out["reg_weights"]])
 
 
 @PIPELINES.register_module
@@ -171,6 +214,9 @@ class Reformat:
                        voxel_features=v.get("voxel_features"))
         if "targets" in res["lidar"]:
             example["anchors"] = res["lidar"]["targets"]["anchors"]
+            for k in ("labels", "reg_targets", "reg_weights"):      # train mode (formating.py:45-57)
+                if k in res["lidar"]["targets"]:
+                    example[k] = res["lidar"]["targets"][k]
         return example, info
 
 

@@ -4,6 +4,7 @@ Activations are NHWC float32.  Weight packing helpers turn reference-layout
 parameters (``Conv2d.weight [Cout,Cin,k,k]``, ``ConvTranspose2d.weight [Cin,Cout,2,2]``,
 eval ``BatchNorm2d``) into the kernel layouts once, outside the hot loop.
 """
+import ctypes
 from typing import NamedTuple
 
 import torch
@@ -1447,3 +1448,141 @@ def box_planes(boxes):
     p0 = faces[:, :, 0]
     planes[..., 3] = -p0[..., 0] * planes[..., 0] - p0[..., 1] * planes[..., 1] - p0[..., 2] * planes[..., 2]
     return planes
+
+
+# ---- anchor target assignment (al3d_assign_targets_f32) -----------------------------------------------------------------
+class AssignClass(ctypes.Structure):
+    """``al3d_assign_class_t`` of include/al3d.h."""
+    _fields_ = [("out_base", ctypes.c_int64), ("anchor_begin", ctypes.c_int), ("num_loc", ctypes.c_int),
+                ("num_rot", ctypes.c_int), ("slot_offset", ctypes.c_int), ("slot_stride", ctypes.c_int),
+                ("task_anchors", ctypes.c_int), ("label", ctypes.c_int), ("matched", ctypes.c_float),
+                ("unmatched", ctypes.c_float)]
+
+
+class AssignPlan:
+    """What every frame shares: the anchors grouped by class with their near boxes on the device, and the class table.
+
+    ``tasks``: per task a list of ``dict(class_name, anchors, matched, unmatched)``, the class's anchors
+    ``[..., per-location anchors, n_dim]`` float32 numpy in the task's class order (``generate_anchors_dict``,
+    target_assigner.py:167-187).  ``anchors_bv`` is ``rbbox2d_to_near_bbox`` on the host (preprocess.py:367-370), once:
+    the pi/4 standing-or-lying decision and ``limit_period`` are the reference's own float32 arithmetic."""
+
+    def __init__(self, tasks, box_coder, device):
+        import numpy as np
+        from .ops.box_np_ops import rbbox2d_to_near_bbox
+        self.device = torch.device(device)
+        self.n_dim, self.code_size = int(box_coder.n_dim), int(box_coder.code_size)
+        self.vec_encode, self.linear_dim, self.norm_velo = bool(box_coder.vec_encode), bool(box_coder.linear_dim), \
+            bool(box_coder.norm_velo)
+        self.class_names, self.task_of, self.task_anchors, rows, flat = [], [], [], [], []
+        begin = 0
+        for t, classes in enumerate(tasks):
+            stride = sum(int(c["anchors"].shape[-2]) for c in classes)
+            slot, num_loc = 0, None
+            for k, c in enumerate(classes):
+                a = np.ascontiguousarray(c["anchors"], dtype=np.float32)
+                if a.shape[-1] != self.n_dim:
+                    raise lib.Al3dError(f"assign_targets: class {c['class_name']!r} has {a.shape[-1]}-column anchors, the box "
+                                        f"coder's n_dim is {self.n_dim}")
+                num_rot = int(a.shape[-2])
+                a = a.reshape(-1, num_rot, self.n_dim)
+                if num_loc is not None and a.shape[0] != num_loc:
+                    raise lib.Al3dError("assign_targets: the classes of one task must share the feature map")
+                num_loc = int(a.shape[0])
+                rows.append(dict(anchor_begin=begin, num_loc=num_loc, num_rot=num_rot, slot_offset=slot, slot_stride=stride,
+                                 task_anchors=num_loc * stride, label=k + 1, matched=float(np.float32(c["matched"])),
+                                 unmatched=float(np.float32(c["unmatched"]))))
+                flat.append(a.reshape(-1, self.n_dim))
+                self.class_names.append(c["class_name"])
+                self.task_of.append(t)
+                begin += num_loc * num_rot
+                slot += num_rot
+            self.task_anchors.append((num_loc or 0) * stride)
+        self.rows = rows
+        anchors = np.concatenate(flat, axis=0) if flat else np.zeros((0, self.n_dim), np.float32)
+        self.anchors_np = anchors
+        self.anchors_bv_np = np.ascontiguousarray(rbbox2d_to_near_bbox(anchors[:, [0, 1, 3, 4, -1]]), dtype=np.float32)
+        self.anchors = torch.from_numpy(anchors).to(self.device)
+        self.anchors_bv = torch.from_numpy(self.anchors_bv_np).to(self.device)
+        if len(set(self.class_names)) != len(self.class_names):
+            raise lib.Al3dError(f"assign_targets: a class name occurs twice in {self.class_names}: boxes are given to classes by name")
+        self.class_index = {n: i for i, n in enumerate(self.class_names)}
+        self._tables = {}
+
+    def table(self, B):
+        """-> (ctypes array of AssignClass for a batch of B frames, out_rows, per-task first row); kept per B."""
+        if B in self._tables:
+            return self._tables[B]
+        base, bases = 0, []
+        for n in self.task_anchors:
+            bases.append(base)
+            base += B * n
+        tab = (AssignClass * len(self.rows))()
+        for i, r in enumerate(self.rows):
+            tab[i] = AssignClass(out_base=bases[self.task_of[i]], **r)
+        self._tables[B] = (tab, base, bases)
+        return self._tables[B]
+
+
+def assign_targets(plan, gt_boxes, gt_names=None, gt_class=None, limit_angle=True, launch=None, with_index=True):
+    """``al3d_assign_targets_f32`` for a batch: AssignTarget's train branch (preprocess.py:396-479) for every frame and task
+    in one launch, nothing read back.
+
+    ``gt_boxes``: per frame ``[n_i, n_dim]`` float32 numpy; ``gt_names``: per frame the boxes' class names (a box whose name
+    no class carries is ignored, its row still counts) or ``gt_class``: per frame int indexes into ``plan.class_names``.
+    Like the reference the boxes pass ``limit_period(r, 0.5, 2 pi)`` (preprocess.py:413-417, ``limit_angle``) and
+    ``np.nan_to_num`` (target_assigner.py:97); their near boxes are the reference's numpy calls on the host.
+    -> ``dict(labels, reg_targets, reg_weights, gt_index)``, each a list over tasks of ``[B, A_t]`` (``[B, A_t, code_size]``)
+    device tensors, plus ``gt_overlap [R]`` and the host ``gt_off [B + 1]``.  ``launch``: (groups, threads, chunk)."""
+    import numpy as np
+    from .ops.box_np_ops import limit_period, rbbox2d_to_near_bbox
+    B, nd = len(gt_boxes), plan.n_dim
+    counts = [int(np.asarray(b).shape[0]) for b in gt_boxes]
+    gt_off = np.zeros(B + 1, dtype=np.int32)
+    np.cumsum(counts, out=gt_off[1:])
+    R = int(gt_off[-1])
+    boxes = np.zeros((R, nd), dtype=np.float32)
+    cls = np.full((R,), -1, dtype=np.int32)
+    for b in range(B):
+        if counts[b] == 0:
+            continue
+        g = np.asarray(gt_boxes[b])
+        if g.dtype != np.float32 or g.ndim != 2 or g.shape[1] != nd:
+            raise lib.Al3dError(f"assign_targets: frame {b}: gt_boxes [n, {nd}] float32 expected, got {g.dtype} {g.shape}")
+        boxes[gt_off[b]:gt_off[b + 1]] = g
+        if gt_class is not None:
+            cls[gt_off[b]:gt_off[b + 1]] = np.asarray(gt_class[b], dtype=np.int32)
+        else:
+            cls[gt_off[b]:gt_off[b + 1]] = [plan.class_index.get(str(n), -1) for n in gt_names[b]]
+    if limit_angle:
+        boxes[:, -1] = limit_period(boxes[:, -1], offset=0.5, period=np.pi * 2)
+    boxes = np.nan_to_num(boxes)
+    bv = np.ascontiguousarray(rbbox2d_to_near_bbox(boxes[:, [0, 1, 3, 4, -1]]), dtype=np.float32)
+    dev = plan.device
+    # one upload: [R, 4] near boxes (16-byte rows first), [R, n_dim] boxes, [R] class indexes
+    host = np.concatenate([bv.reshape(-1).view(np.int32), boxes.reshape(-1).view(np.int32), cls])
+    buf = torch.from_numpy(host).to(dev, non_blocking=True)
+    d_bv, d_boxes, d_cls = buf[:4 * R], buf[4 * R:(4 + nd) * R], buf[(4 + nd) * R:]
+    tab, out_rows, bases = plan.table(B)
+    labels = torch.empty((out_rows,), dtype=torch.int32, device=dev)
+    weights = torch.empty((out_rows,), dtype=torch.float32, device=dev)
+    targets = torch.empty((out_rows, plan.code_size), dtype=torch.float32, device=dev)
+    index = torch.empty((out_rows,), dtype=torch.int32, device=dev) if with_index else None
+    overlap = torch.empty((max(R, 1),), dtype=torch.float32, device=dev)
+    args = [_ptr(plan.anchors), _ptr(plan.anchors_bv), plan.anchors.shape[0], nd, tab, len(plan.rows),
+            _ptr(d_boxes) if R else None, _ptr(d_bv) if R else None, _ptr(d_cls) if R else None, R,
+            gt_off.ctypes.data_as(ctypes.c_void_p), B, int(plan.vec_encode), int(plan.linear_dim), int(plan.norm_velo),
+            _ptr(labels), _ptr(targets), _ptr(weights), _ptr(index) if with_index else None, out_rows, _ptr(overlap)]
+    if launch is None:
+        lib.call("al3d_assign_targets_f32", *args, _stream())
+    else:
+        lib.call("al3d_assign_targets_launch_f32", *args, *(int(v) for v in launch), _stream())
+    out = dict(labels=[], reg_targets=[], reg_weights=[], gt_index=[], gt_overlap=overlap[:R], gt_off=gt_off)
+    for t, n in enumerate(plan.task_anchors):
+        s = slice(bases[t], bases[t] + B * n)
+        out["labels"].append(labels[s].view(B, n))
+        out["reg_weights"].append(weights[s].view(B, n))
+        out["reg_targets"].append(targets[s].view(B, n, plan.code_size))
+        if with_index:
+            out["gt_index"].append(index[s].view(B, n))
+    return out

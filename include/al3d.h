@@ -1361,6 +1361,62 @@ int al3d_points_in_boxes_mask_u8(const float* points, int64_t P, int F, const fl
 int al3d_points_in_boxes_mask_launch_u8(const float* points, int64_t P, int F, const float* planes, int R, unsigned char* out,
                                         int threads, int tile, void* stream);
 
+/* ---------------------------------------------------------------- anchor target assignment (AssignTarget, train mode)
+ * Replace the per-sample, per-class numpy / numba loop of det3d/datasets/pipelines/preprocess.py:450-479:
+ * TargetAssigner.assign_v2 (det3d/core/anchor/target_assigner.py:68-142) over create_target_np (target_ops.py:28-222, with
+ * positive_fraction=None, prune_anchor_fn=None, norm_by_num_examples=False), NearestIouSimilarity = iou_jit(eps=0) on near
+ * boxes (box_np_ops.py:957-996) and GroundBox3dCoder.encode = second_box_encode (box_np_ops.py:54-114), for a batch of
+ * frames and every task in one launch (frames beyond 256 take one more launch per 256).
+ * Input, shared by the frames: anchors [A, n_dim] f32 (n_dim 7 or 9: x y z w l h [vx vy] r), grouped by anchor class, class
+ * c's anchors in (location, rotation) order; anchors_bv [A, 4] f32 their near boxes (rbbox2d_to_near_bbox, :345-357, built
+ * on the host), 16-byte aligned.  classes [num_classes] is HOST memory (num_classes <= AL3D_ASSIGN_MAX_CLASSES), see
+ * al3d_assign_class_t.  Per frame a ragged list: gt_boxes [R, n_dim], gt_bv [R, 4] f32 (16-byte aligned), gt_class [R] i32 =
+ * the index into `classes` (any other value: the box belongs to no class and is ignored), gt_off [B+1] i32 in HOST memory,
+ * ascending inside [0, R].  vec_encode / linear_dim / norm_velo: the coder's encode_angle_to_vector / smooth_dim / norm_velo.
+ * Output, per task t one [B, A_t] block that starts at row out_base of each buffer, A_t = num_loc * slot_stride, the anchor
+ * order assign_v2's (y, x, class within the task, rotation): labels [out_rows] i32 (-1 ignore, 0 background, the class's
+ * label where foreground), reg_targets [out_rows, code_size] f32 (code_size = n_dim + vec_encode; zeros where the anchor is
+ * not encoded), reg_weights [out_rows] f32 (1 where the label is > 0), gt_index [out_rows] i32 (may be null) = the row, within
+ * the frame's list, of the box the anchor is encoded against, -1 elsewhere (create_target_np's positive_gt_id);
+ * gt_overlap [R] f32 = every box's largest overlap with an anchor of its class (gt_to_anchor_max; 0 for a box of no class).
+ * Rules, per (frame, class), on that class's boxes in list order: overlap = iou_jit's float32 operations in its order (no
+ * fused multiply-add); an anchor's box is the FIRST maximum of its row (strict >); every anchor whose overlap with a box
+ * equals that box's positive column maximum is forced foreground, ties included, and is encoded against its OWN argmax box;
+ * label: max >= matched foreground, then max < unmatched background, then the forced ones foreground again, else -1; a class
+ * with no box in the frame is all background.  The encode's + - * / sqrt are correctly rounded.  The overlap matrix is
+ * never stored, nothing is read back, and every output is bit-identical from run to run and for every launch shape.
+ * AL3D_EINVAL: n_dim not 7 / 9, a negative count, gt_off not ascending inside [0, R], a class whose anchor range overruns A,
+ * whose slot overruns its task or whose output block overruns out_rows, a label < 1, a bad launch shape.
+ * _launch: groups (workgroups; a (frame, class) pair is one workgroup's, pairs beyond `groups` by grid stride) in [1, 65536],
+ * threads a multiple of 64 in [64, 1024], chunk (a class's boxes in LDS at a time) in [1, AL3D_ASSIGN_CHUNK]. */
+typedef struct {
+    int64_t out_base;      /* first row of the task's [B, A_t] block in labels / reg_weights / gt_index / reg_targets */
+    int anchor_begin;      /* first row of the class in anchors / anchors_bv */
+    int num_loc;           /* feature-map locations (z * y * x) */
+    int num_rot;           /* the class's anchors per location (sizes x rotations) */
+    int slot_offset;       /* where the class starts on the task's per-location anchor axis */
+    int slot_stride;       /* the task's anchors per location */
+    int task_anchors;      /* A_t = num_loc * slot_stride */
+    int label;             /* the class id within its task, >= 1 */
+    float matched;         /* foreground at max >= matched */
+    float unmatched;       /* background at max < unmatched */
+} al3d_assign_class_t;
+#define AL3D_ASSIGN_MAX_CLASSES 32
+#define AL3D_ASSIGN_GROUPS 4096
+#define AL3D_ASSIGN_THREADS 512
+#define AL3D_ASSIGN_CHUNK 256
+int al3d_assign_targets_f32(const float* anchors, const float* anchors_bv, int64_t A, int n_dim,
+                            const al3d_assign_class_t* classes, int num_classes, const float* gt_boxes, const float* gt_bv,
+                            const int* gt_class, int64_t R, const int* gt_off, int B, int vec_encode, int linear_dim,
+                            int norm_velo, int* labels, float* reg_targets, float* reg_weights, int* gt_index,
+                            int64_t out_rows, float* gt_overlap, void* stream);
+int al3d_assign_targets_launch_f32(const float* anchors, const float* anchors_bv, int64_t A, int n_dim,
+                                   const al3d_assign_class_t* classes, int num_classes, const float* gt_boxes,
+                                   const float* gt_bv, const int* gt_class, int64_t R, const int* gt_off, int B,
+                                   int vec_encode, int linear_dim, int norm_velo, int* labels, float* reg_targets,
+                                   float* reg_weights, int* gt_index, int64_t out_rows, float* gt_overlap, int groups,
+                                   int threads, int chunk, void* stream);
+
 /* ---------------------------------------------------------------- runtime
  * A HIP stream restricted to n_cus compute units starting at first_cu (hipExtStreamCreateWithCUMask); the
  * reference has no analogue (its loader workers are host processes, det3d/datasets/loader/build_loader.py:23-59):
