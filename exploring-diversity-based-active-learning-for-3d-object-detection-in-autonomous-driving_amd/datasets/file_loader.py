@@ -99,7 +99,8 @@ class FileSweepLoader:
     therefore not reproducible)."""
 
     def __init__(self, infos, voxel_cfg, anchors, batch_size=8, device="cuda", nsweeps=10, root=None, threads=8,
-                 indices=None, depth=2, min_distance=1.0, with_points=False, view=None, with_targets=False, target_cfg=None):
+                 indices=None, depth=2, min_distance=1.0, with_points=False, view=None, with_targets=False, target_cfg=None,
+                 train_cfg=None):
         self.with_points = bool(with_points)   # also yield the padded point slots (``voxels``) for PillarFeatureNet
         # also yield the training targets of every batch (``labels`` / ``reg_targets`` / ``reg_weights`` / ``gt_index`` per
         # task, [B, A_t]...) from the infos' ``gt_boxes`` / ``gt_names``: one al3d_assign_targets_f32 launch per batch.
@@ -109,6 +110,18 @@ class FileSweepLoader:
             raise ValueError("with_targets=True needs target_cfg (the config's assigner dict)")
         self._target_cfg = target_cfg
         self._target_plan = None
+        # ``train_cfg``: the config's ``train_preprocessor`` dict.  Every batch then goes through ONE
+        # datasets.augment.augment_batch between the sweep merge and the voxelizer (GT-AUG sampling, per-object noise, flips,
+        # global rotation / scale, shuffle), the boxes through Voxelization's range filter, and the targets are assigned from
+        # the boxes that are left; ``gt_boxes`` / ``gt_names`` / ``gt_classes`` per frame join the example.  The sampler's
+        # ``.bin`` paths are relative to ``root``.  Costs one more host read per batch (the merged frames' sizes).
+        self._train_aug = None
+        if train_cfg is not None:
+            if not self.with_targets:
+                raise ValueError("train_cfg needs with_targets=True")
+            from .augment import TrainAugmenter
+            self._train_aug = TrainAugmenter(train_cfg)
+            self._bv_range = np.array(_cfg_get(voxel_cfg, "range"), dtype=np.float32)[[0, 1, 3, 4]]
         # (flip_x, flip_y, rot, scale): the merged points of every batch are augmented in place before they are voxelized
         # (selector_ops.points_view_, CALD's second sweep); None launches nothing
         self.view = view
@@ -229,6 +242,9 @@ class FileSweepLoader:
         if self.view is not None:
             from ..selector_ops import points_view_
             points_view_(out[:st.total], self.view)
+        gt = None
+        if self._train_aug is not None:
+            out, frame_off, gt = self._augment(st.ids, out, frame_off)
         v = self.voxelizer(out, frame_off, want_voxels=self.with_points)
         gs = self.voxelizer.grid_size
         ex = {
@@ -242,12 +258,32 @@ class FileSweepLoader:
         if self.with_points:
             ex["voxels"] = v["voxels"]
         if self.with_targets:
-            ex.update(self._targets(st.ids))
+            ex.update(self._targets(st.ids, gt))
+            if gt is not None:
+                ex.update(gt_boxes=[g["gt_boxes"] for g in gt], gt_names=[g["gt_names"] for g in gt],
+                          gt_classes=[g["gt_classes"] for g in gt])
         if "point2voxel" in v:              # dynamic voxelizer: each point's row, what DynamicPillarFeatureNet pools by
             ex["point2voxel"] = v["point2voxel"]
         return ex
 
-    def _targets(self, ids):
+    def _augment(self, ids, points, frame_off):
+        """The train Preprocess of the batch's frames and Voxelization's range filter on their boxes (preprocess.py:57-256,
+        282-288) -> (points, frame offsets, per-frame annotations)."""
+        from .augment import augment_batch, filter_gt_box_outside_range
+        offs = frame_off.cpu().tolist()
+        frames = [dict(points=points[offs[b]:offs[b + 1]], boxes=np.asarray(self.infos[i]["gt_boxes"]).astype(np.float32),
+                       names=self.infos[i]["gt_names"], image_prefix=self.root, num_point_features=5, flip_both=True)
+                  for b, i in enumerate(ids)]
+        gt = augment_batch(frames, self._train_aug)
+        for g in gt:
+            g.pop("points")
+            mask = filter_gt_box_outside_range(g["gt_boxes"], self._bv_range)
+            for k in g:
+                g[k] = g[k][mask]
+        off = torch.from_numpy(self._train_aug.batch_offsets).to(self.device)
+        return self._train_aug.batch_points, off, gt
+
+    def _targets(self, ids, gt=None):
         """AssignTarget's train branch for the batch's frames (preprocess.py:380-479) from their infos.  A box whose name is
         in no task keeps its row and matches nothing (the reference's Preprocess removes it beforehand, ``gt_boxes_mask``);
         ``gt_index`` counts the info's own rows."""
@@ -259,10 +295,10 @@ class FileSweepLoader:
             self._target_plan, _ = build_assign_plan(self._target_cfg, fm, self.device)
         nd = self._target_plan.n_dim
         boxes, names = [], []
-        for i in ids:
-            g = np.asarray(self.infos[i]["gt_boxes"], dtype=np.float32).reshape(-1, 9)
+        for b, i in enumerate(ids):
+            g = np.asarray(self.infos[i]["gt_boxes"] if gt is None else gt[b]["gt_boxes"], dtype=np.float32).reshape(-1, 9)
             boxes.append(np.ascontiguousarray(g if nd == 9 else g[:, [0, 1, 2, 3, 4, 5, 8]]))
-            names.append(self.infos[i]["gt_names"])
+            names.append(self.infos[i]["gt_names"] if gt is None else gt[b]["gt_names"])
         out = assign_targets(self._target_plan, boxes, gt_names=names)
         return {k: out[k] for k in ("labels", "reg_targets", "reg_weights", "gt_index")}
 

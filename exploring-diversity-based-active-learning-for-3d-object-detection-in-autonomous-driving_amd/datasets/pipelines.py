@@ -65,28 +65,61 @@ class LoadPointCloudFromFile:
 
 @PIPELINES.register_module
 class LoadPointCloudAnnotations:
-    """Val-mode pass-through: the sweep never reads annotations (loading.py:163-199 fills
-    ``res["lidar"]["annotations"]`` for training); kept so reference pipelines load unchanged."""
+    """loading.py:166-180.  Val mode is a pass-through (the sweep never reads annotations); with ``res["mode"] == "train"``
+    the nuScenes annotations of the info go to ``res["lidar"]["annotations"]`` as float32, for ``Preprocess``."""
 
     def __init__(self, with_bbox=True, **kwargs):
         pass
 
     def __call__(self, res, info):
+        if res.get("mode") == "train" and res.get("type") in ("NuScenesDataset", "LyftDataset") and "gt_boxes" in info:
+            res["lidar"]["annotations"] = {
+                "boxes": np.asarray(info["gt_boxes"]).astype(np.float32),
+                "names": info["gt_names"],
+                "tokens": info.get("gt_boxes_token"),
+                "velocities": np.asarray(info["gt_boxes_velocity"]).astype(np.float32) if "gt_boxes_velocity" in info else None,
+            }
         return res, info
 
 
 @PIPELINES.register_module
 class Preprocess:
-    """Val branch of preprocess.py:33-257: NuScenes points become the 5-column ``combined`` cloud;
-    no shuffling, no filtering, no augmentation."""
+    """preprocess.py:29-257.  Val: NuScenes points become the 5-column ``combined`` cloud; no shuffling, no filtering, no
+    augmentation.  Train (:57-256): GT-AUG sampling, the per-object noise, flips, global rotation and scale, shuffle and
+    ``symmetry_intensity`` through ``datasets.augment.augment_batch`` -- numpy's draws in the reference's order, the boxes
+    on the host, the points in one fused launch; ``res["lidar"]["annotations"]`` becomes ``gt_boxes`` / ``gt_names`` /
+    ``gt_classes``."""
 
     def __init__(self, cfg=None, **kwargs):
         self.mode = _get(cfg, "mode") if cfg is not None else "val"
+        self.device = kwargs.get("device", "cuda")
+        self._aug = None
         if self.mode == "train":
-            raise NotImplementedError("al3d implements the inference sweep, not training")
+            from .augment import TrainAugmenter
+            self._aug = TrainAugmenter(cfg)
+
+    def _train(self, res):
+        from .augment import augment_batch
+        nusc = res["type"] == "NuScenesDataset"
+        points = res["lidar"]["combined"] if nusc else res["lidar"]["points"]
+        if not isinstance(points, torch.Tensor):
+            points = torch.as_tensor(np.ascontiguousarray(points, dtype=np.float32))
+        points = points.to(self.device).contiguous()
+        anno = res["lidar"]["annotations"]
+        frame = dict(points=points, boxes=anno["boxes"], names=anno["names"], difficulty=anno.get("difficulty"),
+                     image_prefix=res["metadata"]["image_prefix"], num_point_features=res["metadata"]["num_point_features"],
+                     flip_both=nusc, calib=res.get("calib"))
+        out = augment_batch([frame], self._aug, keep_debug=bool(res.get("keep_debug")))[0]
+        res["lidar"]["points"] = out.pop("points")
+        if nusc:
+            res["lidar"]["combined"] = res["lidar"]["points"]            # what Voxelization reads
+        res["lidar"]["annotations"] = out
 
     def __call__(self, res, info):
         res["mode"] = self.mode
+        if self.mode == "train":
+            self._train(res)
+            return res, info
         if res.get("type") in ("NuScenesDataset", "LyftDataset") and res["lidar"].get("combined") is not None:
             res["lidar"]["points"] = res["lidar"]["combined"]
         return res, info
@@ -112,8 +145,13 @@ class Voxelization:
         return self._vox
 
     def __call__(self, res, info):
-        if res.get("mode", "val") == "train":
-            raise NotImplementedError("al3d implements the inference sweep, not training")
+        if res.get("mode", "val") == "train":                        # preprocess.py:282-288
+            from .augment import filter_gt_box_outside_range
+            gt_dict = res["lidar"]["annotations"]
+            bv_range = np.array(self.range, dtype=np.float32)[[0, 1, 3, 4]]
+            mask = filter_gt_box_outside_range(gt_dict["gt_boxes"], bv_range)
+            for k in gt_dict:
+                gt_dict[k] = gt_dict[k][mask]
         pts = res["lidar"].get("combined")
         if pts is None:
             pts = res["lidar"]["points"]
@@ -221,10 +259,12 @@ class Reformat:
 
 
 class SweepDataset:
-    """Minimal val-mode dataset (reference NuScenesDataset.get_sensor_data,
+    """Minimal dataset (val by default; ``mode="train"`` sets ``res["mode"]`` up front, nuscenes.py:156-172) (reference NuScenesDataset.get_sensor_data,
     det3d/datasets/nuscenes/nuscenes.py:139-170): ``dataset[i]`` runs the pipeline on ``infos[i]``."""
 
-    def __init__(self, infos, pipeline, nsweeps=10, class_names=None, **kwargs):
+    def __init__(self, infos, pipeline, nsweeps=10, class_names=None, mode="val", root_path=None, **kwargs):
+        self.mode = mode                                              # "train": the loaders fill the annotations
+        self.root_path = root_path                                    # image_prefix: where the sampler finds its .bin files
         self.infos = infos
         self.nsweeps = nsweeps
         self.class_names = class_names
@@ -236,8 +276,8 @@ class SweepDataset:
     def __getitem__(self, idx):
         info = self.infos[idx]
         res = {"lidar": {"type": "lidar", "points": None, "nsweeps": self.nsweeps, "annotations": None},
-               "metadata": {"image_prefix": None, "num_point_features": 5, "token": info.get("token")},
-               "calib": None, "cam": {}, "mode": "val"}
+               "metadata": {"image_prefix": self.root_path, "num_point_features": 5, "token": info.get("token")},
+               "calib": None, "cam": {}, "mode": self.mode}
         data, _ = self.pipeline(res, info)
         return data
 

@@ -1417,6 +1417,83 @@ int al3d_assign_targets_launch_f32(const float* anchors, const float* anchors_bv
                                    float* reg_weights, int* gt_index, int64_t out_rows, float* gt_overlap, int groups,
                                    int threads, int chunk, void* stream);
 
+/* ---------------------------------------------------------------- train-mode Preprocess: GT-AUG noise and the point pass
+ * Replace the numba loops of the reference's train Preprocess (det3d/datasets/pipelines/preprocess.py:163-247) for a batch of
+ * frames.  The frames' boxes are back to back, box_off [B+1] i32 ascending inside [0, R]; the points likewise, point_off
+ * [B+1] i64.  Every output is bit-identical from run to run and for every launch shape; no float atomics.  *status (device
+ * int, written by every entry): a frame with bad offsets or an exceeded limit sets its bit, counts as empty, and nothing of
+ * it is read or written.  _launch: groups (workgroups per frame) in [1, 1024], threads 64 / 128 / 256, tile in [1, 64].
+ *
+ * (a) al3d_noise_per_box_f32 = noise_per_box (det3d/core/sampler/preprocess.py:238-267) with box_collision_test (:876-959:
+ *     the stand-up rejection with > 0, the 4 x 4 strict segment test, the two containment tests with cross >= 0, and
+ *     coll_mat[0, i] = False), one workgroup per frame (`groups` is only checked), boxes strictly in row order, `tile` tries at
+ *     a time.  corners [R, 4, 2] f32 and centres [R, 2] f32 (the host's box2d_to_corner_jit, box_np_ops.py:503-521),
+ *     valid_mask [R] u8, rot_cos / rot_sin [R, T] f32 (evaluated in double and rounded, as _rotation_box2d_jit_ :206-213 stores
+ *     them), loc_noises [R, T, 3] f64 (x, y used here, z by (b)).  A try's corners: corner - centre; x*c + y*s and x*(-s) + y*c,
+ *     every product and sum rounded to float32; + (centre + loc) evaluated in double, rounded once.  selected [R] i32 = the
+ *     smallest try without a collision, or -1 (also for a box that is not valid).  Limits: a frame's boxes <=
+ *     AL3D_AUG_MAX_BOXES (corners resident in LDS), 1 <= T <= AL3D_AUG_MAX_TRIES. */
+#define AL3D_AUG_BAD_POINT_OFF 1
+#define AL3D_AUG_BAD_BOX_OFF 2
+#define AL3D_AUG_FRAME_TOO_LARGE 4
+#define AL3D_AUG_BAD_WORKSPACE 8
+#define AL3D_AUG_BAD_ROWS 16
+#define AL3D_AUG_TOO_MANY_BOXES 32
+#define AL3D_AUG_BAD_TRIES 64
+#define AL3D_AUG_BAD_SAMPLED_OFF 128
+#define AL3D_AUG_BAD_SELECTED 256
+#define AL3D_AUG_MAX_BOXES 1024
+#define AL3D_AUG_MAX_TRIES 256
+#define AL3D_AUG_GROUPS 32
+#define AL3D_AUG_THREADS 256
+#define AL3D_AUG_NOISE_TILE 4
+int al3d_noise_per_box_f32(const float* corners, const float* centres, const unsigned char* valid_mask, const float* rot_cos,
+                           const float* rot_sin, const double* loc_noises, const int* box_off, int B, int R, int T,
+                           int* selected, int* status, void* stream);
+int al3d_noise_per_box_launch_f32(const float* corners, const float* centres, const unsigned char* valid_mask,
+                                  const float* rot_cos, const float* rot_sin, const double* loc_noises, const int* box_off,
+                                  int B, int R, int T, int* selected, int* status, int groups, int threads, int tile,
+                                  void* stream);
+/* (b) The fused point pass.  points [P, F] f32 (F >= 3), per frame the sampled objects' points first, then the scene points;
+ *     sampled_off [B] i64 = the number of sampled points of each frame.  Membership is the sign rule of "points in boxes"
+ *     above on planes [R, 6, 4] f32 built by detector_ops.box_planes; every test is on the point's ORIGINAL coordinates.
+ *     al3d_augment_points_count_f32 (pipelines/preprocess.py:178-180, remove_points_after_sample): drop_mask [P] u8 = a scene
+ *     point inside any box of drop_planes [R, 6, 4] / drop_off [B+1] (the sampled boxes); kept [B] i32 = the frame's points
+ *     that stay; workspace (al3d_augment_points_workspace_bytes(B, groups, threads), -1 for bad arguments) receives the
+ *     scanned per-wave partial counts.  Only needed when something can be dropped.
+ *     al3d_augment_points_f32: drop_mask / workspace as the count entry left them for the same points, offsets, groups and
+ *     threads (else AL3D_AUG_BAD_WORKSPACE), or both null: nothing is dropped.  Owner = the first box in row order with
+ *     valid_mask whose planes hold the point (points_transform_, sampler/preprocess.py:450-467): p - c (centres [R, 3] f32),
+ *     the z rotation with rot_cos / rot_sin[r, selected[r]], + c, then + loc_noises[r, selected[r]] in double rounded once;
+ *     selected[r] == -1 takes angle 0 and zero offset, still through (p - c) + c.  Then the double flip (random_flip_both
+ *     :829-854; flip [B, 2] u8 = (y = -y, x = -x), may be null), the global rotation (box_np_ops.py:396-418) and scale
+ *     (global_scaling_v2 :857-861) with global_xf [B, 3] f32 = (cos, sin, scale), and with `symmetry` the last column - 0.5
+ *     (pipelines/preprocess.py:246-247).  Destination: out [out_rows, F], frame b's rows [out_off[b], out_off[b+1]); the
+ *     point with rank k among the frame's kept points (original order) goes to row out_off[b] + rows[out_off[b] + k]
+ *     (rows [out_rows] i32, the shuffle; null = k).  A rank or row outside the frame's range is not written and sets
+ *     AL3D_AUG_BAD_ROWS.  owner [P] i32 (may be null) = the owning box's row within its frame, or -1. */
+int64_t al3d_augment_points_workspace_bytes(int B, int groups, int threads);
+int al3d_augment_points_count_f32(const float* points, int64_t P, int F, const int64_t* point_off, const int64_t* sampled_off,
+                                  int B, const float* drop_planes, const int* drop_off, int R, unsigned char* drop_mask,
+                                  int* kept, void* workspace, int* status, void* stream);
+int al3d_augment_points_count_launch_f32(const float* points, int64_t P, int F, const int64_t* point_off,
+                                         const int64_t* sampled_off, int B, const float* drop_planes, const int* drop_off,
+                                         int R, unsigned char* drop_mask, int* kept, void* workspace, int* status, int groups,
+                                         int threads, int tile, void* stream);
+int al3d_augment_points_f32(const float* points, int64_t P, int F, const int64_t* point_off, int B,
+                            const unsigned char* drop_mask, const void* workspace, const float* planes, const int* box_off,
+                            int R, const unsigned char* valid_mask, const float* centres, const float* rot_cos,
+                            const float* rot_sin, const double* loc_noises, const int* selected, int T,
+                            const unsigned char* flip, const float* global_xf, int symmetry, const int64_t* out_off,
+                            const int* rows, float* out, int64_t out_rows, int* owner, int* status, void* stream);
+int al3d_augment_points_launch_f32(const float* points, int64_t P, int F, const int64_t* point_off, int B,
+                                   const unsigned char* drop_mask, const void* workspace, const float* planes,
+                                   const int* box_off, int R, const unsigned char* valid_mask, const float* centres,
+                                   const float* rot_cos, const float* rot_sin, const double* loc_noises, const int* selected,
+                                   int T, const unsigned char* flip, const float* global_xf, int symmetry,
+                                   const int64_t* out_off, const int* rows, float* out, int64_t out_rows, int* owner,
+                                   int* status, int groups, int threads, int tile, void* stream);
+
 /* ---------------------------------------------------------------- runtime
  * A HIP stream restricted to n_cus compute units starting at first_cu (hipExtStreamCreateWithCUMask); the
  * reference has no analogue (its loader workers are host processes, det3d/datasets/loader/build_loader.py:23-59):
